@@ -20,14 +20,19 @@ blocks, LeakyReLU MLP conditioner [256,256], Laplace base) at batch 65536 per GP
     (image configurations: --base radial|laplace, --radial-norm lognormal|gammamm, --prior-scale choose the base / prior;
      mnist_image / cifar_image default to the Laplace base of rounds 2-3, the *_live ones to their YAML's radial base)
 
-With no flags at N = 1 the line also carries an "also" block: the other BASELINE configurations, the image models and the
-training steps measured in the same process after the headline (bounded steps each), so that every number DESIGN.md quotes
-has the driver's clock around it.
-
 One "step" = one full pass of the hot path over this rank's resident batch (inputs already in HBM)
-+ the scalar mean-log_prob all-reduce.  Prints ONE JSON line (rank 0) with the whole-job
-throughput, the roofline of the dominant kernel (HIP-event timed inside the timed region) and a
-CPU baseline (the oracle; rank 0 at N=1 only)."""
++ the scalar mean-log_prob all-reduce.  Prints ONE JSON line (rank 0) with the whole-job throughput.
+
+A plain run sets up, warms up, times the --steps steps and prints the line; nothing else.  --full adds what the
+headline does not need: the roofline of the dominant kernel (HIP events on sampled steps of the timed region, the MFMA
+probe and clock meter behind it), the opt-in fp16x2 mode, the CPU baseline (the oracle; rank 0 at N=1 only), parity
+checks, the warm re-prep -- and, with no other flags at N = 1, an "also" block: the other BASELINE configurations, the
+image models and the training steps measured in the same process after the headline (bounded steps each), so that every
+number DESIGN.md quotes has the driver's clock around it.
+
+--dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, at most
+64 MB in all: larger outputs as a fixed, seeded sample of their elements); the inputs are seeded, so two builds run
+with the same arguments can be compared output for output."""
 import argparse
 import json
 import os
@@ -130,7 +135,15 @@ def parse_args(argv=None):
     ap.add_argument("--device", choices=["cuda", "cpu"], default="cuda",
                     help="cpu: PLUMBING TEST of the launcher / collective path on gloo with the torch composite "
                          "formulation -- the line says so and is not a measurement")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: roofline / per-kernel times, the fp16x2 mode, CPU baseline, "
+                         "parity checks, warm re-prep and (default line at N = 1) the \"also\" block; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: the last step's outputs as DIR/<name>.npy (rank 0; at most 64 MB in all)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def free_port() -> int:
@@ -163,9 +176,12 @@ def main():
     os.dup2(2, 1)
     try:
         out = run_config(args, under_launcher)
-        if out is not None:
-            default_line = (len(sys.argv) == 1 or all(a.split("=")[0] in ("--gpus", "--steps", "--warmup") or a.lstrip("-").isdigit()
-                                                     for a in sys.argv[1:]))
+        if out is not None and args.dump_outputs:
+            dump_outputs(args.dump_outputs, args.outputs)
+        if out is not None and args.full:
+            defaults = vars(parse_args([]))
+            default_line = all(v == defaults[k] for k, v in vars(args).items()
+                               if k in defaults and k not in ("gpus", "steps", "warmup", "full", "dump_outputs"))
             if default_line and args.gpus == 1 and not under_launcher and not args.no_also and args.device == "cuda":
                 out["also"] = run_also(args)
     finally:
@@ -222,6 +238,29 @@ ALSO = [
 ]
 
 
+DUMP_BUDGET_BYTES = 64 << 20      # --dump-outputs: all arrays together
+
+
+def step_outputs(args, **arrays):
+    """keep what the timed path returned in its last step for --dump-outputs (host copies)"""
+    args.outputs = {k: v.detach().cpu() for k, v in arrays.items() if v is not None}
+
+
+def dump_outputs(path, arrays):
+    """DIR/<name>.npy per output, float32 (float64 where the path returns float64).  An array over its share of
+    DUMP_BUDGET_BYTES is written as a fixed sample of its flattened elements (seeded, sorted indices), the same in every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        cap = share // t.element_size()
+        if t.numel() > cap:
+            idx = torch.randint(0, t.numel(), (cap,), generator=torch.Generator().manual_seed(0)).unique()
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), t.numpy())
+
+
 _TRAIN_WGRADS = ("usf_wgrad_f32", "usf_wgrad_bias_f32", "usf_wgrad_planes_f32", "usf_wgrad_blocked_f32")
 _TRAIN_TIMED = _TRAIN_WGRADS + ("usf_gemm_planes_bf16x3", "usf_coupling_planes", "usf_coupling_additive_f32", "usf_linear_f32",
                                 "usf_pack_planes_f32", "usf_run_ops", "usf_gemm_f64", "usf_pack_weights_f32", "usf_pack_weights_t_f32")
@@ -243,7 +282,7 @@ def run_also(args):
             out.append(rec)
             continue
         try:
-            a = parse_args(argv)
+            a = parse_args(argv + ["--full"])
             if a.config == "cfg4":
                 a.probe_rows = _golden_probe("synth_d3072_k48_cfg4", a.seed)
             elif a.golden:
@@ -309,6 +348,7 @@ def main_flat(args, under_launcher):
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1")) if under_launcher else 1
     on_gpu = args.device == "cuda"
+    full = args.full
     import torch.distributed as dist
     backend = None
     own_group = False
@@ -444,10 +484,11 @@ def main_flat(args, under_launcher):
     # per-launch HIP events: on every TIMING_EVERY-th step of the timed region (first step included).  Two event records per
     # launch on all 66 launches of every step cost the cfg2 step 2 % (18.55 vs 18.18 ms, same box): the headline would measure
     # its own instrumentation; sampled, the events cost 0.5 % and still see >= 160 launches of the dominant kernel
-    timing_on = on_gpu and not args.no_kernel_timing and mode not in ("train", "fit")
+    timing_on = full and on_gpu and not args.no_kernel_timing and mode not in ("train", "fit")
+    train_timing = full and on_gpu and not args.no_kernel_timing and mode == "train"
     timed_launch_steps = [0]
     op_records = []
-    if on_gpu and not args.no_kernel_timing and mode == "train":
+    if train_timing:
         from usflows_amd import _ext as _ext_t
         # HIP events around the launches of the training step's kernel classes -- on every TIMING_EVERY-th step only (two event records
         # around each of the ~430 launches cost the 68 ms step 3.5 ms)
@@ -461,7 +502,7 @@ def main_flat(args, under_launcher):
         if timing_on and i_step % TIMING_EVERY == 0:
             eng.op_timing = op_records
             timed_launch_steps[0] += 1
-        if on_gpu and not args.no_kernel_timing and mode == "train":
+        if train_timing:
             _ext_t.launch_timing = train_events if i_step % TIMING_EVERY == 0 else None
             train_timed_steps += 1 if i_step % TIMING_EVERY == 0 else 0
         mean, lp = step()
@@ -476,7 +517,7 @@ def main_flat(args, under_launcher):
     if on_gpu:
         timing = op_records if timing_on else None
         eng.op_timing = None
-        if mode == "train" and not args.no_kernel_timing:
+        if train_timing:
             from usflows_amd import _ext as _ext_t
             _ext_t.launch_timing = None
             wg_timing = [(e0, e1, a, fn) for fn in _TRAIN_WGRADS for e0, e1, a in train_events[fn]]
@@ -487,12 +528,21 @@ def main_flat(args, under_launcher):
     elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
     value = global_rows * args.steps / elapsed
+    if rank == 0 and args.dump_outputs:
+        # what the caller of the timed path received in the last step: per-row log_prob and its mean / the drawn samples / the
+        # loss and the updated parameters
+        if mode == "sample":
+            step_outputs(args, samples=lp)
+        elif mode == "log_prob":
+            step_outputs(args, log_prob=lp, mean_log_prob=mean)
+        else:
+            step_outputs(args, loss=-mean, parameters=torch.cat([p_.detach().reshape(-1).float() for p_ in flow.parameters()]))
 
     # ---- opt-in fast mode, measured beside the headline (same process, same inputs, every rank): the planes pipeline
     # with fp16x2 planes -- 22 significant bits per operand instead of 24, three MFMAs per product instead of six.
     # NOT the headline: `value` above is the default (bf16x3) mode.
     fast = None
-    if on_gpu and mode == "log_prob" and args.gemm is None and not args.no_fast_mode:
+    if full and on_gpu and mode == "log_prob" and args.gemm is None and not args.no_fast_mode:
         lp_default = lp.clone()
         eng.gemm_mode = "f16x2"
         for _ in range(3):
@@ -672,7 +722,7 @@ def main_flat(args, under_launcher):
 
     # ---- cfg5: UDL-preservation check of the drawn samples (rank 0, outside the timed region) ----
     udl = None
-    if mode == "sample" and on_gpu:
+    if full and mode == "sample" and on_gpu:
         with torch.no_grad():
             xs = lp[: min(B, 65536)]
             lpx = flow.log_prob(xs)
@@ -687,7 +737,7 @@ def main_flat(args, under_launcher):
     # ---- CPU baseline: the oracle (op-for-op torch-CPU restatement of the reference), rank 0 at N = 1 only ----
     cpu = None
     # (on the metric's configuration only: one oracle call at cfg4 re-inverts 98 triangular 3072 x 3072 factors, minutes)
-    if world == 1 and not args.no_cpu_baseline and mode == "log_prob" and on_gpu and args.config == "cfg2" and B <= 65536:
+    if full and world == 1 and not args.no_cpu_baseline and mode == "log_prob" and on_gpu and args.config == "cfg2" and B <= 65536:
         from oracle import usflows_oracle as orc      # the CPU oracle: this leg only
         # 16 threads is the fastest setting for this workload on the GPU box's 2 x EPYC 9575F (probed with
         # tools/cpu_threads_probe.py: 8 -> 1860, 16 -> 2403, 32 -> 1362, 64 -> 651, 128 (torch default) -> 203 samples/s)
@@ -732,7 +782,7 @@ def main_flat(args, under_launcher):
 
     # warm re-prep: parameters changed (optimiser step), same storage -> the pack is refreshed in place (N1)
     prep_warm_ms = None
-    if mode == "log_prob" and world == 1 and on_gpu:
+    if full and mode == "log_prob" and world == 1 and on_gpu:
         with torch.no_grad():
             for p_ in flow.parameters():
                 p_.add_(0.0)                       # bumps the version counters: every prepared matrix is stale
@@ -743,7 +793,7 @@ def main_flat(args, under_launcher):
         prep_warm_ms = (time.perf_counter() - t_w) * 1e3
     # training modes: log_prob of head / middle / tail rows after the timed steps, device vs the CPU oracle at the CURRENT parameters
     train_parity = None
-    if mode in ("train", "fit") and world == 1 and on_gpu and not args.no_cpu_baseline and D <= 1024:
+    if full and mode in ("train", "fit") and world == 1 and on_gpu and not args.no_cpu_baseline and D <= 1024:
         from oracle import usflows_oracle as orc      # the CPU oracle: parity leg only
         n3 = min(64, max(B // 3, 1))
         tidx = torch.cat([torch.arange(0, n3), torch.arange(B // 2, min(B // 2 + n3, B)), torch.arange(B - n3, B)]).unique()
@@ -758,7 +808,7 @@ def main_flat(args, under_launcher):
                         "max_abs_err_over_max_abs_log_prob": float(((got - ref_t).abs().max() / ref_t.abs().max()).item()),
                         "what": "log_prob of the trained-on rows after the timed steps, device vs oracle/usflows_oracle.py at the current parameters"}
     probe_parity = None
-    if probe is not None and lp is not None and mode == "log_prob":
+    if full and probe is not None and lp is not None and mode == "log_prob":
         got = lp[probe[0]].double().cpu()
         probe_parity = {"rows": int(got.numel()), "placed_at": "head / middle / tail of the batch",
                         "max_rel_vs_reference_fp64": float(((got - probe[1].double()).abs() / probe[1].double().abs()).max().item()),
@@ -894,7 +944,7 @@ def _image_launch_cost(name, a):
 def main_image(args, under_launcher):
     """log_prob of an image-shaped flow (the reference's MNIST / CIFAR experiment models) over this rank's resident batch;
     the same contract as the flat configurations: W warm-up steps, K timed steps between barriers, max over ranks, ONE
-    JSON line with the roofline of the dominant kernel and the CPU baseline (the image oracle, rank 0 at N = 1)."""
+    JSON line; with --full also the roofline of the dominant kernel and the CPU baseline (the image oracle, rank 0 at N = 1)."""
     import torch.distributed as dist
     cfg = IMAGE_CONFIGS[args.config]
     if args.device != "cuda":
@@ -992,7 +1042,7 @@ def main_image(args, under_launcher):
         flow.__dict__["_grad_allreduce"] = (None, True)       # (Flow._zero_grad_for_step then zeroes the bound buffer in place)
     for _ in range(max(args.warmup, 5 if mode == "train" else 1)):
         mean, lp = step()
-    if not args.no_kernel_timing and mode == "train" and not args.eager_train and world == 1 and not args.force_dist:
+    if args.full and not args.no_kernel_timing and mode == "train" and not args.eager_train and world == 1 and not args.force_dist:
         # per-kernel times of the step: three eager steps with HIP events around every launch (a replayed graph runs no
         # host code to put events around), before the timed region
         _ext.launch_timing = {n: [] for n in _IMAGE_KERNELS}
@@ -1012,7 +1062,7 @@ def main_image(args, under_launcher):
     # per-launch HIP events on every TIMING_EVERY-th step of the timed region only (as for the flat configurations): an
     # instrumented step runs its ~230 calls one by one with two event records each instead of replaying the recorded op list
     # (round 5: the live MNIST configuration measured 41 ms per step with events on every step, its kernels add up to 32 ms)
-    sampled = {n: [] for n in _IMAGE_KERNELS} if (not args.no_kernel_timing and eager_timing is None) else None
+    sampled = {n: [] for n in _IMAGE_KERNELS} if (args.full and not args.no_kernel_timing and eager_timing is None) else None
     n_sampled = 0
     if under_launcher:
         dist.barrier()
@@ -1043,6 +1093,11 @@ def main_image(args, under_launcher):
         return None
     ms_per_step = elapsed / args.steps * 1e3
     value = global_rows * args.steps / elapsed
+    if args.dump_outputs:
+        if mode == "log_prob":
+            step_outputs(args, log_prob=lp, mean_log_prob=mean)
+        else:
+            step_outputs(args, loss=-mean, parameters=torch.cat([p_.detach().reshape(-1).float() for p_ in flow.parameters()]))
 
     roofline = None
     if timing and any(timing.values()):
@@ -1097,10 +1152,10 @@ def main_image(args, under_launcher):
     # ---- CPU baseline + parity: the image oracle (torch-CPU restatement of the reference's image path) on a bounded
     # sample of the same rows; rank 0 at N = 1 only ----
     cpu = None
-    if world == 1 and not args.no_cpu_baseline and mode == "train":
+    if args.full and world == 1 and not args.no_cpu_baseline and mode == "train":
         with torch.no_grad():               # (outside the timed region) the trained-on rows' log_prob for the parity check
             lp = flow.log_prob(x)
-    if world == 1 and not args.no_cpu_baseline and lp is not None:
+    if args.full and world == 1 and not args.no_cpu_baseline and lp is not None:
         from oracle import usflows_image_oracle as iorc           # the CPU oracle: this leg only
         spec = iorc.ImageSpec(in_dims=dims, coupling_blocks=n_blocks, cond_args=dict(cfg["cond"]), householder=cfg["householder"],
                               affine_conjugation=True, base=base_kind, radial_p=1.0, radial_norm=radial_norm)

@@ -1,9 +1,8 @@
 """Import harness for the *reference* USFlows package (this container only).
 
 TEST INFRASTRUCTURE -- never imported by the product (``usflows_amd``), by ``bench.py``
-or by the ``-m gpu`` tests.  It is used only by ``make_golden.py`` (fixture generator)
-and by the optional ``test_oracle_vs_reference`` cross-check, which skips itself when
-``/root/reference`` is absent (it is absent on the GPU box).
+or by the ``-m gpu`` tests.  It is used only by the fixture generators (``make_golden*.py``; ``make_golden_live.py``
+records the reference's side of the side-by-side tests, which otherwise read the recording).
 
 The reference hard-imports ``pyro`` (flows.py:5, transforms.py:7-14, networks.py:9,
 distributions.py:5,16) which is not installed here and cannot be (no network).  The

@@ -1,4 +1,5 @@
 """Load golden fixtures (tests/golden/*.npz, produced by tests/golden/make_golden.py)."""
+import contextlib
 import glob
 import json
 import math
@@ -16,7 +17,7 @@ def case_names(small_only=False):
     # (the BASELINE cfg4 fixture -- 1.28 G parameters regenerated from the seed -- is loaded by name in
     # tests/test_configs_gpu.py only: far too big for the per-case loops)
     names = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN_DIR, "*.npz"))
-                   if not os.path.basename(p).startswith(("grads_", "fit_", "udl_", "image_", "imagegrads_", "imagefit_", "imageradial_", "imageradialfit_", "fitsophia_", "sophia_", "gmfit_", "tbase_")) and "cfg4" not in p)
+                   if not os.path.basename(p).startswith(("grads_", "fit_", "udl_", "image_", "imagegrads_", "imagefit_", "imageradial_", "imageradialfit_", "fitsophia_", "sophia_", "gmfit_", "tbase_", "live_")) and "cfg4" not in p)
     if small_only:
         names = [n for n in names if "d784" not in n]
     return names
@@ -251,3 +252,69 @@ def grads_close(named, g_ref, tol=5e-5):
         if err > tol:
             bad.append((err, k))
     assert not bad, f"{len(bad)} of {len(g_ref)} gradients beyond {tol:.0e}: {sorted(bad, reverse=True)[:5]}"
+
+
+# ---- recorded side-by-side runs of the real reference (tests/golden/live_*.npz, tests/golden/make_golden_live.py) -------
+RECORD_LIVE = os.environ.get("USFLOWS_RECORD_LIVE") == "1"
+LIVE_THREADS = 4      # torch's intra-op pool while recording and replaying (single-threaded CPU kernels round differently)
+_live_store = {}
+_live_loaded = {}
+
+
+class LiveReference:
+    """The reference's side of a side-by-side test.  Each result is computed by the live reference while recording
+    (USFLOWS_RECORD_LIVE=1, tests/golden/make_golden_live.py) and read from the committed fixture otherwise, so the test
+    needs nothing outside the repository.  Keys are "<test id>|<name>"."""
+
+    def __init__(self, fixture, test_id):
+        self.fixture, self.prefix = fixture, test_id + "|"
+        self.record = RECORD_LIVE
+
+    def _get(self, name, fn, encode, decode):
+        key = self.prefix + name
+        if self.record:
+            v = fn()
+            _live_store.setdefault(self.fixture, {})[key] = encode(v)
+            return v
+        if self.fixture not in _live_loaded:
+            with np.load(os.path.join(GOLDEN_DIR, self.fixture + ".npz"), allow_pickle=False) as z:
+                _live_loaded[self.fixture] = {k: z[k] for k in z.files}
+        return decode(_live_loaded[self.fixture][key])
+
+    def tensor(self, name, fn):
+        return self._get(name, fn, lambda v: v.detach().cpu().numpy().copy(), torch.from_numpy)
+
+    def float(self, name, fn):
+        """a scalar; None (e.g. the reference raised) is stored as NaN"""
+        return self._get(name, fn, lambda v: np.float64("nan" if v is None else float(v)),
+                         lambda a: None if math.isnan(float(a)) else float(a))
+
+    def flag(self, name, fn):
+        return self._get(name, fn, lambda v: np.bool_(bool(v)), lambda a: bool(a))
+
+    def names(self, name, fn):
+        return self._get(name, fn, lambda v: np.array(list(v), dtype=str), lambda a: [str(x) for x in a])
+
+    def shape(self, name, fn):
+        return self._get(name, fn, lambda v: np.array(tuple(v), dtype=np.int64), lambda a: tuple(int(x) for x in a))
+
+    def state_dict(self, name, fn):
+        keys = self.names(name + "/keys", lambda: list(fn().keys()))
+        sd = fn() if self.record else None
+        return {k: self.tensor(f"{name}/{k}", lambda k=k: sd[k]) for k in keys}
+
+
+@contextlib.contextmanager
+def live_threads():
+    n = torch.get_num_threads()
+    torch.set_num_threads(LIVE_THREADS)
+    try:
+        yield
+    finally:
+        torch.set_num_threads(n)
+
+
+def write_recorded_live():
+    """(recording only) write what the live reference returned to tests/golden/<fixture>.npz"""
+    for fixture, arrays in _live_store.items():
+        np.savez_compressed(os.path.join(GOLDEN_DIR, fixture + ".npz"), **arrays)

@@ -65,3 +65,22 @@ def test_eight_ranks_shard_cfg3_and_cfg5_as_the_node_will():
             os.environ.pop("OMP_NUM_THREADS", None)
         else:
             os.environ["OMP_NUM_THREADS"] = env_threads
+
+
+def test_plain_run_is_lean_and_dumps_the_same_outputs_each_time(tmp_path):
+    """a plain run carries the headline only (the extras are --full's); --dump-outputs writes the last timed step's outputs,
+    and the seeded inputs make two runs with the same arguments write the same arrays"""
+    import numpy as np
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        o = _run(["--gpus", "1", "--batch", "64", "--dump-outputs", str(d)] + SMALL)
+        assert o["steps"] == 2 and o["ms_per_step"] > 0
+        assert o["roofline"] is None and o["cpu_baseline"] is None and o["fast_mode"] is None and "also" not in o
+        runs.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    assert sorted(runs[0]) == ["log_prob.npy", "mean_log_prob.npy"]
+    assert runs[0]["log_prob.npy"].dtype == np.float32 and runs[0]["log_prob.npy"].shape == (64,)
+    assert runs[0]["mean_log_prob.npy"].dtype == np.float64
+    for f in runs[0]:
+        assert np.array_equal(runs[0][f], runs[1][f])
+    assert np.isclose(runs[0]["mean_log_prob.npy"], runs[0]["log_prob.npy"].astype(np.float64).mean(), rtol=1e-12, atol=0)

@@ -1,7 +1,7 @@
 """Pin the CPU oracle (oracle/usflows_oracle.py) against
  (a) golden vectors generated from the real reference (tests/golden/*.npz), fp32 and fp64,
  (b) the reference's own known-answer tests (tests/veriflow/transforms_test.py:5-19, 35-51),
- (c) -- only where /root/reference exists -- a live re-run of the reference."""
+ (c) a recorded run of the reference (tests/golden/live_oracle.npz) on a model of its own construction."""
 import math
 import os
 
@@ -103,25 +103,36 @@ def test_checkerboard_mask():
     assert m.shape == (1, 7) and m.flatten().tolist() == [0, 1, 0, 1, 0, 1, 0]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src/usflows"), reason="reference not present")
-def test_oracle_vs_live_reference():
-    """Build container only: rerun the real reference now and compare with the oracle."""
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
-    import ref_shim
-    flows, transforms, networks, distributions = ref_shim.install()
-    torch.manual_seed(7)
-    D = 12
-    flow = flows.USFlow(torch.distributions.Laplace(torch.zeros(D), torch.ones(D)), [D], 3,
-                        networks.ConditionalDenseNN,
-                        dict(input_dim=D, context_dim=1, hidden_dims=[20, 20], out_dim=D,
-                             nonlinearity=torch.nn.LeakyReLU(0.01)),
-                        householder=1, affine_conjugation=True)
-    spec = orc.FlowSpec(D, 3, [20, 20], householder=1, affine_conjugation=True)
-    sd = {k: v.detach() for k, v in flow.state_dict().items()}
-    x = torch.rand(9, D)
+def test_oracle_vs_live_reference(request):
+    """a run of the real reference (recorded: tests/golden/live_oracle.npz, tests/golden/make_golden_live.py) against the
+    oracle on its state dict and inputs"""
+    from golden_util import LiveReference, RECORD_LIVE, live_threads, write_recorded_live
+    R = LiveReference("live_oracle", request.node.name)
+    with live_threads():
+        _oracle_vs_live_reference(R)
+    if RECORD_LIVE:
+        write_recorded_live()
+
+
+def _oracle_vs_live_reference(R):
+    flow = None
+    if R.record:
+        import sys
+        sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
+        import ref_shim
+        flows, transforms, networks, distributions = ref_shim.install()
+        torch.manual_seed(7)
+        D = 12
+        flow = flows.USFlow(torch.distributions.Laplace(torch.zeros(D), torch.ones(D)), [D], 3,
+                            networks.ConditionalDenseNN,
+                            dict(input_dim=D, context_dim=1, hidden_dims=[20, 20], out_dim=D,
+                                 nonlinearity=torch.nn.LeakyReLU(0.01)),
+                            householder=1, affine_conjugation=True)
+    spec = orc.FlowSpec(12, 3, [20, 20], householder=1, affine_conjugation=True)
+    sd = R.state_dict("state_dict", lambda: {k: v.detach() for k, v in flow.state_dict().items()})
+    x = R.tensor("x", lambda: torch.rand(9, 12))
     with torch.no_grad():
-        ref = flow.log_prob(x)
+        ref = R.tensor("log_prob", lambda: flow.log_prob(x))
     assert _rel(orc.flow_log_prob(sd, spec, x), ref) < 2e-6
 
 

@@ -107,29 +107,42 @@ def test_constructor_checks_and_state_dict_round_trip():
     assert torch.equal(opt2.state[p]["hessian"], opt.state[p]["hessian"])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src/usflows"), reason="reference not present")
-def test_sophiag_side_by_side_with_live_reference():
-    sys.path.insert(0, os.path.join(HERE, "golden"))
-    import ref_shim
-    ref_shim.install()
-    from src.usflows.sophia import SophiaG as RefSophia
+def test_sophiag_side_by_side_with_live_reference(request):
+    """the reference's SophiaG step by step (recorded: tests/golden/live_sophia.npz, tests/golden/make_golden_live.py)"""
+    from golden_util import LiveReference, RECORD_LIVE, write_recorded_live
     from usflows_amd.sophia import SophiaG
+    R = LiveReference("live_sophia", request.node.name)
     g = torch.Generator().manual_seed(9)
     init = [torch.randn(17, 5, generator=g), torch.randn(3, generator=g)]
-    pr = [torch.nn.Parameter(t.clone()) for t in init]
     pm = [torch.nn.Parameter(t.clone()) for t in init]
-    orf, om = RefSophia(pr, lr=1e-2), SophiaG(pm, lr=1e-2)
+    om = SophiaG(pm, lr=1e-2)
+    pr = orf = None
+    if R.record:
+        sys.path.insert(0, os.path.join(HERE, "golden"))
+        import ref_shim
+        ref_shim.install()
+        from src.usflows.sophia import SophiaG as RefSophia
+        pr = [torch.nn.Parameter(t.clone()) for t in init]
+        orf = RefSophia(pr, lr=1e-2)
     for t in range(5):
-        for a, b in zip(pr, pm):
-            a.grad = torch.randn(a.shape, generator=g)
-            b.grad = a.grad.clone()
+        for i, b in enumerate(pm):
+            b.grad = torch.randn(b.shape, generator=g)
+            if pr is not None:
+                pr[i].grad = b.grad.clone()
         if t in (1, 2):
-            orf.update_hessian(); om.update_hessian()
-        orf.step(bs=2); om.step(bs=2)
-        for a, b in zip(pr, pm):
-            assert torch.equal(a, b)                                                # same ops in the same order on the CPU
-            assert torch.equal(orf.state[a]["exp_avg"], om.state[b]["exp_avg"])
-            assert torch.equal(orf.state[a]["hessian"], om.state[b]["hessian"])
+            if orf is not None:
+                orf.update_hessian()
+            om.update_hessian()
+        if orf is not None:
+            orf.step(bs=2)
+        om.step(bs=2)
+        for i, b in enumerate(pm):
+            # same ops in the same order on the CPU
+            assert torch.equal(R.tensor(f"{t}/{i}/param", lambda: pr[i].detach()), b.detach())
+            assert torch.equal(R.tensor(f"{t}/{i}/exp_avg", lambda: orf.state[pr[i]]["exp_avg"]), om.state[b]["exp_avg"])
+            assert torch.equal(R.tensor(f"{t}/{i}/hessian", lambda: orf.state[pr[i]]["hessian"]), om.state[b]["hessian"])
+    if RECORD_LIVE:
+        write_recorded_live()
 
 
 def _fit_default(device):

@@ -3,8 +3,9 @@
     python3 tools/make_profiles.py r03 [sections]   # writes gpurun_out/profiles_r03/*, copy them into profiles/
     sections (default all): bench pmc f16 peak other train trainpmc image imagetrain live -- several calls fit gpurun's 20-minute limit
 
-1. `python3 bench.py` (defaults)                                   -> <tag>_bench.json
-2. `rocprofv3 --kernel-trace --stats -- python3 bench.py`          -> <tag>_bench_kernel_stats.{csv,md}, <tag>_bench_under_rocprof.json
+Every bench.py run below is a --full run (roofline, CPU baseline, fp16x2 mode, "also" block: what the profiles record).
+1. `python3 bench.py --full` (defaults)                            -> <tag>_bench.json
+2. `rocprofv3 --kernel-trace --stats -- python3 bench.py --full`   -> <tag>_bench_kernel_stats.{csv,md}, <tag>_bench_under_rocprof.json
 3. `rocprofv3 --pmc FETCH_SIZE` and, separately, `--pmc WRITE_SIZE` on a short bench run
                                                                    -> <tag>_hbm_traffic.json
 3b. `rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES ... GRBM_GUI_ACTIVE` (own pass)        -> <tag>_mfma_util.json
@@ -40,6 +41,9 @@ def last_json_line(text):
 
 
 def run(cmd, **kw):
+    if "bench.py" in cmd:
+        i = cmd.index("bench.py") + 1
+        cmd = cmd[:i] + ["--full"] + cmd[i:]
     print("+", " ".join(cmd), flush=True)
     return subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, **kw)
 
@@ -247,7 +251,7 @@ if want("train"):
         r = run(["python3", "bench.py", "--steps", "10", "--warmup", "3"] + extra)
         lines.append(last_json_line(r.stdout))
         for composite_env in ([("USFLOWS_AMD_TRAIN", "composite")] if extra[-1] == "4096" else []):
-            r = subprocess.run(["python3", "bench.py", "--steps", "5", "--warmup", "2"] + extra, cwd=ROOT,
+            r = subprocess.run(["python3", "bench.py", "--full", "--steps", "5", "--warmup", "2"] + extra, cwd=ROOT,
                                env=dict(env, **dict([composite_env])), capture_output=True, text=True)
             j = json.loads(last_json_line(r.stdout))
             j["config"]["training_path"] = "composite torch ops (USFLOWS_AMD_TRAIN=composite)"
@@ -371,8 +375,8 @@ if want("imagetrain"):
         # the same flow through torch autograd + MIOpen (what round 2 replayed): USFLOWS_AMD_TUNE=image_train=0
         env_t = dict(env, USFLOWS_AMD_TUNE="image_train=0")
         for cfg, batch in (("mnist_image", "65536"), ("mnist_image", "32")):
-            print("+ USFLOWS_AMD_TUNE=image_train=0 python3 bench.py --config", cfg, "--mode train --batch", batch, flush=True)
-            r = subprocess.run(["python3", "bench.py", "--config", cfg, "--mode", "train", "--batch", batch, "--steps", "10"], cwd=ROOT,
+            print("+ USFLOWS_AMD_TUNE=image_train=0 python3 bench.py --full --config", cfg, "--mode train --batch", batch, flush=True)
+            r = subprocess.run(["python3", "bench.py", "--full", "--config", cfg, "--mode", "train", "--batch", batch, "--steps", "10"], cwd=ROOT,
                                env=env_t, capture_output=True, text=True)
             line = json.loads(last_json_line(r.stdout))
             line["config"]["workload"] += " [USFLOWS_AMD_TUNE=image_train=0: torch autograd + MIOpen backward]"
