@@ -112,3 +112,42 @@ def test_tiny_coupling_rule_of_the_engine_is_the_librarys():
         n_checked += 1
         n_tiny += int(py)
     assert n_checked > 800 and 20 < n_tiny < n_checked
+
+
+def _coupling_variant(B, n_pass, hidden, n_trans):
+    """usf_coupling_variant of a forward coupling descriptor with the engine's weight strides (pointers never read)"""
+    from usflows_amd import _ext
+    d = _ext.CouplingDesc()
+    d.z = d.out = 0x10000
+    d.ldz = d.ldo = 512
+    d.M, d.off_pass, d.n_pass, d.off_trans, d.n_trans = B, 0, n_pass, 256, n_trans
+    d.n_hidden = len(hidden)
+    r32 = lambda v: (v + 31) // 32 * 32
+    for i, h in enumerate(hidden):
+        d.hidden[i] = h
+    d.W_in, d.ldw_in, d.b_in = 0x20000, r32(n_pass), 0x30000
+    for i in range(1, len(hidden)):
+        d.W_hid[i - 1], d.ldw_hid[i - 1], d.b_hid[i - 1] = 0x40000 + 0x10000 * i, 64, 0x30000
+    d.W_out, d.ldw_out, d.b_out = 0x80000, 64, 0x30000
+    d.sign, d.slope, d.act = 1.0, 0.01, _ext.ACT_LEAKY_RELU
+    return _ext.load().usf_coupling_variant(d)
+
+def test_tiny_coupling_decision_of_the_engine_follows_the_library_knob():
+    """usf_set_tuning("coupling_tiny", 0) switches the tiny-layer kernel off in the library: the engine must not emit the fused
+    coupling op (with hidden_out / GATE, which only that kernel serves) for such layers any more, and the knob's value is part of
+    the plan-cache key (tests/test_training_emulated.py builds the plans)"""
+    from usflows_amd.config import config
+    from usflows_amd.engine import FlowEngine
+    shapes = [(32, 1, [32, 32], 1), (32, 5, [32, 32], 5), (256, 50, [32, 32], 50), (1, 17, [32], 17)]
+    old = config.get_lib("coupling_tiny", 1)
+    try:
+        config.set_lib("coupling_tiny", 1)
+        for B, n_pass, hidden, n_trans in shapes:
+            assert FlowEngine.tiny_coupling(None, dict(hidden=hidden, pass_n=n_pass, tr_n=n_trans), B)
+            assert _coupling_variant(B, n_pass, hidden, n_trans) == 3
+        config.set_lib("coupling_tiny", 0)
+        for B, n_pass, hidden, n_trans in shapes:
+            assert _coupling_variant(B, n_pass, hidden, n_trans) != 3
+            assert not FlowEngine.tiny_coupling(None, dict(hidden=hidden, pass_n=n_pass, tr_n=n_trans), B)
+    finally:
+        config.set_lib("coupling_tiny", old)

@@ -89,6 +89,25 @@ def test_mirror_fit_reproduces_the_reference_run_cpu(name):
 def test_device_gradients_of_the_fit_loss_match_the_reference(name):
     """Flow.fit's loss on the device: log_prob to 1e-5 of the reference's fp64 run, EVERY gradient -- no parameter skipped --
     to 5e-5 of its tensor's largest entry; the flow's own training path ran (no composite fallback)"""
+    _device_gradients_of_the_fit_loss(name)
+
+
+@pytest.mark.gpu
+def test_device_gradients_of_the_fit_loss_with_the_tiny_layer_kernel_off():
+    """usf_set_tuning("coupling_tiny", 0): the engine follows the library and runs the coupling layers unfused -- same
+    golden tolerances"""
+    from usflows_amd.config import config
+    old = config.get_lib("coupling_tiny", 1)
+    config.set_lib("coupling_tiny", 0)
+    try:
+        flow = _device_gradients_of_the_fit_loss("init_d10_k10_gmlive")
+        metas = [m for p in flow.engine()._plans.values() for m in p.get("meta", []) if m["kind"] == "coupling"]
+        assert metas and not any(m.get("tiny") for m in metas)
+    finally:
+        config.set_lib("coupling_tiny", old)
+
+
+def _device_gradients_of_the_fit_loss(name):
     spec, sd, a = load_case(name)
     loss_ref, _prior_ref, g_ref = load_gm_live_grads(name)
     flow = build_flow(spec, sd, device=DEV)
@@ -97,6 +116,9 @@ def test_device_gradients_of_the_fit_loss_match_the_reference(name):
     lp = flow.log_prob(x)
     assert lp.requires_grad and flow.engine().launch_count > before, "the device training path did not run"
     _close(lp, a["log_prob64"], 1e-5, "log_prob")
+    # row-wise as well (the reference's own fp32 run is within 3.2e-6 of its fp64 one on every row of the three fixtures)
+    rel = ((lp.detach().cpu().double() - a["log_prob64"].double()).abs() / a["log_prob64"].double().abs()).max().item()
+    assert rel < 1e-5, ("log_prob row-wise", rel)
     loss = -lp.mean() - flow.log_prior()
     assert abs(float(loss) - loss_ref) <= 1e-5 * abs(loss_ref)
     loss.backward()
@@ -108,6 +130,7 @@ def test_device_gradients_of_the_fit_loss_match_the_reference(name):
         # meet -- is held to the noise floor of the pass: 1e-5 of the largest gradient entry of the flow)
         d = (named[k].grad.detach().cpu().double().reshape(g.shape) - g.double()).abs().max().item()
         assert d <= 5e-5 * g.abs().max().item() + 1e-5 * gmax, (k, d, g.abs().max().item())
+    return flow
 
 
 @pytest.mark.gpu

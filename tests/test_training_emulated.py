@@ -305,3 +305,145 @@ def test_input_gradient_from_the_training_path(name):
     x2 = a["x"].clone().requires_grad_(True)
     (training.log_prob_with_grad(path, x2, None) * g_lp).sum().backward()
     assert torch.allclose(x2.grad, x.grad, rtol=1e-6, atol=1e-7 * s_)
+
+
+# ---- padded feature dims: the segment layout (LD) and the natural one (LDn) differ ----------------------------------------------
+from padded_cases import PADDED_GOLDEN, Reference, sweep_ids, sweep_input, sweep_spec  # noqa: E402
+
+
+def _ld_pair(spec, sd):
+    eng = build_flow(spec, sd).engine()
+    return eng.LD, eng.LDn
+
+
+def test_padded_cases_cover_ld_above_ldn():
+    """the padded-D tests below are only worth their name while some of their flows have LD > LDn (and some LD == LDn)"""
+    pairs = [_ld_pair(*load_case(n)[:2]) for n in PADDED_GOLDEN]
+    pairs += [_ld_pair(*sweep_spec(D, c, conj, hh, b)) for D, c, conj, hh, b in sweep_ids() if c == "DenseNN" and not conj
+              and b == "laplace"]
+    assert sum(ld > ldn for ld, ldn in pairs) >= 6, pairs
+    assert any(ld == ldn for ld, ldn in pairs), pairs
+
+
+@pytest.mark.parametrize("name", PADDED_GOLDEN)
+def test_input_gradient_from_the_training_path_at_padded_dims(name):
+    """d log_prob / dx at dims where the first layer's data gradient is written with row stride LDn inside a buffer of width
+    max(LD, LDn): against fp64 autograd through the oracle, within 3x the fp32 oracle's own error (and never tighter than the
+    2e-5 of test_input_gradient_from_the_training_path); once eagerly, once more on the same plan"""
+    from usflows_amd import training
+    spec, sd, a = load_case(name)
+    flow = build_flow(spec, sd)
+    x0 = a["x"]
+    g_lp = torch.randn(x0.shape[0], generator=torch.Generator().manual_seed(2))
+    ref = Reference(spec, sd, x0, g_lp)
+    path = TrainPath(flow)
+    x = x0.clone().requires_grad_(True)
+    assert path.supported(x, None)
+    lp = training.log_prob_with_grad(path, x, None)
+    (lp * g_lp).sum().backward()
+    ref.check_log_prob(lp)
+    ref.check_input_grad(x.grad, name)
+    assert ref.check_param_grads(flow, name) >= 5
+    x2 = x0.clone().requires_grad_(True)
+    (training.log_prob_with_grad(path, x2, None) * g_lp).sum().backward()
+    assert torch.allclose(x2.grad, x.grad, rtol=1e-6, atol=1e-7 * ref.gx_scale)
+
+
+@pytest.mark.parametrize("D,cond,conj,hh,base", sweep_ids())
+def test_training_path_at_padded_dims_matches_oracle_autograd(D, cond, conj, hh, base):
+    """synthetic sweep over D mod 4, segment parity, both conditioner layouts, plain / conjugated blocks with and without a
+    Householder factor, a Laplace and a radial base: log_prob row-wise, d/dx and every parameter gradient"""
+    from usflows_amd import training
+    spec, sd = sweep_spec(D, cond, conj, hh, base)
+    flow = build_flow(spec, sd)
+    x0, g_lp = sweep_input(spec, sd, 37)
+    ref = Reference(spec, sd, x0, g_lp)
+    x = x0.clone().requires_grad_(True)
+    path = TrainPath(flow)
+    assert path.supported(x, None)
+    lp = training.log_prob_with_grad(path, x, None)
+    (lp * g_lp).sum().backward()
+    ref.check_log_prob(lp)
+    ref.check_input_grad(x.grad)
+    assert ref.check_param_grads(flow) >= 5
+
+
+def _overlaps(t, others):
+    lo, hi = t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
+    for o in others:
+        s = o.untyped_storage()
+        if s.data_ptr() < hi and lo < s.data_ptr() + s.nbytes():
+            return True
+    return False
+
+
+def test_input_gradient_is_not_a_view_of_the_workspace():
+    """x.grad / torch.autograd.grad must own their storage: the next pass over the same (B, device) plan rewrites the workspace.
+    The shape is one where the natural slice of the gradient buffer is already contiguous (D = 32: LD == LDn == D, conditioner
+    widths <= D) and no ScaleTransform is folded in front of the first block (the division would copy): the layer list of a
+    USFlow without its final ScaleTransform"""
+    from usflows_amd import training
+    from usflows_amd.flows import Flow
+    spec, sd = sweep_spec(32, "DenseNN", False, 0, "laplace")
+    host = build_flow(spec, sd)
+    layers = list(host.layers)
+    assert type(layers[-1]).__name__ == "ScaleTransform"
+    flow = Flow(host.base_distribution, layers[:-1])
+    eng = flow.engine()
+    assert eng.LD == eng.LDn == 32
+    path = TrainPath(flow)
+    B = 24
+    x1, g_lp = sweep_input(spec, sd, B, seed=1)
+    x2, _ = sweep_input(spec, sd, B, seed=2)
+
+    def grad_of(x0):
+        x = x0.clone().requires_grad_(True)
+        return torch.autograd.grad((training.log_prob_with_grad(path, x, None) * g_lp).sum(), x)[0]
+
+    g1 = grad_of(x1)
+    assert eng._plans and path._dx is not None
+    ws = [t for p in eng._plans.values() for t in p["ws"].values() if torch.is_tensor(t)]
+    assert not _overlaps(g1, ws), "the input gradient is a view of the plan's workspace"
+    keep = g1.clone()
+    g2 = grad_of(x2)
+    assert not torch.equal(g2, keep)                    # (the second pass did write another gradient)
+    assert torch.equal(g1, keep), "a later pass on the same plan changed an input gradient already handed out"
+    x = x1.clone().requires_grad_(True)
+    for _ in range(2):
+        (training.log_prob_with_grad(path, x, None) * g_lp).sum().backward()
+    assert torch.allclose(x.grad, 2 * keep, rtol=1e-6, atol=1e-7 * keep.abs().max().item())
+
+
+def test_training_plan_follows_the_librarys_tiny_coupling_knob():
+    """usf_set_tuning("coupling_tiny", 0): a plan built afterwards (the knob is part of the plan-cache key) runs the coupling
+    layers as unfused linear launches instead of the fused op the library would now hand to the f32 kernel, and the gradients
+    still match the oracle"""
+    from usflows_amd import training
+    from usflows_amd.config import config
+    spec, sd = sweep_spec(13, "DenseNN", True, 1, "laplace")
+    x0, g_lp = sweep_input(spec, sd, 37)
+    ref = Reference(spec, sd, x0, g_lp)
+    old = config.get_lib("coupling_tiny", 1)
+    try:
+        for knob in (1, 0):
+            config.set_lib("coupling_tiny", knob)
+            flow = build_flow(spec, sd)
+            eng = flow.engine()
+            x = x0.clone().requires_grad_(True)
+            lp = training.log_prob_with_grad(TrainPath(flow), x, None)
+            (lp * g_lp).sum().backward()
+            plans = [p for p in eng._plans.values() if p["meta"]]
+            tiny = [m.get("tiny", False) for p in plans for m in p["meta"] if m["kind"] == "coupling"]
+            assert tiny and all(tiny) == bool(knob) and any(tiny) == bool(knob), (knob, tiny)
+            ref.check_log_prob(lp)
+            ref.check_input_grad(x.grad)
+            assert ref.check_param_grads(flow) >= 5
+            with torch.no_grad():
+                eng.latent(x0, None)
+            n_plans = len(eng._plans)
+            config.set_lib("coupling_tiny", 1 - knob)
+            with torch.no_grad():
+                eng.latent(x0, None)
+            assert len(eng._plans) == n_plans + 1, "the library's knob is not part of the plan-cache key"
+    finally:
+        config.set_lib("coupling_tiny", old)

@@ -1048,21 +1048,23 @@ class FlowEngine(PlanesPlanMixin):
             meta.append(dict(kind="coupling", op=len(ops), step=i, buf=cur[0], sign=sign, use_ctx=use_ctx))
             # the fused kernel keeps a wave on 16 rows for the whole MLP: unbeatable when the chip is full, but
             # its latency is one wave's serial MFMA chain; small batches run the MLP as 3 short linear launches
+            op = None
+            if not cp.get("general") and self.use_fused_coupling and self._fused_ok(cp) and \
+                    (B >= self.fused_min_rows or self.tiny_coupling(cp, B)):
+                op = self._coupling_op(cp, zptr, B, sign, ws if use_ctx else None)
+                if B < self.fused_min_rows and not self._tiny_served(pk, cp, op, ws, i, B, train, device):
+                    op = None
             if cp.get("general"):
                 self._general_coupling_ops(ops, lin_op, pk, cp, ws, zptr, B, sign, device)
-            elif self.use_fused_coupling and self._fused_ok(cp) and (B >= self.fused_min_rows or self.tiny_coupling(cp, B)):
+            elif op is not None:
                 tiny = B < self.fused_min_rows
-                op = self._coupling_op(cp, zptr, B, sign, ws if use_ctx else None)
                 # training: the fused kernel also stores the hidden activations (buffers of the layer's own; 2 x B x 256 x 4
                 # bytes per coupling) -- the backward pass reads them instead of running the conditioner a second time
                 # (tiny layers at launch-bound batches: usf_coupling_tiny.hip does the same, and the backward chain in one launch)
                 meta[-1]["tiny"] = tiny
                 if train and (tiny or (self.save_fused_hidden(cp, B) and op.u.coupling.split_in)):
-                    for j in range(len(cp["hidden"])):
-                        hname = f"Hs{j}_{i}"
-                        if hname not in ws or ws[hname].shape[0] != B or ws[hname].shape[1] < self.hmax:
-                            ws[hname] = torch.zeros(B, self.hmax, dtype=torch.float32, device=device)
-                        op.u.coupling.hidden_out[j] = ws[hname].data_ptr()
+                    for j, hb in enumerate(self._hidden_bufs(ws, i, len(cp["hidden"]), B, device)):
+                        op.u.coupling.hidden_out[j] = hb.data_ptr()
                     op.u.coupling.ld_hidden_out = self.hmax
                     meta[-1]["hidden_saved_fused"] = True
                 ops.append(op)
@@ -1124,7 +1126,7 @@ class FlowEngine(PlanesPlanMixin):
         (usf_coupling_tiny.hip's eligibility rule, restated for the forward AND the backward descriptor: <= 256 rows, segments
         and hidden widths <= 64, the layer's weight images + rows + side inputs in 64 KB of LDS)"""
         from .config import config
-        if not config.tiny_coupling or not (0 < B <= 256) or cp.get("general"):
+        if not config.tiny_coupling or not config.get_lib("coupling_tiny", 1) or not (0 < B <= 256) or cp.get("general"):
             return False
         hid = [int(h_) for h_ in cp["hidden"]]
         if len(hid) > 3 or max(hid) > 64 or cp["pass_n"] > 64 or cp["tr_n"] > 64:
@@ -1140,6 +1142,28 @@ class FlowEngine(PlanesPlanMixin):
             return f + 32 * (r4(n_pass) + 4) + 2 * 32 * 68 + rows_sum + 32 * n_trans + 32 * sum(hidden) + 32 + 128
 
         return max(lds_floats(cp["pass_n"], hid, cp["tr_n"]), lds_floats(cp["tr_n"], hid[::-1], cp["pass_n"])) * 4 <= 64 * 1024
+
+    def _hidden_bufs(self, ws, i, n, B, device):
+        """the per-layer buffers a training plan's coupling step i keeps its hidden activations in (training.py reads them)"""
+        for j in range(n):
+            hname = f"Hs{j}_{i}"
+            if hname not in ws or ws[hname].shape[0] != B or ws[hname].shape[1] < self.hmax:
+                ws[hname] = torch.zeros(B, self.hmax, dtype=torch.float32, device=device)
+        return [ws[f"Hs{j}_{i}"] for j in range(n)]
+
+    def _tiny_served(self, pk, cp, op, ws, i, B, train, device) -> bool:
+        """the library's own answer for a layer tiny_coupling() admits: the tiny-layer kernel serves the forward descriptor and,
+        for a training plan whose backward chain runs fused (training.py: _fused_cbwd), the backward one (usf_coupling_variant,
+        host-only).  Otherwise the layer takes the unfused ops: the f32 kernel rejects hidden_out / GATE"""
+        lib = _ext.load()
+        if lib.usf_coupling_variant(C.byref(op.u.coupling)) != 3:
+            return False
+        if train and config.fused_cbwd:
+            hb = self._hidden_bufs(ws, i, len(cp["hidden"]), B, device)
+            bop = self.coupling_backward_op(pk, cp, op.u.coupling.z, self.LD, B, 1.0, hb, hb)
+            if lib.usf_coupling_variant(C.byref(bop.u.coupling)) != 3:
+                return False
+        return True
 
     def save_fused_hidden(self, cp, B: int) -> bool:
         """training: the fused bf16x3 coupling kernel stores its hidden activations (usf_coupling_desc::hidden_out) -- where
@@ -1380,7 +1404,7 @@ class FlowEngine(PlanesPlanMixin):
     def _plan(self, direction, B, device, has_ctx, final, train: bool = False):
         pk = self.pack(device)   # may invalidate plans
         key = (direction, B, str(device), has_ctx, final, self.use_fused_coupling, self.gemm_mode, self.fused_min_rows,
-               config.tiny_coupling, train, self.use_planes, self.planes_min_rows, self._planes_fmt(), self.planes_min_rows_bf16x3,
+               config.tiny_coupling, config.get_lib("coupling_tiny", 1), train, self.use_planes, self.planes_min_rows, self._planes_fmt(), self.planes_min_rows_bf16x3,
                (not train) and self._merge_on(direction), train and self.use_train_planes, train and self.train_planes_min_rows)
         plan = self._plans.get(key)
         if plan is None:

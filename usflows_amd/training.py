@@ -285,11 +285,14 @@ class TrainPath:
         """d sum_m g_lp[m] log_prob[m] / dx [B, D] from the gradient the last backward pass left at the first layer's input"""
         g, ld = self._dx
         D = self.eng.D
-        dx = g[:, :D]
+        B = plan["ws"]["zA"].shape[0]
+        # the data-gradient GEMM wrote rows of stride ld, which need not be the buffer's width (LD != LDn at D = 2, 10, 100, ...)
+        dx = g.reshape(-1)[:B * ld].view(B, ld)[:, :D]
         sm = plan["meta"][0]["pre_scale"]
         if sm is not None:                                             # x' = x / scale in front of the block (ScaleTransform.backward)
-            dx = dx / sm.scale.detach().to(dx.device, torch.float32).reshape(1, D)
-        return dx.contiguous() if sm is None else dx
+            return dx / sm.scale.detach().to(dx.device, torch.float32).reshape(1, D)
+        # autograd may keep what we return (x.grad): never hand out the workspace, which the next pass overwrites
+        return dx.clone()
 
     def backward(self, plan, x, g_lp: torch.Tensor, gsum: Optional[torch.Tensor] = None,
                  into_bound: bool = False, want_dx: bool = False) -> Dict[int, torch.Tensor]:
