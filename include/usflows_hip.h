@@ -25,7 +25,7 @@ extern "C" {
 
 typedef void* usf_stream_t; /* hipStream_t */
 
-#define USF_ABI_VERSION 35
+#define USF_ABI_VERSION 36
 
 /* activation ids (conditioner nonlinearity, networks.py:717,737) */
 #define USF_ACT_NONE 0
@@ -368,6 +368,28 @@ int usf_conv2d_same_fits(int64_t cin, int64_t cout, int64_t H, int64_t W, int64_
 int usf_conv2d_same_f32(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
                         const void* w_planes, const float* bias, const float* in_mul, int32_t in_act, float in_slope,
                         int32_t out_act, float out_slope, const float* gate_x, int64_t gate_channels, usf_stream_t stream);
+/* usf_conv2d_same_ctx_f32 (ABI 36): the FIRST convolution of a conditional conditioner -- CondConvNet2D / the spatial
+ * CondConvNet (reference networks.py:513-680), which append the per-row context as one more input channel, broadcast over
+ * the image, in front of Conv2d(cin + 1, cout) -- without the [B, cin + 1, H, W] tensor.  Under stride 1 and zero "same"
+ * padding that channel is the constant plane ctx[b], so its share of the output is rank-1:
+ *   y[b, co, p] = out_act( <usf_conv2d_same_f32's sum over the cin data channels> + bias[co] + ctx[b * ctx_stride] * S[co, p] ),
+ *   S[co, p] = sum over the taps t = dy * ks + dx of p that land inside the image of w_ctx[co, t]
+ * with w_ctx [cout, ks * ks] = W[:, cin, :, :] (the context channel's weights) and w_planes the planes of W[:, :cin] (in_mul
+ * masks the data channels only: the reference concatenates after MaskedCoupling's mask).  ctx_stride 0 broadcasts ctx[0],
+ * 1 reads one value per row.  The term is computed in the epilogue of every kernel variant that serves the shape; no table,
+ * no extra launch.  ctx == NULL: exactly usf_conv2d_same_f32 (same kernels, same bits).  No gated mode. */
+int usf_conv2d_same_ctx_f32(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
+                            const void* w_planes, const float* bias, const float* in_mul, int32_t in_act, float in_slope,
+                            int32_t out_act, float out_slope, const float* ctx, int64_t ctx_stride, const float* w_ctx,
+                            usf_stream_t stream);
+/* usf_conv_ctx_wgrad_f32 (ABI 36): the weight gradient of that context channel (reference networks.py:513-680 under autograd),
+ *   dw_ctx[co, t] = sum_b ctx[b * ctx_stride] * sum over the p whose tap t lands inside the image of dy[b, co, p]
+ * dy [B, cout, H, W] contiguous fp32, dw_ctx [cout, ks * ks].  One block per output channel reads its dy plane once; the sums
+ * run in a fixed order (same bits on every run) and need no workspace and no second launch.  The data channels' weight and
+ * bias gradients are usf_conv_wgrad_f32's, the data gradient the usual transposed convolution over the cin data channels;
+ * there is no gradient with respect to the context. */
+int usf_conv_ctx_wgrad_f32(const float* dy, const float* ctx, int64_t ctx_stride, int64_t B, int64_t cout, int64_t H, int64_t W,
+                           int64_t ks, float* dw_ctx, usf_stream_t stream);
 /* The LAST convolution of a coupling layer's conditioner with MaskedCoupling's masked residual (transforms.py:277-306) in
  * its output stream:  y = res_x + res_sign * (res_mul * conv(in_act(x) * in_mul)),  res_x [B, cout, H, W] (the coupling's
  * input), res_mul [cout * H * W] = 1 - mask -- the arithmetic of usf_conv2d_same_f32 followed by usf_masked_residual_f32,
@@ -693,6 +715,7 @@ int usf_gated_norm_rows_bwd_f32(const usf_gated_norm_bwd_desc* d, usf_stream_t s
 #define USF_FN_BASE_LOGPROB 9
 #define USF_FN_RADIAL_LOGPROB 10
 #define USF_FN_GATED_TAIL 11
+#define USF_FN_CONV2D_SAME_CTX 12   /* usf_conv2d_same_ctx_f32 (ABI 36) */
 #define USF_CALL_MAX_ARGS 20
 typedef struct usf_call_desc {
   int32_t fn;

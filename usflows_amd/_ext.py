@@ -20,7 +20,7 @@ from .config import config  # noqa: E402
 
 LIB_PATH = config.lib_path     # (USFLOWS_AMD_LIB: A/B builds)
 
-USF_ABI_VERSION = 35
+USF_ABI_VERSION = 36
 USF_MAX_HIDDEN = 4
 
 ACT_NONE, ACT_LEAKY_RELU, ACT_GATE = 0, 1, 2
@@ -230,6 +230,9 @@ SYMBOLS = {
     "usf_conv2d_same_fits": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "usf_conv2d_same_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, _fp, _fp,
                                       C.c_int32, C.c_float, C.c_int32, C.c_float, _fp, C.c_int64, C.c_void_p]),
+    "usf_conv2d_same_ctx_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, _fp, _fp,
+                                          C.c_int32, C.c_float, C.c_int32, C.c_float, _fp, C.c_int64, _fp, C.c_void_p]),
+    "usf_conv_ctx_wgrad_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_void_p]),
     "usf_conv2d_same_res_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, _fp, _fp,
                                           C.c_int32, C.c_float, _fp, _fp, C.c_float, C.c_void_p]),
     "usf_masked_residual_f32": (C.c_int, [_fp, _fp, _fp, C.c_float, _fp, C.c_int64, C.c_int64, C.c_void_p]),
@@ -413,7 +416,7 @@ def _timed_call(fn, args, name):
 # ---- a layer loop's calls as ONE op list (USF_OP_CALL; flows.py: image-shaped flows) ------------------------------------
 CALL_FNS = {"usf_scale_f32": 1, "usf_channel_affine_f32": 2, "usf_layernorm_channels_f32": 3, "usf_gated_residual_f32": 4,
             "usf_masked_residual_f32": 5, "usf_pointwise_conv_f32": 6, "usf_conv2d_same_f32": 7, "usf_conv2d_same_res_f32": 8,
-            "usf_base_logprob_f32": 9, "usf_radial_logprob_f32": 10, "usf_gated_tail_f32": 11}
+            "usf_base_logprob_f32": 9, "usf_radial_logprob_f32": 10, "usf_gated_tail_f32": 11, "usf_conv2d_same_ctx_f32": 12}
 
 
 class CallList:
@@ -811,6 +814,35 @@ def conv2d_same(x, planes, cout, ks, bias=None, in_mul=None, in_act=ACT_NONE, in
                                      ptr(in_mul), int(in_act), float(in_slope), int(out_act), float(out_slope),
                                      ptr(gate_x), gc, current_stream(x.device))
     return y
+
+
+def conv2d_same_ctx(x, planes, cout, ks, ctx, w_ctx, bias=None, in_mul=None, in_act=ACT_NONE, in_slope=0.0, out_act=ACT_NONE,
+                    out_slope=0.0):
+    """usf_conv2d_same_ctx_f32: Conv2d(cin + 1, cout) over cat(in_act(x) * in_mul, ctx-plane) without the concatenated tensor.
+    x: contiguous [B, cin, H, W] fp32; planes: of W[:, :cin]; w_ctx: contiguous [cout, ks * ks] fp32 = W[:, cin]; ctx: a
+    contiguous fp32 device tensor of B values (one per row) or of 1 value (broadcast) -> new [B, cout, H, W] tensor"""
+    B, cin, H, W = x.shape
+    n = ctx.numel()
+    assert ctx.is_cuda and ctx.dtype == torch.float32 and ctx.is_contiguous() and n in (1, B), (ctx.shape, B)
+    assert w_ctx.dtype == torch.float32 and w_ctx.is_contiguous() and w_ctx.numel() == cout * ks * ks
+    y = torch.empty(B, cout, H, W, dtype=torch.float32, device=x.device)
+    _direct("usf_conv2d_same_ctx_f32", x.data_ptr(), y.data_ptr(), B, cin, cout, H, W, ks, planes.data_ptr(), ptr(bias),
+            ptr(in_mul), int(in_act), float(in_slope), int(out_act), float(out_slope), ctx.data_ptr(), 1 if (n == B and B > 1) else 0,
+            w_ctx.data_ptr(), current_stream(x.device))
+    return y
+
+
+def conv_ctx_wgrad(dy, ctx, ks):
+    """usf_conv_ctx_wgrad_f32: the context channel's weight gradient [cout, ks * ks] from dy [B, cout, H, W] and the context
+    (a contiguous fp32 device tensor of B values or of 1 value, as for conv2d_same_ctx)"""
+    B, cout, H, W = dy.shape
+    n = ctx.numel()
+    assert ctx.is_cuda and ctx.dtype == torch.float32 and ctx.is_contiguous() and n in (1, B), (ctx.shape, B)
+    dy = dy.contiguous()
+    dwc = torch.empty(cout, ks * ks, dtype=torch.float32, device=dy.device)
+    _direct("usf_conv_ctx_wgrad_f32", dy.data_ptr(), ctx.data_ptr(), 1 if (n == B and B > 1) else 0, B, cout, H, W, ks,
+            dwc.data_ptr(), current_stream(dy.device))
+    return dwc
 
 
 def conv2d_same_res(x, planes, cout, ks, res_x, res_mul, res_sign, bias=None, in_mul=None, in_act=ACT_NONE, in_slope=0.0):

@@ -110,7 +110,10 @@ int conv2d_same_res(const float* x, float* y, int64_t B, int64_t cin, int64_t co
                     const float* res_x, const float* res_mul, float res_sign, hipStream_t stream);
 int conv2d_same(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
                 const void* wplanes, const float* bias, const float* in_mul, int32_t in_act, float in_slope,
-                int32_t out_act, float out_slope, const float* gate_x, int64_t gate_channels, hipStream_t stream);
+                int32_t out_act, float out_slope, const float* gate_x, int64_t gate_channels, hipStream_t stream,
+                const float* ctx = nullptr, int64_t ctx_stride = 0, const float* w_ctx = nullptr);
+int conv_ctx_wgrad(const float* dy, const float* ctx, int64_t ctx_stride, int64_t B, int64_t cout, int64_t H, int64_t W, int64_t ks,
+                   float* dw_ctx, hipStream_t stream);
 int conv2d_same_gate(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
                      const void* wplanes, const float* gate_h, float gate_slope, const float* gate_mul, const float* gate_add,
                      hipStream_t stream);
@@ -437,6 +440,17 @@ int usf_conv2d_same_f32(const float* x, float* y, int64_t B, int64_t cin, int64_
   return usf::conv2d_same(x, y, B, cin, cout, H, W, ks, w_planes, bias, in_mul, in_act, in_slope, out_act, out_slope,
                           gate_x, gate_channels, (hipStream_t)stream);
 }
+int usf_conv_ctx_wgrad_f32(const float* dy, const float* ctx, int64_t ctx_stride, int64_t B, int64_t cout, int64_t H, int64_t W,
+                           int64_t ks, float* dw_ctx, usf_stream_t stream) {
+  return usf::conv_ctx_wgrad(dy, ctx, ctx_stride, B, cout, H, W, ks, dw_ctx, (hipStream_t)stream);
+}
+int usf_conv2d_same_ctx_f32(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
+                            const void* w_planes, const float* bias, const float* in_mul, int32_t in_act, float in_slope,
+                            int32_t out_act, float out_slope, const float* ctx, int64_t ctx_stride, const float* w_ctx,
+                            usf_stream_t stream) {
+  return usf::conv2d_same(x, y, B, cin, cout, H, W, ks, w_planes, bias, in_mul, in_act, in_slope, out_act, out_slope,
+                          nullptr, 0, (hipStream_t)stream, ctx, ctx_stride, w_ctx);
+}
 int usf_conv2d_same_res_f32(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
                             const void* w_planes, const float* bias, const float* in_mul, int32_t in_act, float in_slope,
                             const float* res_x, const float* res_mul, float res_sign, usf_stream_t stream) {
@@ -552,8 +566,8 @@ static int run_call(const usf_call_desc* c, usf_stream_t stream) {
 #define J(i) ((int32_t)a[i])
   auto F = [&](int i) { float f; uint32_t u = (uint32_t)a[i]; memcpy(&f, &u, 4); return f; };
   auto Dbl = [&](int i) { double d; uint64_t u = a[i]; memcpy(&d, &u, 8); return d; };
-  static const int nargs[] = {0, 8, 8, 10, 5, 7, 16, 17, 16, 11, 17, 15};
-  if (c->fn < 1 || c->fn > USF_FN_GATED_TAIL || c->n_args != nargs[c->fn]) {
+  static const int nargs[] = {0, 8, 8, 10, 5, 7, 16, 17, 16, 11, 17, 15, 18};
+  if (c->fn < 1 || c->fn > USF_FN_CONV2D_SAME_CTX || c->n_args != nargs[c->fn]) {
     usf::set_error("usf_run_ops: call op with unknown function %d or %d arguments", c->fn, c->n_args);
     return -2;
   }
@@ -570,6 +584,9 @@ static int run_call(const usf_call_desc* c, usf_stream_t stream) {
     case USF_FN_CONV2D_SAME:
       return usf_conv2d_same_f32(P(0), Q(1), I(2), I(3), I(4), I(5), I(6), I(7), (const void*)(uintptr_t)a[8], P(9), P(10), J(11), F(12),
                                  J(13), F(14), P(15), I(16), stream);
+    case USF_FN_CONV2D_SAME_CTX:
+      return usf_conv2d_same_ctx_f32(P(0), Q(1), I(2), I(3), I(4), I(5), I(6), I(7), (const void*)(uintptr_t)a[8], P(9), P(10), J(11),
+                                     F(12), J(13), F(14), P(15), I(16), P(17), stream);
     case USF_FN_CONV2D_SAME_RES: {
       const int rc = usf_conv2d_same_res_f32(P(0), Q(1), I(2), I(3), I(4), I(5), I(6), I(7), (const void*)(uintptr_t)a[8], P(9), P(10), J(11),
                                              F(12), P(13), P(14), F(15), stream);

@@ -56,6 +56,22 @@ __device__ __forceinline__ float act_apply(float v, int act, float slope) {
 // USF_ACT_GATE: leaky_relu_backward from the saved OUTPUT h (as usf_act_grad_f32: h > 0 ? v : v * slope)
 __device__ __forceinline__ float gate_apply(float v, float h, float slope) { return (h > 0.0f) ? v : v * slope; }
 
+// The context channel of a conditional conditioner's first convolution (usf_conv2d_same_ctx_f32): a constant plane ctx[b]
+// under zero padding contributes ctx[b] * S[co, p] with S = the sum of the channel's taps that land inside the image at p.
+// ctx_tapmask: bit t (t = dy * ks + dx) set when tap t of output pixel (py, px) reads inside the H x W image.
+__device__ __forceinline__ unsigned ctx_tapmask(int py, int px, int H, int W, int ks) {
+  if (ks == 1) return 1u;
+  const unsigned rowok = (py > 0 ? 0x007u : 0u) | 0x038u | (py + 1 < H ? 0x1c0u : 0u);
+  const unsigned colok = (px > 0 ? 0x049u : 0u) | 0x092u | (px + 1 < W ? 0x124u : 0u);
+  return rowok & colok;
+}
+// S for one output channel: wc = w_ctx + co * ks * ks, taps added in index order (deterministic)
+__device__ __forceinline__ float ctx_tapsum(const float* wc, int taps, unsigned mask) {
+  float s = 0.f;
+  for (int t = 0; t < taps; ++t) s += ((mask >> t) & 1u) ? wc[t] : 0.f;
+  return s;
+}
+
 // 64-lane sum via DPP-friendly shuffles (wavefront = 64 on gfx950)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -38,6 +38,8 @@ struct ConvArgs {
   int in_act, out_act; float in_slope, out_slope;
   const float* gate_x; int gateC;   // gated mode (GatedConv's second convolution + its gate): see usf_conv2d_same_f32
   int dbg;                     // tuning aid (USF_CONV_DBG): 1 no staging, 2 no k loop, 4 no output stores, 8 no input loads
+  const float* ctx; int ctx_stride;   // context channel (CTX instantiation only): ctx[b * ctx_stride], see usf_conv2d_same_ctx_f32
+  const float* w_ctx;          // [cout][ks * ks] weights of the context channel
 };
 
 __device__ __forceinline__ void cv_split(float x, __bf16& h, __bf16& m, __bf16& l) {
@@ -47,6 +49,8 @@ __device__ __forceinline__ void cv_split(float x, __bf16& h, __bf16& m, __bf16& 
   l = (__bf16)(r - (float)m);
 }
 
+// CTX: the context channel's rank-1 term joins the bias in the epilogue (usf_conv2d_same_ctx_f32); false: the plain kernel
+template <bool CTX>
 __global__ __launch_bounds__(512, 2) void conv2d_same_bf16x3_kernel(const ConvArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -220,6 +224,13 @@ __global__ __launch_bounds__(512, 2) void conv2d_same_bf16x3_kernel(const ConvAr
           if (r >= R) continue;
           const int sl = r / HW, p = r - sl * HW;
           float* yb = a.y + ((size_t)(s0 + sl) * a.cout) * HW + p;
+          float cx = 0.f;
+          unsigned cmask = 0u;
+          if constexpr (CTX) {
+            const int py = p / a.W;
+            cx = a.ctx[(size_t)(s0 + sl) * a.ctx_stride];
+            cmask = ctx_tapmask(py, p - py * a.W, a.H, a.W, a.ks);
+          }
           if (PC == 2 && a.gateC > 0) {
             // gated mode: the patch's two tiles are (value, gate) of the same 16 channels (rows interleaved at pack time):
             // y[c] = x[c] + value * sigmoid(gate) -- GatedConv.forward's tail (networks.py:108-122) without the [B, 2C] tensor
@@ -243,6 +254,7 @@ __global__ __launch_bounds__(512, 2) void conv2d_same_bf16x3_kernel(const ConvAr
               const int co = co0 + 16 * i + 4 * lg + j;
               if (co < a.cout && !(a.dbg & 4)) {
                 float v = acc[i][b][j] + (a.bias ? a.bias[co] : 0.f);
+                if constexpr (CTX) v += cx * ctx_tapsum(a.w_ctx + co * taps, taps, cmask);
                 yb[(size_t)co * HW] = act_apply(v, a.out_act, a.out_slope);
               }
             }
@@ -264,7 +276,8 @@ __global__ __launch_bounds__(512, 2) void conv2d_same_bf16x3_kernel(const ConvAr
 // second kernel (usf_conv_wreg.hip): 1 = launched, 0 = shape not served there, < 0 = error
 int conv2d_same_wreg(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, const void* wplanes,
                      const float* bias, const float* in_mul, int32_t in_act, float in_slope, int32_t out_act, float out_slope,
-                     const float* res_x, const float* res_mul, float res_sign, int res_mode, hipStream_t stream);
+                     const float* res_x, const float* res_mul, float res_sign, int res_mode, hipStream_t stream,
+                     const float* ctx = nullptr, int64_t ctx_stride = 0, const float* w_ctx = nullptr);
 
 static int odd16(int units) { return units | 1; }
 // register-staged iterations per thread for a group of S samples (the kernel holds at most 16 pixel pairs per thread)
@@ -297,7 +310,8 @@ int conv2d_same_fits(int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks
 
 int conv2d_same(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
                 const void* wplanes, const float* bias, const float* in_mul, int32_t in_act, float in_slope,
-                int32_t out_act, float out_slope, const float* gate_x, int64_t gate_channels, hipStream_t stream) {
+                int32_t out_act, float out_slope, const float* gate_x, int64_t gate_channels, hipStream_t stream,
+                const float* ctx, int64_t ctx_stride, const float* w_ctx) {
   if (B < 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0 || cin > 64 || cout > 64 || H * W > 256 || (ks != 1 && ks != 3) ||
       B > 0x7fffffff) {
     set_error("usf_conv2d_same_f32: unsupported sizes (channels 1..64, H * W <= 256, kernel 1 or 3)");
@@ -313,10 +327,14 @@ int conv2d_same(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, 
   if (!aligned16(wplanes)) { set_error("usf_conv2d_same_f32: weight planes must be 16-byte aligned"); return -2; }
   for (int32_t act : {in_act, out_act})
     if (act != USF_ACT_NONE && act != USF_ACT_LEAKY_RELU) { set_error("usf_conv2d_same_f32: bad act"); return -2; }
+  if (ctx && (!w_ctx || gate_x || (ctx_stride != 0 && ctx_stride != 1))) {
+    set_error("usf_conv2d_same_ctx_f32: the context channel wants w_ctx, ctx_stride 0 or 1 and no gated mode");
+    return -2;
+  }
   if (ks == 3 && !gate_x) {
     // the register-weight kernel where it serves the shape (the conditioner layers of the reference's image configurations)
     const int rc = conv2d_same_wreg(x, y, B, cin, cout, H, W, wplanes, bias, in_mul, in_act, in_slope, out_act, out_slope, nullptr,
-                                    nullptr, 0.f, 0, stream);
+                                    nullptr, 0.f, 0, stream, ctx, ctx_stride, w_ctx);
     if (rc != 0) return rc < 0 ? rc : 0;
   }
   ConvArgs a;
@@ -325,6 +343,7 @@ int conv2d_same(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, 
   a.in_act = in_act; a.out_act = out_act; a.in_slope = in_slope; a.out_slope = out_slope;
   a.dbg = (int)tuning("conv_dbg", 0);
   a.gate_x = gate_x; a.gateC = (int)gate_channels;
+  a.ctx = ctx; a.ctx_stride = (int)ctx_stride; a.w_ctx = w_ctx;
   // samples per group: as many as fit 158 KB of LDS (at most 8; at least one has to fit)
   int S = 8;
   int64_t lds = 0;
@@ -338,11 +357,12 @@ int conv2d_same(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, 
     lds = conv_lds_bytes(a.cin, a.cout, a.H, a.W, a.ks, S, &a.xs16, &a.ws16, &a.cp, &a.kp, &a.coutp);
   }
   a.S = S;
-  static bool attr_done_dev[USF_MAX_DEVICES] = {false};      // (the attribute belongs to the device)
-  bool& attr_done = attr_done_dev[current_device_slot()];
+  static bool attr_done_dev[2][USF_MAX_DEVICES] = {{false}};   // (the attribute belongs to the device and the instantiation)
+  bool& attr_done = attr_done_dev[ctx ? 1 : 0][current_device_slot()];
+  const void* kfn = ctx ? reinterpret_cast<const void*>(&conv2d_same_bf16x3_kernel<true>)
+                        : reinterpret_cast<const void*>(&conv2d_same_bf16x3_kernel<false>);
   if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_same_bf16x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024) != hipSuccess) {
+    if (hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
       set_error("usf_conv2d_same_f32: cannot raise the LDS limit");
       return -4;
     }
@@ -351,8 +371,9 @@ int conv2d_same(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, 
   const int cus = device_cu_count();
   const int64_t ngroups = (B + S - 1) / S;
   const unsigned grid = (unsigned)(ngroups < cus ? ngroups : cus);
-  hipLaunchKernelGGL(conv2d_same_bf16x3_kernel, dim3(grid), dim3(512), (size_t)lds, stream, a);
-  return check_launch("usf_conv2d_same_f32");
+  if (ctx) hipLaunchKernelGGL(conv2d_same_bf16x3_kernel<true>, dim3(grid), dim3(512), (size_t)lds, stream, a);
+  else hipLaunchKernelGGL(conv2d_same_bf16x3_kernel<false>, dim3(grid), dim3(512), (size_t)lds, stream, a);
+  return check_launch(ctx ? "usf_conv2d_same_ctx_f32" : "usf_conv2d_same_f32");
 }
 
 // y = res_x + res_sign * (res_mul * conv(...)): the last convolution of a coupling's conditioner with MaskedCoupling's

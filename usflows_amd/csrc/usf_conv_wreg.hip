@@ -47,6 +47,8 @@ struct ConvWArgs {
   int dbg;                     // tuning aid (USF_CONVW_DBG; wrong results): 1 no staging, 2 no k loop, 4 no output flush, 8 no input loads,
                                // 16 no staging-area writes, 32 no barriers
   unsigned mHW, mW, mSE;       // floor(2^32 / d) + 1 for d = H W, W, cin H W: n / d == umulhi(n, m) for n < 2^16
+  const float* ctx; int ctx_stride;   // context channel (CTX instantiations only): ctx[b * ctx_stride], see usf_conv2d_same_ctx_f32
+  const float* w_ctx;          // [cout][9] weights of the context channel
 };
 
 __device__ __forceinline__ int cw_div(int n, unsigned m) { return (int)__umulhi((unsigned)n, m); }
@@ -59,7 +61,8 @@ __device__ __forceinline__ void cw_split(float x, __bf16& h, __bf16& m, __bf16& 
 }
 
 // NB: k-blocks of 32 (= kp / 32), CP: input channels padded to a multiple of 8, NCT: 16-channel output tiles
-template <int NB, int CP, int NCT>
+// CTX: the context channel's rank-1 term joins the bias (usf_conv2d_same_ctx_f32); false: the plain kernel
+template <int NB, int CP, int NCT, bool CTX>
 __global__ __launch_bounds__(512, 2) void conv2d_same_wreg_kernel(const ConvWArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int WPC = 8 / NCT;                        // waves per output tile
@@ -266,7 +269,11 @@ __global__ __launch_bounds__(512, 2) void conv2d_same_wreg_kernel(const ConvWArg
         for (int j = 0; j < 4; ++j) {
           const int co = ct * 16 + 4 * lg + j;
           if (co < a.cout) {
-            const float v = res[t][j] + (a.bias ? a.bias[co] : 0.f);
+            float v = res[t][j] + (a.bias ? a.bias[co] : 0.f);
+            if constexpr (CTX) {
+              const int py = cw_div(p, a.mW);
+              v += a.ctx[(size_t)(gidx * a.S + sl) * a.ctx_stride] * ctx_tapsum(a.w_ctx + co * 9, 9, ctx_tapmask(py, p - py * a.W, a.H, a.W, 3));
+            }
             ostage[(sl * a.cout + co) * HW + p] = act_apply(v, a.out_act, a.out_slope);
           }
         }
@@ -293,7 +300,7 @@ __global__ __launch_bounds__(512, 2) void conv2d_same_wreg_kernel(const ConvWArg
 //   * image AND output staging area are double-buffered, ONE barrier per group.
 // Arithmetic and summation order are those of the kernel above: bit-identical results.
 // ------------------------------------------------------------------------------------------
-template <int NB, int CP, int NCT>
+template <int NB, int CP, int NCT, bool CTX>
 __global__ __launch_bounds__(512, 2) void conv2d_same_wsp_kernel(const ConvWArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int NMW = (NCT == 1) ? 2 : 4;             // multiplying waves (16 output channels: half the matrix work, the service side is the bottleneck -> 2 + 6)
@@ -357,6 +364,8 @@ __global__ __launch_bounds__(512, 2) void conv2d_same_wsp_kernel(const ConvWArgs
     struct RowTile { int base, ooff; unsigned vmask; bool live; };
     int tbase[MAXRT], toff[MAXRT];
     unsigned tmask[MAXRT];
+    int tsl[CTX ? MAXRT : 1];                           // CTX: the row's sample in its group, and its context tap sums
+    float csum[CTX ? MAXRT : 1][4];
 #pragma unroll
     for (int t = 0; t < MAXRT; ++t) {
       const int r = min((wi + WPC * t) * 16 + li, a.S * HW - 1);
@@ -367,6 +376,15 @@ __global__ __launch_bounds__(512, 2) void conv2d_same_wsp_kernel(const ConvWArgs
       tbase[t] = r * 48;
       tmask[t] = rowok & colok;
       toff[t] = (sl * a.cout + ct * 16 + 4 * lg) * HW + p;
+      if constexpr (CTX) {
+        // the context channel's tap sums S[co, p] of this row (the same pixel in every group): once per kernel
+        tsl[t] = sl;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int co = ct * 16 + 4 * lg + j;
+          csum[t][j] = co < a.cout ? ctx_tapsum(a.w_ctx + co * 9, 9, tmask[t]) : 0.f;
+        }
+      }
     }
     __syncthreads();                                    // (A) the first group's image is staged
     int cur = 0;
@@ -402,6 +420,8 @@ __global__ __launch_bounds__(512, 2) void conv2d_same_wsp_kernel(const ConvWArgs
         if (!tc.live || (a.dbg & 2)) break;               // wave-uniform (dbg 2: no matrix work)
         const RowTile tn = tile_of(t + 1);
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        float cx = 0.f;
+        if constexpr (CTX) cx = a.ctx[(size_t)min(s0 + tsl[t < MAXRT ? t : MAXRT - 1], a.B - 1) * a.ctx_stride];   // (issued under the k loop)
 #pragma unroll
         for (int blk = 0; blk < NB; ++blk) {
           if (blk + D < NB) read_blk(tc, blk + D, xf[(blk + D) % R]);
@@ -419,7 +439,11 @@ __global__ __launch_bounds__(512, 2) void conv2d_same_wsp_kernel(const ConvWArgs
         // lane (li, lg) holds channels ct * 16 + 4 lg + (0..3) of row li
         if ((wi + WPC * t) * 16 + li < R_ && ct * 16 + 4 * lg < a.cout) {        // (cout is a multiple of 4 here: 16 / 32 / 64)
 #pragma unroll
-          for (int j = 0; j < 4; ++j) ost[tc.ooff + j * HW] = act_apply(acc[j] + bias4[j], a.out_act, a.out_slope);
+          for (int j = 0; j < 4; ++j) {
+            float v = acc[j] + bias4[j];
+            if constexpr (CTX) v += cx * csum[t < MAXRT ? t : MAXRT - 1][j];   // the context channel's rank-1 term
+            ost[tc.ooff + j * HW] = act_apply(v, a.out_act, a.out_slope);
+          }
         }
         tc = tn;
       }
@@ -610,7 +634,8 @@ int conv2d_same_wreg_fits(int64_t cin, int64_t cout, int64_t H, int64_t W) {
 // returns 1 when the launch was made, 0 when the shape is not served (the caller uses the first kernel), < 0 on error
 int conv2d_same_wreg(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, const void* wplanes,
                      const float* bias, const float* in_mul, int32_t in_act, float in_slope, int32_t out_act, float out_slope,
-                     const float* res_x, const float* res_mul, float res_sign, int res_mode, hipStream_t stream) {
+                     const float* res_x, const float* res_mul, float res_sign, int res_mode, hipStream_t stream,
+                     const float* ctx, int64_t ctx_stride, const float* w_ctx) {
   if (!tuning("conv_wreg", 1)) return 0;                   // tuning aid: 0 = first kernel only
   ConvWArgs a;
   int64_t lds = 0;
@@ -636,16 +661,18 @@ int conv2d_same_wreg(const float* x, float* y, int64_t B, int64_t cin, int64_t c
   a.S = S; a.in_act = in_act; a.out_act = out_act; a.in_slope = in_slope; a.out_slope = out_slope;
   a.mHW = (unsigned)(0x100000000ULL / (uint64_t)(H * W)) + 1u; a.mW = (unsigned)(0x100000000ULL / (uint64_t)W) + 1u;
   a.mSE = (unsigned)(0x100000000ULL / (uint64_t)(cin * H * W)) + 1u;
+  a.ctx = ctx; a.ctx_stride = (int)ctx_stride; a.w_ctx = w_ctx;
+  if (ctx && res_x) { set_error("usf_conv2d_same_ctx_f32: the context channel has no residual / gate form"); return -2; }
   const int cus = device_cu_count();
   const int64_t ngroups = (B + S - 1) / S;
   const unsigned grid = (unsigned)(ngroups < cus ? ngroups : cus);
   const int nct = a.coutp / 16;
-#define USF_CW(NB_, CP_, NCT_)                                                                                     \
+#define USF_CW(NB_, CP_, NCT_, CTX_)                                                                                    \
   do {                                                                                                              \
     static bool attr_done_dev[USF_MAX_DEVICES] = {false};                                                           \
     bool& attr_done = attr_done_dev[current_device_slot()];                                                         \
     if (!attr_done) {                                                                                               \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_same_wreg_kernel<NB_, CP_, NCT_>),              \
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_same_wreg_kernel<NB_, CP_, NCT_, CTX_>),              \
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {              \
         set_error("usf_conv2d_same_f32: cannot raise the LDS limit");                                               \
         return -4;                                                                                                  \
@@ -656,43 +683,49 @@ int conv2d_same_wreg(const float* x, float* y, int64_t B, int64_t cin, int64_t c
       static bool attr2_dev[USF_MAX_DEVICES] = {false};                                                             \
       bool& attr2 = attr2_dev[current_device_slot()];                                                               \
       if (!attr2) {                                                                                                 \
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_same_wsp_kernel<NB_, CP_, NCT_>),             \
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_same_wsp_kernel<NB_, CP_, NCT_, CTX_>),             \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {            \
           set_error("usf_conv2d_same_f32: cannot raise the LDS limit");                                             \
           return -4;                                                                                                \
         }                                                                                                           \
         attr2 = true;                                                                                               \
       }                                                                                                             \
-      hipLaunchKernelGGL((conv2d_same_wsp_kernel<NB_, CP_, NCT_>), dim3(grid), dim3(512), (size_t)lds, stream, a);  \
+      hipLaunchKernelGGL((conv2d_same_wsp_kernel<NB_, CP_, NCT_, CTX_>), dim3(grid), dim3(512), (size_t)lds, stream, a);  \
     } else {                                                                                                        \
-      hipLaunchKernelGGL((conv2d_same_wreg_kernel<NB_, CP_, NCT_>), dim3(grid), dim3(512), (size_t)lds, stream, a); \
+      hipLaunchKernelGGL((conv2d_same_wreg_kernel<NB_, CP_, NCT_, CTX_>), dim3(grid), dim3(512), (size_t)lds, stream, a); \
     }                                                                                                               \
   } while (0)
-#define USF_CW_SP(NB_, CP_, NCT_)                                                                                  \
+#define USF_CW_SP(NB_, CP_, NCT_, CTX_)                                                                                 \
   do {                                                                                                              \
     static bool attr3_dev[USF_MAX_DEVICES] = {false};                                                               \
     bool& attr3 = attr3_dev[current_device_slot()];                                                                 \
     if (!attr3) {                                                                                                   \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_same_wsp_kernel<NB_, CP_, NCT_>),               \
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_same_wsp_kernel<NB_, CP_, NCT_, CTX_>),               \
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {              \
         set_error("usf_conv2d_same_f32: cannot raise the LDS limit");                                               \
         return -4;                                                                                                  \
       }                                                                                                             \
       attr3 = true;                                                                                                 \
     }                                                                                                               \
-    hipLaunchKernelGGL((conv2d_same_wsp_kernel<NB_, CP_, NCT_>), dim3(grid), dim3(512), (size_t)lds, stream, a);    \
+    hipLaunchKernelGGL((conv2d_same_wsp_kernel<NB_, CP_, NCT_, CTX_>), dim3(grid), dim3(512), (size_t)lds, stream, a);    \
   } while (0)
-#define USF_CW_NCT(NB_, CP_)                                                                                       \
-  do { if (nct == 1) USF_CW(NB_, CP_, 1); else if (nct == 2) USF_CW(NB_, CP_, 2); else USF_CW(NB_, CP_, 4); } while (0)
-  if (cin == 16) USF_CW_NCT(5, 16);
-  else if (cin == 32) USF_CW_NCT(9, 32);
-  else {                                                  // 48 input channels: the specialised kernel only
-    if (nct == 1) USF_CW_SP(14, 48, 1); else if (nct == 2) USF_CW_SP(14, 48, 2); else USF_CW_SP(14, 48, 4);
-  }
+#define USF_CW_NCT(NB_, CP_, CTX_)                                                                                 \
+  do { if (nct == 1) USF_CW(NB_, CP_, 1, CTX_); else if (nct == 2) USF_CW(NB_, CP_, 2, CTX_); else USF_CW(NB_, CP_, 4, CTX_); } while (0)
+#define USF_CW_CIN(CTX_)                                                                                           \
+  do {                                                                                                              \
+    if (cin == 16) USF_CW_NCT(5, 16, CTX_);                                                                         \
+    else if (cin == 32) USF_CW_NCT(9, 32, CTX_);                                                                    \
+    else {                                                  /* 48 input channels: the specialised kernel only */    \
+      if (nct == 1) USF_CW_SP(14, 48, 1, CTX_); else if (nct == 2) USF_CW_SP(14, 48, 2, CTX_); else USF_CW_SP(14, 48, 4, CTX_); \
+    }                                                                                                               \
+  } while (0)
+  if (ctx) USF_CW_CIN(true);
+  else USF_CW_CIN(false);
+#undef USF_CW_CIN
 #undef USF_CW_NCT
 #undef USF_CW_SP
 #undef USF_CW
-  int rc = check_launch("usf_conv2d_same_f32");
+  int rc = check_launch(ctx ? "usf_conv2d_same_ctx_f32" : "usf_conv2d_same_f32");
   return rc ? rc : 1;
 }
 

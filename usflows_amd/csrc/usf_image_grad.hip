@@ -994,4 +994,47 @@ int gated_residual_bwd(const float* dy, const float* vg, float* dvg, int64_t B, 
   return check_launch("usf_gated_residual_bwd_f32");
 }
 
+// Weight gradient of the context channel of a conditional first convolution (usf_conv_ctx_wgrad_f32):
+//   dWc[co, t] = sum_b ctx[b] * sum over p with tap t of p inside the image of dy[b, co, p]
+// One block per output channel reads its dy plane once (HBM-bound); a thread walks a fixed set of (b, p) elements, the nine tap
+// sums are reduced over the wave by a fixed butterfly and over the block's waves in index order: the same bits on every run.
+__global__ __launch_bounds__(256) void conv_ctx_wgrad_kernel(const float* __restrict__ dy, const float* __restrict__ ctx, int ctx_stride,
+                                                             int B, int cout, int H, int W, int ks, float* __restrict__ dwc) {
+  __shared__ float part[4][9];
+  const int co = blockIdx.x, tid = threadIdx.x, HW = H * W, taps = ks * ks;
+  float acc[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) acc[t] = 0.f;
+  const int64_t n = (int64_t)B * HW;
+  for (int64_t e = tid; e < n; e += 256) {
+    const int b = (int)(e / HW), p = (int)(e - (int64_t)b * HW);
+    const int py = p / W;
+    const unsigned m = ctx_tapmask(py, p - py * W, H, W, ks);
+    const float v = ctx[(size_t)b * ctx_stride] * dy[((size_t)b * cout + co) * HW + p];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) acc[t] += ((m >> t) & 1u) ? v : 0.f;
+  }
+  const int wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+  for (int t = 0; t < 9; ++t) {
+    const float v = wave_sum(acc[t]);
+    if (lane == 0) part[wave][t] = v;
+  }
+  __syncthreads();
+  if (tid < taps) dwc[co * taps + tid] = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
+}
+
+int conv_ctx_wgrad(const float* dy, const float* ctx, int64_t ctx_stride, int64_t B, int64_t cout, int64_t H, int64_t W, int64_t ks,
+                   float* dw_ctx, hipStream_t stream) {
+  if (B < 0 || cout <= 0 || H <= 0 || W <= 0 || (ks != 1 && ks != 3) || (ctx_stride != 0 && ctx_stride != 1) || B * H * W > 0x7fffffffLL) {
+    set_error("usf_conv_ctx_wgrad_f32: bad sizes (kernel 1 or 3, ctx_stride 0 or 1)");
+    return -2;
+  }
+  if (!dw_ctx) { set_error("usf_conv_ctx_wgrad_f32: null pointer"); return -1; }
+  if (B > 0 && (!dy || !ctx)) { set_error("usf_conv_ctx_wgrad_f32: null pointer"); return -1; }
+  hipLaunchKernelGGL(conv_ctx_wgrad_kernel, dim3((unsigned)cout), dim3(256), 0, stream, dy, ctx, (int)ctx_stride, (int)B, (int)cout,
+                     (int)H, (int)W, (int)ks, dw_ctx);
+  return check_launch("usf_conv_ctx_wgrad_f32");
+}
+
 }  // namespace usf

@@ -52,6 +52,8 @@ def _activation_of(f) -> Optional[Tuple[int, float]]:
 
 
 def conditioner_supported(cond: nn.Module) -> bool:
+    if getattr(cond, "consumes_context", False):
+        return False                     # (CondConvNet: the flat plan has no context column)
     if isinstance(cond, ConditionalDenseNN):
         return cond.context_dim == 1 and _activation_of(cond.f) is not None
     if isinstance(cond, DenseNN):

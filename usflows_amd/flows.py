@@ -47,6 +47,30 @@ class TransformedDistribution(tdist.TransformedDistribution):
 
 
 
+def _layer_reads_context(layer) -> bool:
+    """False for the layers that ignore a context: affine / scale layers and couplings whose conditioner ignores it
+    (ConvNet2D, the spatial ConvNet); a layer of another kind counts as reading it"""
+    from .networks import _ConvStack
+    from .transforms import (AffineTransform, BlockAffineTransform, InverseTransform, MaskedCoupling, ScaleTransform,
+                             SequentialAffineTransform)
+    if isinstance(layer, InverseTransform):
+        return _layer_reads_context(layer.transform)
+    if isinstance(layer, (ScaleTransform, BlockAffineTransform, AffineTransform, SequentialAffineTransform)):
+        return False
+    if isinstance(layer, MaskedCoupling):
+        cond = layer.conditioner
+        return not (isinstance(cond, _ConvStack) and not getattr(cond, "consumes_context", False))
+    return True
+
+
+def _reads_context_rows(layer) -> bool:
+    """a coupling whose conditioner is a CondConvNet2D / CondConvNet: it broadcasts a [B] context exactly as a [B, 1] one"""
+    from .transforms import InverseTransform, MaskedCoupling
+    if isinstance(layer, InverseTransform):
+        return _reads_context_rows(layer.transform)
+    return isinstance(layer, MaskedCoupling) and getattr(layer.conditioner, "consumes_context", False)
+
+
 class Flow(LayerLoopMixin, FitMixin, torch.nn.Module):
     """Base flow: a list of bijective layers over a base distribution (flows.py:22-378)."""
 
@@ -191,8 +215,28 @@ class Flow(LayerLoopMixin, FitMixin, torch.nn.Module):
             self._train_obj = TrainPath(self)
         return self._train_obj if self._train_obj.supported(x, context) else None
 
+    def _image_context(self, x, context):
+        """image-shaped inputs (the layer loop): a context that no layer reads is dropped -- a soft-trained flow whose
+        conditioners ignore it (ConvNet2D) takes the launches of the same flow without soft training -- and a per-row scalar
+        context that conditional conditioners read (CondConvNet2D) becomes ONE contiguous fp32 [B] device vector for the whole
+        pass (the recorded op list and the small-batch graph patch / copy that one pointer)"""
+        if context is None or not (torch.is_tensor(x) and x.dim() == 4):
+            return context
+        readers = [l for l in self.layers if _layer_reads_context(l)]
+        if not readers:
+            return None
+        # (only when every layer that reads the context is a conditional conditioner of this package, which takes [B] as the
+        # reference's [B, 1]: a conditioner of another kind keeps the caller's context as it is)
+        if all(_reads_context_rows(l) for l in readers) and x.is_cuda and torch.is_tensor(context) and not context.requires_grad:
+            from .networks import context_rows
+            rows = context_rows(context, x)
+            if rows is not None and rows.numel() == x.shape[0]:
+                return rows
+        return context
+
     def log_prob(self, x: torch.Tensor, context: Optional[torch.Tensor] = None) -> torch.Tensor:
         """log p(x) = base.log_prob(f^-1(x)) - sum_layers log|det J|   (flows.py:225-245)"""
+        context = self._image_context(x, context)
         if self._on_device_fast_path(x, context):
             return self._log_prob_device(x, context)
         path = self._train_path(x, context)
@@ -217,11 +261,11 @@ class Flow(LayerLoopMixin, FitMixin, torch.nn.Module):
                 if not getattr(e, "input_grad_only", False):
                     self._train_failed = True      # this layer list has no device backward: composite from now on
         if self._layer_loop_list_ok(x, context):
-            out = self._layer_loop_listed(x)
+            out = self._layer_loop_listed(x, context)
             if out is not None:
                 return out
         if self._layer_loop_graph_ok(x, context):
-            out = self._layer_loop_graphed(x)
+            out = self._layer_loop_graphed(x, context)
             if out is not None:
                 return out
         return self._layer_loop_log_prob(x, context)
@@ -302,8 +346,11 @@ class Flow(LayerLoopMixin, FitMixin, torch.nn.Module):
             x = eng.transform(z, "forward")
             return x.reshape(*shape, eng.D)
         y = None
-        if dev.type == "cuda" and context is None and not _needs_grad(self) and self.engine() is None:
+        if dev.type == "cuda" and not _needs_grad(self) and self.engine() is None:
+            # (with a context: the radial head all the same, then the layers with the context -- class-conditional generation)
             y = self._radial_sample_image(tuple(sample_shape), dev, seed, row_offset)
+            if y is not None and context is not None:
+                context = self._image_context(y, context)
         if y is None:
             if dev.type == "cuda" and not _needs_grad(self) and self.engine() is None:
                 self._warn_composite("Flow.sample")

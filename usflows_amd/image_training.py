@@ -62,6 +62,8 @@ def _weight_planes(w, want_transposed: bool, param=None):
         hit = batch.get(id(param))
         if hit is not None:
             return hit
+    if w is None:
+        return None, None                 # (lookup only)
     if want_transposed and w.is_cuda and w.dtype == torch.float32:
         return _ext.conv2d_weight_planes_pair(w)
     return _ext.conv2d_weight_planes(w), None
@@ -85,23 +87,42 @@ class batched_weight_planes:
 
     def __enter__(self):
         self.prev = _WSTATE.planes
-        ws = []
+        ws, srcs = [], []
         for l in self.layers:
             for m in l.modules():
                 if isinstance(m, torch.nn.Conv2d) and m.kernel_size == (3, 3) and m.weight.device == self.device \
                         and m.weight.dtype == torch.float32 and m.weight.is_contiguous():
                     ws.append(m.weight)
+                    srcs.append(m.weight.detach())
+            cond = getattr(l, "conditioner", None)
+            if getattr(cond, "consumes_context", False) and len(getattr(cond, "nn", ())) > 0:
+                # a conditional conditioner's first convolution: the planes of its C data channels (ConvSameCtxFork).  The
+                # weight's data columns are gathered into a buffer kept with the batch (refreshed in place every pass: the
+                # weight changes between steps, the buffer's address does not)
+                m = cond.nn[0]
+                if isinstance(m, torch.nn.Conv2d) and m.kernel_size == (3, 3) and m.weight.device == self.device \
+                        and m.weight.dtype == torch.float32 and m.in_channels >= 2 and id(m.weight) in {id(w) for w in ws}:
+                    i = next(j for j, w in enumerate(ws) if w is m.weight)
+                    srcs[i] = None
+                    ws[i] = (m.weight, m.in_channels - 1)
         planes = None
         if ws:
-            key = tuple((w.data_ptr(), tuple(w.shape)) for w in ws)
+            key = tuple((w[0].data_ptr(), tuple(w[0].shape), w[1]) if isinstance(w, tuple) else (w.data_ptr(), tuple(w.shape))
+                        for w in ws)
             batch = self.owner.__dict__.get("_wplanes_batch")
             if batch is None or batch.key != key:
-                batch = _ext.WeightPlanesBatch([w.detach() for w in ws])
+                bufs = [s_ if s_ is not None else torch.empty(w[0].shape[0], w[1], *w[0].shape[2:], dtype=torch.float32,
+                                                                device=self.device) for w, s_ in zip(ws, srcs)]
+                batch = _ext.WeightPlanesBatch(bufs)
+                batch.key = key
+                batch.cond_bufs = [(b_, w) for b_, w in zip(bufs, ws) if isinstance(w, tuple)]
                 if not torch.cuda.is_current_stream_capturing():
                     self.owner.__dict__["_wplanes_batch"] = batch
+            for b_, (wt, C) in getattr(batch, "cond_bufs", ()):
+                b_.copy_(wt.detach()[:, :C])
             out = batch.run()
             if out is not None:
-                planes = {id(w): pr for w, pr in zip(ws, out)}
+                planes = {id(w[0] if isinstance(w, tuple) else w): pr for w, pr in zip(ws, out)}
         _WSTATE.planes = planes
         return self
 
@@ -268,6 +289,76 @@ class ConvSameFork(torch.autograd.Function):
                 if dxs is not None:
                     dx = dx + dxs
         return dx, dW, db, None, None
+
+
+class ConvSameCtxFork(torch.autograd.Function):
+    """(conv(cat(x * in_mul, context plane)) + bias, x): the FIRST convolution of a conditional conditioner (CondConvNet2D /
+    CondConvNet, reference networks.py:513-680) in training, on usf_conv2d_same_ctx_f32 -- the concatenated tensor never
+    exists.  ``weight`` is the full [cout, C + 1, ks, ks] Parameter; ``ctx_rows`` a [1] / [B] fp32 device vector (no gradient:
+    the reference detaches the noise).  The backward returns the full weight gradient: the C data channels from
+    usf_conv_wgrad_f32, the context column from usf_conv_ctx_wgrad_f32; the data gradient is the transposed convolution over the
+    data channels with the residual branch's gradient in its output stream (as ConvSameFork)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, in_mul, ctx_rows):
+        x = x.contiguous()
+        w = weight.detach()
+        cout, C, ks = w.shape[0], w.shape[1] - 1, w.shape[2]
+        planes, ctx.planes_t = _weight_planes(None, ctx.needs_input_grad[0], weight)
+        if planes is None:
+            planes, ctx.planes_t = _weight_planes(w[:, :C].contiguous(), ctx.needs_input_grad[0])
+        wc = w[:, C].reshape(cout, ks * ks).contiguous()
+        y = _ext.conv2d_same_ctx(x, planes, cout, ks, ctx_rows, wc, bias=None if bias is None else bias.detach().contiguous(),
+                                 in_mul=in_mul)
+        ctx.save_for_backward(x, w, in_mul, ctx_rows)
+        ctx.cfg = (ks, bias is not None)
+        return y, x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, dy, dxs):
+        x, w, in_mul, ctx_rows = ctx.saved_tensors
+        ks, has_bias = ctx.cfg
+        cout, C = w.shape[0], w.shape[1] - 1
+        dy = dy.contiguous()
+        dW = db = dx = None
+        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
+            # (not deferred: the data columns are joined with the context column here, in this pass)
+            r = _ext.conv_wgrad(x, dy, ks, in_mul=in_mul, want_bias=has_bias)
+            if r is None:
+                raise RuntimeError("usflows_amd: usf_conv_wgrad_f32 does not serve this shape")
+            dWd, db = r
+            dW = torch.cat([dWd, _ext.conv_ctx_wgrad(dy, ctx_rows, ks).view(cout, 1, ks, ks)], 1)
+        if ctx.needs_input_grad[0]:
+            planes_t = ctx.planes_t if ctx.planes_t is not None else \
+                _ext.conv2d_weight_planes(w[:, :C].contiguous(), transposed=True)
+            dxs = None if dxs is None else dxs.contiguous()
+            if dxs is not None and in_mul is not None:
+                dx = _ext.conv2d_same_res(dy, planes_t, C, ks, dxs, in_mul, 1.0)
+            if dx is None:
+                dx = _ext.conv2d_same(dy, planes_t, C, ks)
+                if in_mul is not None:
+                    dx = _ext.masked_residual(None, dx, in_mul, 1.0)
+                if dxs is not None:
+                    dx = dx + dxs
+        return dx, dW, db, None, None
+
+
+def conv_ctx_shape_ok(conv, B: int, H: int, W: int) -> bool:
+    """the first convolution of a conditional conditioner (C + 1 input channels, the last one the context) has a device forward,
+    data gradient and weight gradient at [B, C, H, W]"""
+    if not isinstance(conv, torch.nn.Conv2d) or conv.in_channels < 2:
+        return False
+    k = conv.kernel_size
+    if k[0] != k[1] or k[0] not in (1, 3) or conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 \
+            or conv.padding_mode != "zeros":
+        return False
+    pad = conv.padding
+    if not (pad == "same" or (not isinstance(pad, str) and tuple(pad) == (k[0] // 2, k[0] // 2))):
+        return False
+    lib = _ext.load()
+    C, cout = conv.in_channels - 1, conv.out_channels
+    return (lib.usf_conv2d_same_fits(C, cout, H, W, k[0]) >= 2 and lib.usf_conv2d_same_fits(cout, C, H, W, k[0]) >= 2
+            and lib.usf_conv_wgrad_workspace(max(B, 1), C, cout, H, W, k[0]) > 0)
 
 
 class Pointwise(torch.autograd.Function):

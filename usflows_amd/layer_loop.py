@@ -154,10 +154,10 @@ class LayerLoopMixin:
         """the reference's loop (flows.py:236-245), layer by layer"""
         ladj_total = self._parameter_only_ladj_total(x)
         if ladj_total is not None:
-            steps = self._image_loop_steps(x) if context is None else None
+            steps = self._image_loop_steps(x)
             if steps is not None:
                 for fn in steps:
-                    x = fn(x)
+                    x = fn(x) if context is None else fn(x, context=context)
             else:
                 for layer in reversed(self.layers):
                     x = layer.backward(x, context=context) if context is not None else layer.backward(x)
@@ -318,7 +318,7 @@ class LayerLoopMixin:
                     merged[i0] = (i1, A.float().contiguous(), cvec.float().contiguous())
 
             def make(Wm, cm):
-                def run(t):
+                def run(t, context=None):                # (a channel-affine run ignores the context)
                     t = t.contiguous()
                     y = torch.empty_like(t)
                     _ext.channel_affine(t, y, Wm, bias=cm)
@@ -371,8 +371,15 @@ class LayerLoopMixin:
     list_max_rows = 4096          # USFLOWS_AMD_LOOP_LIST=0: off (and graph_max_rows = 0 switches every replay form off)
     list_max_bytes = 1 << 30
 
+    @staticmethod
+    def _loop_context_ok(x, context) -> bool:
+        """the context forms the replayed loops take: none, or the contiguous fp32 [B] device vector of Flow._image_context"""
+        return context is None or (torch.is_tensor(context) and context.is_cuda and context.dtype == torch.float32
+                                   and context.dim() == 1 and context.shape[0] == x.shape[0] and context.is_contiguous()
+                                   and not context.requires_grad)
+
     def _layer_loop_list_ok(self, x, context) -> bool:
-        return (context is None and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() >= 3
+        return (self._loop_context_ok(x, context) and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() >= 3
                 and 0 < x.shape[0] <= self.list_max_rows and self.graph_max_rows > 0 and x.is_contiguous()
                 and config.loop_list and not _needs_grad(self, x)
                 and not torch.cuda.is_current_stream_capturing())
@@ -387,12 +394,12 @@ class LayerLoopMixin:
         ver += tuple((l.mask.data_ptr(), l.mask._version) for l in self.layers if torch.is_tensor(getattr(l, "mask", None)))
         return ver
 
-    def _layer_loop_listed(self, x):
+    def _layer_loop_listed(self, x, context=None):
         """log_prob of an image-shaped batch through the recorded op list; None when it did not run (first sighting, impure
-        pass, too large)"""
+        pass, too large).  context: None or a [B] fp32 device vector, whose pointer is patched like x's"""
         ver = self._loop_versions()
         cache = self.__dict__.setdefault("_loop_lists", {})
-        key = (tuple(x.shape), str(x.device))
+        key = (tuple(x.shape), str(x.device)) + (() if context is None else ("ctx",))
         hit = cache.get(key)
         if hit is not None and hit[0] == ver:
             plan = hit[1]
@@ -402,6 +409,8 @@ class LayerLoopMixin:
             ops = plan["ops"]
             for i, j in plan["in_pos"]:
                 ops[i].u.call.a[j] = x.data_ptr()
+            for i, j in plan["ctx_pos"]:
+                ops[i].u.call.a[j] = context.data_ptr()
             for i, j in plan["out_pos"]:
                 ops[i].u.call.a[j] = out.data_ptr()
             _ext.run_ops(ops, plan["n"], x.device)
@@ -415,7 +424,7 @@ class LayerLoopMixin:
         cl = _ext.CallList()
         mode = _pure_pass_mode()
         with torch.no_grad(), _ext.recording_calls(cl), mode:
-            out = self._layer_loop_log_prob(x)
+            out = self._layer_loop_log_prob(x, context)
         plan = None
         kept = {t.untyped_storage().data_ptr(): t.untyped_storage().nbytes() for t in mode.kept}
         if cl.bad is None and not mode.impure and cl.calls and sum(kept.values()) <= self.list_max_bytes \
@@ -423,8 +432,10 @@ class LayerLoopMixin:
             xin, xout = x.data_ptr(), out.data_ptr()
             in_pos = [(i, j) for i, (_, words, isp) in enumerate(cl.calls) for j, w in enumerate(words) if isp[j] and w == xin]
             out_pos = [(i, j) for i, (_, words, isp) in enumerate(cl.calls) for j, w in enumerate(words) if isp[j] and w == xout]
-            if in_pos and out_pos:
-                plan = dict(ops=cl.ops(), n=len(cl.calls), in_pos=in_pos, out_pos=out_pos, out_shape=tuple(out.shape),
+            cin = context.data_ptr() if context is not None else None
+            ctx_pos = [(i, j) for i, (_, words, isp) in enumerate(cl.calls) for j, w in enumerate(words) if isp[j] and w == cin]
+            if in_pos and out_pos and (context is None or ctx_pos):
+                plan = dict(ops=cl.ops(), n=len(cl.calls), in_pos=in_pos, out_pos=out_pos, ctx_pos=ctx_pos, out_shape=tuple(out.shape),
                             keep=mode.kept, bytes=sum(kept.values()))
         cache[key] = (ver, plan)
         # at most 8 lists and 2 GB of kept intermediates over all of them (oldest first out)
@@ -436,19 +447,20 @@ class LayerLoopMixin:
     graph_max_rows = 256          # the reference evaluates in chunks of 100 (hyperopt.py:273-278); USFLOWS_AMD_LOOP_GRAPH=0: off
 
     def _layer_loop_graph_ok(self, x, context) -> bool:
-        return (context is None and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() >= 3
+        return (self._loop_context_ok(x, context) and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() >= 3
                 and 0 < x.shape[0] <= self.graph_max_rows and not getattr(self, "_loop_graph_off", False)
                 and config.loop_graph and not _needs_grad(self, x)
                 and not torch.cuda.is_current_stream_capturing())
 
-    def _layer_loop_graphed(self, x):
+    def _layer_loop_graphed(self, x, context=None):
         """The sync-free layer loop captured once per (input shape, parameter versions) and replayed: at 32 .. 256 rows the
         loop is ~50 dependent launches whose host side (module calls, ctypes, allocations) costs twice their GPU time --
         MNIST image configuration, 100 rows: 0.90 -> 0.43 ms.  Any failure to capture switches this off for the flow (the
-        eager loop serves the call).  Returns None when it did not run."""
+        eager loop serves the call).  context: None or a [B] fp32 device vector (a static buffer of the graph, as x).  Returns
+        None when it did not run."""
         ver = self._loop_versions()
         cache = self.__dict__.setdefault("_loop_graphs", {})
-        key = (tuple(x.shape), str(x.device))
+        key = (tuple(x.shape), str(x.device)) + (() if context is None else ("ctx",))
         hit = cache.get(key)
         if hit is None or hit[0] != ver:
             # hysteresis: a capture costs two warm-up passes and a capture pass -- several eager calls' worth.  A (shape,
@@ -463,16 +475,17 @@ class LayerLoopMixin:
             try:
                 with torch.no_grad():
                     static_x = x.detach().clone()
+                    static_c = context.detach().clone() if context is not None else None
                     side = torch.cuda.Stream(device=x.device)
                     side.wait_stream(torch.cuda.current_stream(x.device))
                     with torch.cuda.stream(side):
                         for _ in range(2):                       # caches (prep, weight planes, masks) fill outside the capture
-                            self._layer_loop_log_prob(static_x)
+                            self._layer_loop_log_prob(static_x, static_c)
                     torch.cuda.current_stream(x.device).wait_stream(side)
                     g = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g):
-                        static_out = self._layer_loop_log_prob(static_x)
-                hit = cache[key] = (ver, g, static_x, static_out)
+                        static_out = self._layer_loop_log_prob(static_x, static_c)
+                hit = cache[key] = (ver, g, static_x, static_out, static_c)
                 if len(cache) > 8:
                     cache.pop(next(iter(cache)))
             except Exception as e:                               # noqa: BLE001 -- capture is an optimisation, never a requirement
@@ -481,8 +494,10 @@ class LayerLoopMixin:
                               "small batches keep the eager loop", RuntimeWarning)
                 self._loop_graph_off = True
                 return None
-        _, g, static_x, static_out = hit
+        _, g, static_x, static_out, static_c = hit
         static_x.copy_(x)
+        if static_c is not None:
+            static_c.copy_(context)
         g.replay()
         return static_out.clone()
 

@@ -124,17 +124,19 @@ class _ConvStack(nn.Module):
     """a ``self.nn`` sequence of Conv2d / GatedConv / nonlinearity / LayerNormChannels modules on [B, C, H, W] inputs run as
     device passes (inference and training): shared by ``ConvNet2D`` and the 2-D spatial path of ``ConvNet``"""
 
-    def forward(self, x, context=None, in_mul=None, residual=None):
+    def forward(self, x, context=None, in_mul=None, residual=None, _ctx_rows=None):
         """in_mul (device path only, see ``first_conv_on_device``): a [C * H * W] mask the FIRST convolution multiplies
         into its input -- MaskedCoupling hands over the unmasked x and its mask instead of a masked copy.
         residual = (res_x, one_minus_mask, sign) (device path only): the caller is a MaskedCoupling that wants
         res_x + sign * one_minus_mask * net(x); the return value is then (tensor, done) -- done: the LAST convolution
-        wrote the coupling's output itself (usf_conv2d_same_res_f32), otherwise tensor is net(x) as usual"""
+        wrote the coupling's output itself (usf_conv2d_same_res_f32), otherwise tensor is net(x) as usual.
+        _ctx_rows (conditional subclasses, device path only): a [1] / [B] fp32 device vector -- the first convolution has one
+        input channel more than x, the constant context plane, and runs on usf_conv2d_same_ctx_f32"""
         mods = list(self.nn)
         if not (x.is_cuda and x.dtype == torch.float32):
-            assert in_mul is None and residual is None
+            assert in_mul is None and residual is None and _ctx_rows is None
             return self.nn(x)
-        if residual is None and self.train_on_device(x):
+        if residual is None and _ctx_rows is None and self.train_on_device(x):
             return self._forward_train_device(x, in_mul)
         done = False
         # the same module sequence on the device: convolutions on usf_conv2d_same_f32 (a nonlinearity behind a plain
@@ -144,6 +146,14 @@ class _ConvStack(nn.Module):
             m = mods[k]
             nxt = mods[k + 1] if k + 1 < len(mods) else None
             act = _relu_kind(m)
+            if k == 0 and _ctx_rows is not None:
+                # the conditional first convolution: data channels + the context plane's rank-1 term in one launch
+                fold = _relu_kind(nxt) if nxt is not None else None
+                if fold is not None and isinstance(mods[2] if len(mods) > 2 else None, LayerNormChannels):
+                    fold = None
+                x = _conv_hip_ctx(m, x, _ctx_rows, in_mul=in_mul, out_act=fold)
+                k += 2 if fold is not None else 1
+                continue
             if isinstance(m, nn.Conv2d) and _conv_hip_ok(m, x):
                 fold = _relu_kind(nxt) if nxt is not None else None
                 after = mods[k + 2] if k + 2 < len(mods) else None
@@ -180,6 +190,13 @@ class _ConvStack(nn.Module):
         B, C, H, W = x.shape
         mods = list(self.nn)
         k = 0
+        if getattr(self, "consumes_context", False):
+            # the conditional first convolution (ConvSameCtxFork): C data channels + the context plane, nothing folded behind it
+            m = mods[0] if mods else None
+            if not (isinstance(m, nn.Conv2d) and m.in_channels == C + 1 and it.conv_ctx_shape_ok(m, B, H, W)
+                    and len(mods) > 1 and _relu_kind(mods[1]) is None):
+                return False
+            C, k = m.out_channels, 1
         while k < len(mods):
             m = mods[k]
             nxt = mods[k + 1] if k + 1 < len(mods) else None
@@ -207,7 +224,7 @@ class _ConvStack(nn.Module):
                 return False
         return True
 
-    def _forward_train_device(self, x, in_mul=None, fork: bool = False, residual=None):
+    def _forward_train_device(self, x, in_mul=None, fork: bool = False, residual=None, ctx_rows=None):
         """fork (a MaskedCoupling caller that uses x again for its residual): returns (net(x), x') where x' is x passed through
         the first convolution's autograd node -- see image_training.ConvSameFork.  residual = (one_minus_mask, sign) with fork:
         the coupling's output x' + sign * (1 - mask) * net(x) may leave the LAST convolution's launch
@@ -218,6 +235,12 @@ class _ConvStack(nn.Module):
         x_in = x
         x_fork = None
         k = 0
+        if getattr(self, "consumes_context", False):
+            # conditional conditioner: the context plane joins the first convolution (ctx_rows None: the zero context)
+            x, xf = it.ConvSameCtxFork.apply(x, mods[0].weight, mods[0].bias, in_mul,
+                                             ctx_rows if ctx_rows is not None else _zero_row(x.device))
+            x_fork = xf if fork else None
+            k = 1
         while k < len(mods):
             m = mods[k]
             nxt = mods[k + 1] if k + 1 < len(mods) else None
@@ -475,6 +498,64 @@ def _conv_hip(conv, x, in_act=None, in_mul=None, out_act=None, residual=None):
     return (out, False) if residual is not None else out
 
 
+def _conv_ctx_ok(conv, x) -> bool:
+    """conv is the first convolution of a conditional conditioner (one input channel more than x: the context plane) and
+    usf_conv2d_same_ctx_f32 serves it on x: stride 1, "same" zero padding, kernel 1 or 3, fp32 on a ROCm device, nothing to
+    differentiate, at least two samples per LDS group"""
+    if not (isinstance(conv, nn.Conv2d) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and conv.in_channels == x.shape[1] + 1 and conv.weight.dtype == torch.float32):
+        return False
+    if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad):
+        return False
+    k = conv.kernel_size
+    if k[0] != k[1] or k[0] not in (1, 3) or conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 \
+            or conv.padding_mode != "zeros":
+        return False
+    pad = conv.padding
+    if not (pad == "same" or (not isinstance(pad, str) and tuple(pad) == (k[0] // 2, k[0] // 2))):
+        return False
+    from . import _ext
+    return _ext.load().usf_conv2d_same_fits(x.shape[1], conv.out_channels, x.shape[2], x.shape[3], k[0]) >= 2
+
+
+def _conv_hip_ctx(conv, x, ctx_rows, in_mul=None, out_act=None):
+    """usf_conv2d_same_ctx_f32 for the first convolution of a conditional conditioner: x [B, C, H, W] (unmasked when in_mul
+    is given), ctx_rows a contiguous fp32 [1] / [B] device vector; the planes of W[:, :C] and the context channel's taps
+    W[:, C] are cached per parameter version (one split launch, one small copy)"""
+    from . import _ext
+    key = (conv.weight.data_ptr(), conv.weight._version, str(x.device))
+    cache = getattr(conv, "_usf_ctx_planes", None)
+    if cache is None or cache[0] != key:
+        w = conv.weight.detach().to(x.device)
+        C = w.shape[1] - 1
+        cache = (key, _ext.conv2d_weight_planes(w[:, :C].contiguous()), w[:, C].reshape(w.shape[0], -1).contiguous())
+        conv._usf_ctx_planes = cache
+    oa, osl = out_act if out_act is not None else (_ext.ACT_NONE, 0.0)
+    bias = None if conv.bias is None else conv.bias.detach().to(torch.float32).contiguous()
+    return _ext.conv2d_same_ctx(x.contiguous(), cache[1], conv.out_channels, conv.kernel_size[0], ctx_rows, cache[2], bias=bias,
+                                in_mul=in_mul, out_act=oa, out_slope=osl)
+
+
+def context_rows(context, x):
+    """the context of a conditional conditioner's call as a contiguous fp32 [1] (one value for every row) or [B] device
+    vector when it is a per-row scalar -- a number, a 0-dim / one-element tensor, [B] or [B, 1] on x's device, the shapes the
+    reference broadcasts to [B, 1, H, W] (networks.py:573-592, 656-680) -- else None (the torch formulation serves it).
+    A contiguous fp32 [B] / [B, 1] tensor comes back as a view: no copy, the caller's pointer."""
+    B = x.shape[0]
+    if not torch.is_tensor(context):
+        if isinstance(context, (int, float)):
+            return torch.full((1,), float(context), dtype=torch.float32, device=x.device)
+        return None
+    if context.device != x.device or context.requires_grad or not (context.is_floating_point() or context.dtype in (
+            torch.int32, torch.int64)):
+        return None
+    if context.numel() == 1 and context.dim() <= x.dim():
+        return context.reshape(1).to(torch.float32).contiguous()
+    if tuple(context.shape) in ((B,), (B, 1)):
+        return context.reshape(B).to(torch.float32).contiguous()
+    return None
+
+
 class LayerNormChannels(nn.Module):
     """layer norm across the channel axis of [B, C, H, W] (networks.py:40-58)"""
 
@@ -681,3 +762,136 @@ class ConvNet2D(_ConvStack):
         layers += [conv(c_hidden, c_out)]
         self.nn = nn.Sequential(*layers)
 
+
+
+# ---- conditional conditioners (reference networks.py:513-680): the context as one more input channel ----------------------
+def _cond_device_call(net, x, context, in_mul, residual):
+    """the device form of a conditional conditioner's call, or None: x [B, C, H, W] fp32 on the device, a per-row scalar
+    context (``context_rows``; None -> the reference's zero context), nothing to differentiate, the first convolution served
+    by usf_conv2d_same_ctx_f32 -- then the [B, C + 1, H, W] concatenation never exists"""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and len(net.nn) > 1 and _conv_ctx_ok(net.nn[0], x)):
+        return None
+    if context is None:
+        rows = None
+    else:
+        rows = context_rows(context, x)
+        if rows is None:
+            return None
+    if rows is None:
+        rows = _zero_row(x.device)          # (the reference's implicit zero context, networks.py:660-661)
+    return _ConvStack.forward(net, x, None, in_mul, residual, _ctx_rows=rows)
+
+
+def _cond_train_call(net, x, context, in_mul):
+    """the conditional conditioner as differentiable device passes (training), or None"""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and net.train_on_device(x)):
+        return None
+    rows = None
+    if context is not None:
+        rows = context_rows(context, x)
+        if rows is None:
+            return None
+    return net._forward_train_device(x, in_mul, ctx_rows=rows)
+
+
+_ZERO_ROWS = {}
+
+
+def _zero_row(device):
+    z = _ZERO_ROWS.get(str(device))
+    if z is None:
+        z = _ZERO_ROWS[str(device)] = torch.zeros(1, dtype=torch.float32, device=device)
+    return z
+
+
+class CondConvNet2D(ConvNet2D):
+    """The reference's ``CondConvNet2D`` (networks.py:594-680): ``ConvNet2D`` over ``c_in + 1`` channels (``nn.0`` is
+    ``Conv2d(c_in + 1, c_hidden)``; ``c_out`` defaults to ``c_in``), the context appended as the last input channel,
+    broadcast over the image.  Same constructor signature, ``**kwargs`` forwarding, module tree and state-dict keys.  On a
+    device fp32 input with a per-row scalar context the first convolution is usf_conv2d_same_ctx_f32 (the concatenated
+    tensor never exists); every other call is the reference's formulation."""
+    consumes_context = True
+
+    def __init__(self, c_in: int, c_hidden: int = 3, c_out: int = -1, num_layers: int = 3, nonlinearity=nn.ReLU(),
+                 kernel_size: int = 3, stride: int = 1, dilation: int = 1, padding=None, **kwargs):
+        if c_out < 0:
+            c_out = c_in
+        super().__init__(c_in=c_in + 1, c_hidden=c_hidden, c_out=c_out, num_layers=num_layers, nonlinearity=nonlinearity,
+                         kernel_size=kernel_size, stride=stride, dilation=dilation, padding=padding, **kwargs)
+
+    def first_conv_on_device(self, x) -> bool:
+        return len(self.nn) > 1 and _conv_ctx_ok(self.nn[0], x)
+
+    def forward(self, x, context=None, in_mul=None, residual=None):
+        if residual is None:
+            out = _cond_train_call(self, x, context, in_mul)
+            if out is not None:
+                return out
+        out = _cond_device_call(self, x, context, in_mul, residual)
+        if out is not None:
+            return out
+        assert in_mul is None and residual is None
+        size_in = x.shape
+        if context is None:
+            context = torch.Tensor([0]).to(x.device)
+        else:
+            if not isinstance(context, torch.Tensor):
+                context = torch.tensor(context).to(x.device)
+            n_dims = len(x.shape) - len(context.shape)
+            if n_dims > 0:
+                context = context.reshape(*(tuple(context.shape) + (1,) * n_dims))
+        height, width = x.shape[-2:]
+        context = context.expand(x.shape[0], 1, height, width)
+        x = torch.cat([x, context], dim=1)
+        size_target = torch.Size([size_in[0], size_in[1] + 1, size_in[2], size_in[3]])
+        assert x.shape == size_target, f"Shape mismatch: {x.shape} != {size_target}"
+        return self.nn(x)
+
+
+class CondConvNet(ConvNet):
+    """The reference's ``CondConvNet`` (networks.py:513-592): ``ConvNet`` over ``in_dims`` with one more leading channel /
+    feature, the context appended as that channel (expanded to ``(B, 1, *spatial)``; a context that does not expand becomes
+    a zero channel).  Same constructor signature, module tree and state-dict keys.  Spatial 2-D inputs take the device
+    form of ``CondConvNet2D``; the vector path (``in_dims = [D]``) is the torch formulation only -- the flat engine does not
+    serve it (``engine.conditioner_supported`` is False)."""
+    consumes_context = True
+
+    def __init__(self, in_dims, c_hidden: List[int], c_out: int = -1, nonlinearity=nn.ReLU(), kernel_size: int = 3,
+                 stride: int = 1, dilation: int = 1, padding: Optional[int] = None, normalize_layers: bool = True,
+                 gating: bool = True, **kwargs):
+        from collections.abc import Iterable
+        if not isinstance(in_dims, Iterable):
+            raise ValueError("in_dims must be an iterable like [C, H, W]")
+        in_dims = list(in_dims)
+        super().__init__(in_dims=[in_dims[0] + 1] + in_dims[1:], c_hidden=c_hidden, c_out=c_out, nonlinearity=nonlinearity,
+                         kernel_size=kernel_size, stride=stride, dilation=dilation, padding=padding,
+                         normalize_layers=normalize_layers, gating=gating, **kwargs)
+        self._orig_in_dims = in_dims
+
+    def first_conv_on_device(self, x) -> bool:
+        return not self.is_vector and len(self.nn) > 1 and _conv_ctx_ok(self.nn[0], x)
+
+    def forward(self, x, context=None, in_mul=None, residual=None):
+        if not self.is_vector and getattr(self, "_spatial_rank", 0) == 2:
+            out = _cond_train_call(self, x, context, in_mul) if residual is None else None
+            if out is not None:
+                return out
+            out = _cond_device_call(self, x, context, in_mul, residual)
+            if out is not None:
+                return out
+        assert in_mul is None and residual is None
+        if context is None:
+            context = torch.tensor([0.0], device=x.device)
+        elif not isinstance(context, torch.Tensor):
+            context = torch.tensor(context, device=x.device)
+        n_dims = len(x.shape) - len(context.shape)
+        if n_dims > 0:
+            context = context.reshape(*context.shape, *([1] * n_dims))
+        spatial = x.shape[2:]
+        try:
+            context = context.expand(x.shape[0], 1, *spatial)
+        except Exception:       # noqa: BLE001 -- the reference's fallback (networks.py:585-588)
+            context = torch.zeros((x.shape[0], 1, *spatial), device=x.device)
+        x = torch.cat([x, context], dim=1)
+        return self.nn(x)

@@ -85,7 +85,8 @@ class TrainPath:
                 # the vector ConvNet with GatedMLP / LayerNormVector blocks (networks.py:206-245, 287-308): chain of linear launches
                 # + row passes, backward in _coupling_backward_general
                 cond = s.module.conditioner
-                if not (isinstance(cond, ConvNet) and cond.is_vector and not cond.is_plain_mlp() and context is None):
+                if not (isinstance(cond, ConvNet) and cond.is_vector and not cond.is_plain_mlp() and context is None
+                        and not getattr(cond, "consumes_context", False)):
                     return False
             if s.kind == "scale" and s.inverted:
                 return False

@@ -213,9 +213,19 @@ class MaskedCoupling(BaseTransform):
         """the layer as differentiable device passes when this call trains an image-shaped flow (image_training.py: the
         conditioner's convolutions, their weight gradients and this residual on the HIP kernels); None: not applicable"""
         cond = self.conditioner
-        if context is not None or not (torch.is_tensor(x) and x.dim() == 4 and x.is_cuda and x.dtype == torch.float32
-                                       and torch.is_grad_enabled() and hasattr(cond, "train_on_device")
-                                       and self.mask.numel() == math.prod(x.shape[1:])):
+        if not (torch.is_tensor(x) and x.dim() == 4 and x.is_cuda and x.dtype == torch.float32
+                and torch.is_grad_enabled() and hasattr(cond, "train_on_device")
+                and self.mask.numel() == math.prod(x.shape[1:])):
+            return None
+        rows = None
+        if getattr(cond, "consumes_context", False):
+            # a conditional conditioner: a per-row scalar context without gradient joins its first convolution (else: composite)
+            if context is not None:
+                from .networks import context_rows
+                rows = context_rows(context, x)
+                if rows is None:
+                    return None
+        elif context is not None:
             return None
         if not cond.train_on_device(x):
             return None
@@ -223,26 +233,47 @@ class MaskedCoupling(BaseTransform):
         # (x forks into the conditioner and the residual: the conditioner's first convolution hands x back through its own
         # autograd node, so the two gradients are summed inside its data-gradient pass)
         # (... and the residual leaves the last convolution's launch where its kernel has that form)
-        t, xs, done = cond._forward_train_device(x, self._mask_flat(x), fork=True, residual=(self._one_minus_mask(x), sign))
+        t, xs, done = cond._forward_train_device(x, self._mask_flat(x), fork=True, residual=(self._one_minus_mask(x), sign),
+                                                 **({"ctx_rows": rows} if rows is not None else {}))
         if done:
             return t
         return MaskedResidual.apply(xs if xs is not None else x, t, self._one_minus_mask(x), sign)
 
+    def _image_context(self, x, context):
+        """image-shaped inputs: the context is dropped here when the conditioner ignores it (ConvNet2D, the spatial ConvNet:
+        reference networks.py:379-403, 501-510) -- the layer then takes the launches of a call without one"""
+        if context is not None and torch.is_tensor(x) and x.dim() == 4:
+            from .networks import _ConvStack
+            cond = self.conditioner
+            if isinstance(cond, _ConvStack) and not getattr(cond, "consumes_context", False):
+                return None
+        return context
+
     def _conditioner_masked(self, x, context, sign=None):
         """conditioner(x * mask); a ConvNet2D on the device takes x and the mask and multiplies inside its first
         convolution's staging pass.  sign (+-1.0, device image path): the conditioner may also write the coupling's output
-        x + sign * (1 - mask) * t from its last convolution -- returns (tensor, done)"""
+        x + sign * (1 - mask) * t from its last convolution -- returns (tensor, done).  A conditional conditioner
+        (CondConvNet2D) with a per-row scalar context takes x, the mask and the context the same way."""
         cond = self.conditioner
-        if context is None and hasattr(cond, "first_conv_on_device") and x.dim() == 4 \
-                and self.mask.numel() == math.prod(x.shape[1:]) and use_hip(self, x) and cond.first_conv_on_device(x):
-            if sign is not None:
-                return cond(x, in_mul=self._mask_flat(x), residual=(x, self._one_minus_mask(x), sign))
-            return cond(x, in_mul=self._mask_flat(x))
+        if hasattr(cond, "first_conv_on_device") and x.dim() == 4 \
+                and (context is None or getattr(cond, "consumes_context", False)) \
+                and self.mask.numel() == math.prod(x.shape[1:]) and use_hip(self, x, context) and cond.first_conv_on_device(x):
+            if getattr(cond, "consumes_context", False):
+                from .networks import context_rows
+                if context is None or context_rows(context, x) is not None:
+                    if sign is not None:
+                        return cond(x, context, in_mul=self._mask_flat(x), residual=(x, self._one_minus_mask(x), sign))
+                    return cond(x, context, in_mul=self._mask_flat(x))
+            else:
+                if sign is not None:
+                    return cond(x, in_mul=self._mask_flat(x), residual=(x, self._one_minus_mask(x), sign))
+                return cond(x, in_mul=self._mask_flat(x))
         x_masked = x * self.mask
         t = cond(x_masked) if context is None else cond(x_masked, context)
         return (t, False) if sign is not None else t
 
     def forward(self, x, context=None):
+        context = self._image_context(x, context)
         if self._hip_ok(x, context):
             return self._hip("forward", x, context)
         y = self._image_train(x, context, 1.0)
@@ -255,6 +286,7 @@ class MaskedCoupling(BaseTransform):
         return y if y is not None else x + (1 - self.mask) * t
 
     def backward(self, y, context=None):
+        context = self._image_context(y, context)
         if self._hip_ok(y, context):
             return self._hip("backward", y, context)
         x = self._image_train(y, context, -1.0)
