@@ -1,0 +1,446 @@
+/*
+ * usflows_hip_internal.h -- the rest of libusflows_hip.so's C exports: the plumbing of the Python engine (usflows_amd) that
+ * happens to cross the C boundary.  Every backward, weight-gradient and job-queue entry point of the training path, the
+ * SophiaG optimizer, which kernel variant a descriptor selects, and the measurement / tuning aids.
+ *
+ * NO STABILITY PROMISE: anything here may change in any release.  Such a change bumps USF_INTERNAL_VERSION, never
+ * USF_ABI_VERSION, which covers usflows_hip.h alone.  A binding that mirrors this file checks usf_internal_version() next
+ * to usf_abi_version().  The boundary contract of usflows_hip.h holds for every entry point here.
+ */
+#ifndef USFLOWS_HIP_INTERNAL_H
+#define USFLOWS_HIP_INTERNAL_H
+
+#include "usflows_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define USF_INTERNAL_VERSION 1
+
+/* USF_INTERNAL_VERSION of the header the library was built from (host only, launches nothing). */
+int usf_internal_version(void);
+
+/*
+ * Training-path fields of the public descriptors (declared in usflows_hip.h, where they keep their place in the layout).
+ *
+ * usf_linear_desc::A_planes_out, ldp_out, planes_out_stride:
+ *   Optional side output (ABI 32): the three row-major bf16 planes of the INPUT A (A == p1 + p2 + p3 exactly, the
+ *   split the bf16x3 kernel makes of its operand anyway), plane p at A_planes_out + p * planes_out_stride elements,
+ *   each [ceil32(M), ldp_out] bf16 with ldp_out >= ceil32(K), ldp_out % 8 == 0; rows [M, ceil32(M)) are NOT written
+ *   (the caller's buffer holds zeros there: usf_wgrad_planes_f32 sums over them), columns [K, ceil32(K)) receive finite
+ *   padding.  This is the operand layout of usf_wgrad_planes_f32: the
+ *   data-gradient / forward GEMM of a layer hands the weight gradient of the same layer its operand already split
+ *   (flows.py:196-203: loss.backward() through every F.linear of the flow).  Not with pre_div / pre_sub.
+ *
+ * usf_coupling_desc::hidden_out, ld_hidden_out:
+ *   Optional (ABI 32): hidden_out[l] [M, ld_hidden_out] receives the activations of hidden layer l (after the
+ *   nonlinearity; the padded width, zeros in the padding) -- what the backward pass of the training step otherwise computes a
+ *   second time (two GEMMs per coupling layer; flows.py:196-203).  Only the bf16x3 kernel stores them (its eligibility rule
+ *   in usflows_hip.h): a descriptor that sets hidden_out and is served by another kernel is rejected.  ld_hidden_out % 4 == 0,
+ *   16-byte aligned bases.
+ *
+ * usf_coupling_desc::gate, ld_gate:
+ *   act == USF_ACT_GATE (ABI 32; bf16x3 kernel only, no context): hidden layer l's pre-activation is not passed through
+ *   the nonlinearity but multiplied by (gate[l][m, j] > 0 ? 1 : slope), gate[l] [M, ld_gate] -- the conditioner's BACKWARD
+ *   pass on the same kernel: with the transposed weights (W_in = W_out^T, W_hid reversed and transposed, W_out = W_in^T),
+ *   zero biases, the column segments swapped (pass <-> trans) and gate[l] = the forward's saved activation of hidden layer
+ *   n_hidden - 1 - l, the launch computes  g[:, pass] += sign * d_h1 W_in  from g[:, trans]  and hidden_out receives the
+ *   gradients at the hidden activations (d_h of the last hidden layer first): what autograd derives for the MLP of
+ *   MaskedCoupling (transforms.py:277-306, networks.py:739-751) in three GEMM launches + gates.
+ *
+ * usf_pack_planes_desc::row_weight, loc, scale, grad_base:
+ *   optional, src_cols > 0 only: the source is transformed on the way in -- the head of the TRAINING backward pass,
+ *   src = the latent z and the planes receive  g[m, c] = row_weight[m] * d/dz base_c(z[m, c])  (usf_base_logprob_grad_f32's
+ *   formulas for USF_BASE_LAPLACE / USF_BASE_NORMAL with loc / scale [src_cols]; grad_base = 1 + base id, 0 = plain copy)
+ *
+ * usf_coupling_planes_desc::hidden_out, gate:
+ *   Training (ABI 33; USF_PLANES_BF16X3, n_hidden <= 2).  Planes buffers with 8 blocks per panel (hidden width 256):
+ *     hidden_out[l] (optional, all n_hidden or none): receives the activations of hidden layer l -- the lane-local splits
+ *       the kernel makes anyway, i.e. the operands of the conditioner's weight gradients (usf_wgrad_blocked_f32) and the
+ *       gates of the backward launch.
+ *     act == USF_ACT_GATE (needs hidden_out and gate[l] for every layer): the launch runs the conditioner's data-gradient
+ *       chain -- the caller passes the transposed weight images in reverse order, zero biases and swaps the block ranges:
+ *       z = the gradient buffer, g[:, pass] += sign * MLP^T(g[:, trans]); layer l's nonlinearity is leaky_relu_backward
+ *       from the saved activations gate[l] (v * (h > 0 ? 1 : slope); only plane 0 of gate[l] is read) and hidden_out[l]
+ *       receives the gated values (the gradients at the pre-activations of forward hidden layer n_hidden - 1 - l).
+ *   Replaces autograd's backward of MaskedCoupling + its conditioner (transforms.py:277-306, networks.py:739-751) under
+ *   Flow.fit (flows.py:196-203) at batches of thousands of rows.
+ *
+ * usf_sizeof_desc(kind) also reports sizeof(usf_mt_chunk|usf_grad_job|usf_psum_job) for kind 8|11|12.
+ */
+
+/*
+ * Which kernel family / instantiation usf_linear_f32 would launch for this descriptor (nothing is launched):
+ *   1000                          small-batch kernel (M <= 768)
+ *   2000 + 100 TM + 10 TN + WM    exact-f32 MFMA tile
+ *   3000 + 100 TN + 10 WM + NB    bf16x3 tile (TN x 32 columns, WM waves x 32 rows, NB weight buffers)
+ * 0 for a descriptor with empty extents.  The parity tests use it to prove that every instantiation the BASELINE
+ * configurations select is compared with the reference arithmetic (tests/test_configs_gpu.py).
+ */
+int usf_linear_variant(const usf_linear_desc* d);
+
+/* which kernel usf_coupling_additive_f32 launches for this descriptor (nothing is launched, no pointer is dereferenced):
+ * 3 the tiny-layer kernel (M <= 256, segments and hidden widths <= 64, the layer's images in 64 KB of LDS: usf_coupling_tiny.hip),
+ * 2 the bf16x3 kernel, 1 the exact-f32 MFMA kernel, 0 for a NULL descriptor */
+int usf_coupling_variant(const usf_coupling_desc* d);
+
+/*
+ * The backward of usf_radial_logprob_f32 (usflows_hip.h), same operands:
+ * usf_radial_logprob_grad_f32: from g_lp [M] (gradient at logp) and the saved r:
+ *     g[m,d]   = g_lp[m] * dlogp/dr * dr/dz[m,d]   (0 for D <= d < ldg; ATen's norm backward: p = 1 sign(t), p = 2 t / r,
+ *                                                   p = inf sign(t) / (number of d with |t| == r) where |t| == r: tied
+ *                                                   maxima share the gradient evenly, as x.norm(p=inf) does)
+ *     r == 0 (z == loc exactly): log r = -inf and (D - 1) / r = inf enter the row as they do in the reference
+ *     (distributions.py:506-549): logp is +-inf or NaN depending on the norm distribution and the row of g is NaN (p = 2: t / r
+ *     is taken as 0) -- nothing is clamped.
+ *     d_loc[d] = -sum_m g[m,d];   d_a / d_b / d_logits [K] = gradients of the STORED parameters (chain rule through softplus)
+ * each output pointer but g is optional.  z == NULL (both entry points): the radii are GIVEN -- the forward reads r_out as its
+ * input, the backward writes g [M] = the gradient at r (d_loc must be NULL): the finishing formula alone, for callers whose own
+ * tail kernel reduces the radius (the flat training path).  Partial sums are added in a fixed order (bit-reproducible).  workspace: at least
+ * usf_radial_logprob_grad_workspace(M, D) bytes, 8-byte aligned.
+ */
+int64_t usf_radial_logprob_grad_workspace(int64_t M, int64_t D);
+int usf_radial_logprob_grad_f32(const float* z, int64_t ldz, const float* r, const float* g_lp, int64_t M, int64_t D, int32_t p_id,
+                                const float* loc, int32_t norm, int32_t K, const float* par_a, const float* par_b,
+                                const float* logits, float* g, int64_t ldg, float* d_loc, float* d_a, float* d_b, float* d_logits,
+                                void* workspace, int64_t workspace_bytes, usf_stream_t stream);
+
+/* usf_conv_ctx_wgrad_f32 (ABI 36): the weight gradient of the context channel of usf_conv2d_same_ctx_f32 (usflows_hip.h;
+ * reference networks.py:513-680 under autograd),
+ *   dw_ctx[co, t] = sum_b ctx[b * ctx_stride] * sum over the p whose tap t lands inside the image of dy[b, co, p]
+ * dy [B, cout, H, W] contiguous fp32, dw_ctx [cout, ks * ks].  One block per output channel reads its dy plane once; the sums
+ * run in a fixed order (same bits on every run) and need no workspace and no second launch.  The data channels' weight and
+ * bias gradients are usf_conv_wgrad_f32's, the data gradient the usual transposed convolution over the cin data channels;
+ * there is no gradient with respect to the context. */
+int usf_conv_ctx_wgrad_f32(const float* dy, const float* ctx, int64_t ctx_stride, int64_t B, int64_t cout, int64_t H, int64_t W,
+                           int64_t ks, float* dw_ctx, usf_stream_t stream);
+
+/*
+ * Gradients of the image-shaped coupling layer's pieces: what torch autograd computes for networks.py:40-122, 405-510 and the
+ * 1 x 1 convolution of transforms.py:904-962 when Flow.fit (flows.py:113-210) trains an image flow.  All tensors contiguous
+ * fp32; sums over the batch are deterministic (per-wave partial sums in the caller's workspace, added in a fixed order).
+ *
+ * usf_conv_wgrad_f32: weight and bias gradient of a stride-1 "same" convolution with kernel ks = 1 or 3,
+ *     dW[co, ci, ky, kx] = sum_{b, p} dy[b, co, p] * xin[b, ci, p + (ky - ks/2, kx - ks/2)]     (nn.Conv2d weight layout [cout, cin, ks, ks])
+ *     db[co]             = sum_{b, p} dy[b, co, p]                                             (db may be NULL)
+ *   with xin = in_act(x - pre_sub[ci]) * in_mul -- the input transforms of usf_conv2d_same_f32 (in_act, in_mul) and of
+ *   usf_channel_affine_f32 (pre_sub), each optional -- and zeros outside the image.  Exact fp32 products and sums on
+ *   v_mfma_f32_16x16x4_f32.  Served: cin, cout multiples of 16 up to 64 (kernel 3: cin * cout <= 1536), H * W <= 64, W >= 2, 16-byte
+ *   aligned tensors; returns 1 (nothing written) for other shapes, 0 when done, < 0 on error.  workspace: at least
+ *   usf_conv_wgrad_workspace(...) floats (0 = shape not served).  The DATA gradient of these layers is the forward entry point
+ *   on the flipped, transposed weight (usf_conv2d_same_f32 / usf_pointwise_conv_f32 / usf_channel_affine_f32).
+ * usf_layernorm_channels_bwd_f32: backward of usf_layernorm_channels_f32 (same x, gamma, eps, act, slope):
+ *     dx [B, C, P]; dgamma_dbeta [2 C] = (sum dy * xhat, sum dy); workspace >= usf_layernorm_channels_bwd_workspace(B, C, P) floats.
+ * usf_gated_residual_bwd_f32: backward of usf_gated_residual_f32 with respect to vg: dvg [B, 2C, P] =
+ *     (dy * sigmoid(gate), dy * val * sigmoid(gate) * (1 - sigmoid(gate))); the gradient with respect to x is dy itself.
+ */
+/* Deferred sums of per-wave partial slots (the last stage of usf_conv_wgrad_f32) and many of them in ONE launch.
+ * usf_conv_wgrad_deferred_f32 = usf_conv_wgrad_f32 that stops in front of that stage: job[0 .. 1] (HOST memory, two entries)
+ * then describe what remains -- job[1] the final round that writes dW / db, job[0] the first round into the workspace's
+ * scratch rows when there are more than 64 slots (job[0].nparts == 0: a single round).  dW / db stay UNWRITTEN until
+ * usf_partial_sum_jobs_f32 launches containing first job[0] (if any), then job[1] have run in this stream order; the workspace
+ * must stay alive until then.
+ * usf_partial_sum_jobs_f32: jobs / block_job are DEVICE arrays: job j owns the blocks [first_block, first_block +
+ * ceil(n / 64) * rows) -- ceil(n / 256) * rows when vec4 != 0 (mode 0, n a multiple of 4, 16-byte aligned part / out: four
+ * columns per thread) -- and block_job[b] names block b's job (n_blocks entries).  Row r of a job sums the slots
+ * [r * per, min((r + 1) * per, nparts)) in the order usf_conv_wgrad_f32's own rounds use: same bits.
+ * Why: at the reference's training batch (32 rows, experiments/mnist/mnist.yaml:34) a backward pass of the live MNIST
+ * configuration ends ~165 weight gradients with one or two such launches of a few microseconds each, all on the chain of
+ * dependent launches that bounds the step; queued, they are two launches behind the pass. */
+typedef struct usf_psum_job {
+  const float* part; float* out; float* out2;
+  int32_t nparts, n, mode, cin, cout, CIT, T, ntile;
+  int32_t first_block, per, rows, vec4;
+} usf_psum_job;
+int usf_conv_wgrad_deferred_f32(const float* x, const float* dy, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
+                                const float* in_mul, const float* pre_sub, int32_t in_act, float in_slope, float* dW, float* db,
+                                float* workspace, int64_t workspace_floats, usf_psum_job* job, usf_stream_t stream);
+int usf_partial_sum_jobs_f32(const usf_psum_job* jobs, const int32_t* block_job, int64_t n_blocks, usf_stream_t stream);
+/* The weight-gradient kernel itself queued as well (small batches: one weight gradient occupies an eighth of the chip).
+ * usf_conv_wgrad_plan_f32 = usf_conv_wgrad_deferred_f32 that launches NOTHING when the shape runs on the LDS-staged kernel: it
+ * fills *wjob (HOST memory; blocks > 0) with that kernel's arguments -- the caller later runs all queued jobs of equal
+ * (CIT, COT, T) with ONE usf_conv_wgrad_jobs_f32 launch (jobs / block_job DEVICE arrays as for usf_partial_sum_jobs_f32: job j
+ * owns the blocks [first_block, first_block + blocks), first_block set by the caller; lds_bytes = the largest of the jobs')
+ * and then the sums job[0 .. 1] describe.  x, dy, in_mul, pre_sub and the workspace must stay alive and unchanged until then.
+ * wjob->blocks == 0 on return: the shape runs on the direct kernel-1 form, which HAS been launched (only the sums remain). */
+typedef struct usf_wgrad_job {
+  unsigned char args[192];                      /* the kernel's arguments (opaque) */
+  int32_t CIT, COT, T, blocks, lds_bytes, first_block;
+} usf_wgrad_job;
+int usf_conv_wgrad_plan_f32(const float* x, const float* dy, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
+                            const float* in_mul, const float* pre_sub, int32_t in_act, float in_slope, float* dW, float* db,
+                            float* workspace, int64_t workspace_floats, usf_psum_job* job, usf_wgrad_job* wjob, usf_stream_t stream);
+int usf_conv_wgrad_jobs_f32(const usf_wgrad_job* jobs, const int32_t* block_job, int64_t n_blocks, int32_t CIT, int32_t COT, int32_t T,
+                            int32_t lds_bytes, usf_stream_t stream);
+int64_t usf_conv_wgrad_workspace(int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks);
+int usf_conv_wgrad_f32(const float* x, const float* dy, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
+                       const float* in_mul, const float* pre_sub, int32_t in_act, float in_slope, float* dW, float* db,
+                       float* workspace, int64_t workspace_floats, usf_stream_t stream);
+int64_t usf_layernorm_channels_bwd_workspace(int64_t B, int64_t C, int64_t P);
+int usf_layernorm_channels_bwd_f32(const float* x, const float* dy, float* dx, int64_t B, int64_t C, int64_t P, const float* gamma,
+                                   float eps, int32_t act, float slope, float* dgamma_dbeta, float* workspace,
+                                   int64_t workspace_floats, usf_stream_t stream);
+int usf_gated_residual_bwd_f32(const float* dy, const float* vg, float* dvg, int64_t B, int64_t CP, usf_stream_t stream);
+
+/* usf_conv2d_weight_planes_f32(transposed = 2) for MANY weights in one launch.  jobs / block_job are DEVICE arrays (as for
+ * usf_partial_sum_jobs_f32): job j splits the fp32 weight w [cout, cin, ks, ks] into its planes followed by the planes of its
+ * data-gradient convolution, at planes_base + out_off (bf16 elements; usf_conv2d_weight_elems(cin, cout, ks) +
+ * usf_conv2d_weight_elems(cout, cin, ks) of them), and owns the blocks [first_block, first_block + ceil(max of the two
+ * [rows x K] sizes / 256)); block_job[b] names block b's job.  Same bits as the single launches. */
+typedef struct usf_wplanes_job {
+  const float* w; int64_t out_off;
+  int32_t cin, cout, ks, first_block;
+} usf_wplanes_job;
+int usf_conv2d_weight_planes_batch_f32(const usf_wplanes_job* jobs, const int32_t* block_job, int64_t n_blocks, void* planes_base,
+                                       usf_stream_t stream);
+
+/* usf_gated_tail_bwd_f32: the backward of usf_gated_tail_f32 (usflows_hip.h, same operands) in ONE launch.  It replaces the
+ * chain usf_layernorm_channels_bwd_f32 -> usf_gated_residual_bwd_f32 -> usf_pointwise_conv_f32 on a transposed copy of W ->
+ * usf_conv_wgrad_f32 (kernel 1): the backward recomputes val / gate / r from (h, x) and writes dx [B, C, P] (the skip branch), dh [B, C, P] and
+ * dparams = [dW (2 C C) | dbias (2 C) | dgamma (C) | dbeta (C)] (the last two only with a layer norm); dvg [B, 2 C, P] =
+ * d[val, gate] is written when the pointer is not NULL.  workspace >= usf_gated_tail_workspace floats.
+ * job == NULL: dparams is complete when the call's launches have run; else job[0 .. 1] (HOST memory) describe its last
+ * sum for usf_partial_sum_jobs_f32 as usf_conv_wgrad_deferred_f32 does (nparts == 0: nothing to do).
+ * Eight lanes share a pixel: made for few pixels (a 32-row training batch); HBM traffic 4 C (3 + 2) bytes per pixel backward. */
+int64_t usf_gated_tail_workspace(int64_t B, int64_t C, int64_t P);
+int usf_gated_tail_bwd_f32(const float* h, const float* x, const float* dy, float* dx, float* dh, float* dvg, int64_t B, int64_t C,
+                           int64_t P, const float* W, const float* bias, int32_t in_act, float in_slope, int32_t post_act,
+                           float post_slope, const float* ln_gamma, const float* ln_beta, float ln_eps, float* dparams,
+                           float* workspace, int64_t workspace_floats, struct usf_psum_job* job, usf_stream_t stream);
+
+/* A data-gradient convolution with the factors of the layer's INPUT transforms in its output stream:
+ *   y = conv(x) * (gate_h > 0 ? 1 : gate_slope) * gate_mul          (gate_add == NULL)
+ *   y = gate_add + conv(x) * (gate_h > 0 ? 1 : gate_slope)          (gate_add != NULL; then gate_mul must be NULL)
+ * gate_h [B, cout, H, W] = the forward layer's input (its (Leaky)ReLU's derivative; gate_slope 0 = ReLU, 1 = no nonlinearity),
+ * gate_mul [cout * H * W] or NULL = the forward layer's input mask, gate_add [B, cout, H, W] or NULL = the gradient that
+ * reaches the same tensor along another branch (the forward input forks: GatedConv's skip connection, networks.py:108-122).
+ * The arithmetic of usf_conv2d_same_f32 followed by usf_act_grad_f32 and the mask product / the sum, in one pass.  Returns 0
+ * when done, 1 when the shape is not served by this form (as usf_conv2d_same_res_f32), < 0 on error. */
+int usf_conv2d_same_gate_f32(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
+                             const void* w_planes, const float* gate_h, float gate_slope, const float* gate_mul,
+                             const float* gate_add, usf_stream_t stream);
+
+/* which instantiation of usf_gemm_planes_bf16x3 serves the descriptor (nothing is launched): 5000 + 10 TN + (1: fp32 output, 0: planes output),
+ * TN = column-block width in 32-feature blocks (4 or 5, whichever pads the output less); 0 for empty extents */
+int usf_gemm_planes_variant(const usf_gemm_planes_desc* d);
+
+/* The backward twin of usf_gated_norm_rows_f32 (usflows_hip.h; ABI 34): what torch.autograd derives from GatedMLP's gate (networks.py:222-245) and LayerNormVector
+ * (:206-219) in Flow.fit, rows of [M, C] fp32, r / mean / variance recomputed from (skip, vg) as the forward computes them:
+ *     g = dy * gamma;  dr = (g - mean_c g - xh * mean_c(g xh)) / sqrt(var r + eps)        (gamma == NULL: dr = dy)
+ *     d_skip = dr;  d_vg[:, :C] = dr * sigmoid(gate);  d_vg[:, gate_off:] = dr * val * sigmoid(gate) (1 - sigmoid(gate))
+ *     dy_xh = dy * xh  (optional, needs gamma: dgamma = its column sums, dbeta = the column sums of dy -- usf_colsum_f32)
+ * Columns [C, c_pad) of every output are written as zeros (operand padding of the GEMMs that follow); gate_off >= c_pad. */
+typedef struct usf_gated_norm_bwd_desc {
+  const float* skip;   int64_t ld_skip;
+  const float* vg;     int64_t ld_vg;    int64_t gate_off;
+  const float* gamma;
+  const float* dy;     int64_t ld_dy;
+  float*       d_skip; int64_t ld_d_skip;
+  float*       d_vg;   int64_t ld_d_vg;
+  float*       dy_xh;  int64_t ld_dy_xh;
+  int64_t M, C, c_pad;
+  float eps, reserved;
+} usf_gated_norm_bwd_desc;
+int usf_gated_norm_rows_bwd_f32(const usf_gated_norm_bwd_desc* d, usf_stream_t stream);
+
+/* The last step of LUTransform's parameter gradients under Flow.fit (what autograd derives through transforms.py:1271-1320's
+ * tril(L_raw, -1) + I and triu(U_raw), and the log-det term sum log|diag U|), for n blocks at once, fp64 in / fp32 out:
+ *     dL_out[i] = tril(dL[i] (+ TL[i]), -1)                     dU_out[i] = triu(dU[i] (+ TU[i])) + diag(c[i] / diag(U_i))
+ * dL / dU [n, D, D]: the chain-rule products (only the wanted triangle has to be valid); TL / TU: the products of the M = L U
+ * usages, or NULL; c [n]: coefficient of the log-det term; tri [2n, D, D] as usf_lu_prepare_f64 leaves it (U_i^T at 2i + 1).
+ * One pass instead of triu / tril / diagonal add / sums / converting copies over [n, D, D] tensors. */
+int usf_lu_grad_finish_f64(const double* dL, const double* dU, const double* TL, const double* TU, const double* c,
+                           const double* tri, int64_t n, int64_t D, float* dL_out, float* dU_out, usf_stream_t stream);
+
+/*
+ * ---- backward pass of the training step -----------------------------------------------
+ * Flow.fit (flows.py:196-199) differentiates -log_prob(batch).mean(); these are the batch-sized pieces of that
+ * backward pass (usf_train.hip).  Data gradients of the linear layers are usf_linear_f32 launches on the transposed
+ * weight image (usf_pack_weight_f32 with transpose = 1).
+ *
+ * usf_wgrad_f32: G[n,k] = alpha * sum_m Y[m,n] * A[m,k] + beta * G[n,k]   -- the weight gradient of F.linear
+ *   (Y = gradient at the layer's output [M,N], A = the layer's input [M,K]); exact-f32 MFMA, the batch is cut into
+ *   row ranges whose partial products are summed in a fixed order (bitwise reproducible).  Y / A rows must be 16-byte
+ *   aligned (ld % 4 == 0).  workspace: at least usf_wgrad_workspace_floats(M,N,K) floats.  mode 0: exact-f32 MFMA;
+ *   mode 1: the bf16x3 split of DESIGN.md 3.1b (fp32-equivalent accuracy on the bf16 matrix cores; used from M >= 2048;
+ *   from 8192 rows with enough output tiles to fill the chip, and while (M + 448) * max(ldy, lda) * 4 < 2^32, the
+ *   loader-wave kernel: it reads Y / A with 16-byte loads up to the end of the row extent ((M-1) * ld + N resp. K
+ *   floats from the base pointer) -- the same memory the contract above names).
+ * usf_wgrad_variant: which kernel such a call launches -- 0 exact-f32, 1 bf16x3 (256 threads), 2 bf16x3 with loader
+ *   waves (introspection for the parity tests).
+ * usf_colsum_f32: out[n] = alpha * sum_m Y[m,n] + beta * out[n]           -- the bias gradient; workspace
+ *   (ceil(M/256) + ceil(M/65536) + 2) * N floats (partials of the 256-row levels).
+ */
+int usf_wgrad_f32(const float* Y, int64_t ldy, const float* A, int64_t lda, int64_t M, int64_t N, int64_t K, float* G,
+                  int64_t ldg, float alpha, float beta, int32_t mode, float* workspace, int64_t workspace_floats,
+                  usf_stream_t stream);
+int64_t usf_wgrad_workspace_floats(int64_t M, int64_t N, int64_t K);
+int usf_wgrad_variant(int64_t M, int64_t N, int64_t K, int64_t ldy, int64_t lda, int32_t mode);
+/* usf_wgrad_f32 and the layer's bias gradient in one pass (ABI 32): colsum_out[n] = cs_alpha * sum_m Y[m,n] + cs_beta *
+ * colsum_out[n] (what usf_colsum_f32 computes), from the operand fragments the bf16x3 kernels hold anyway -- three more
+ * MFMAs per fragment row against an operand of ones in the blocks of tile column 0; partial sums in a fixed order.  Only
+ * where usf_wgrad_bias_ok says 1 (usf_wgrad_variant >= 1, i.e. mode 1 from 2048 rows, and K >= 64); the same workspace
+ * as usf_wgrad_f32. */
+int usf_wgrad_bias_f32(const float* Y, int64_t ldy, const float* A, int64_t lda, int64_t M, int64_t N, int64_t K, float* G,
+                       int64_t ldg, float alpha, float beta, int32_t mode, float* colsum_out, float cs_alpha, float cs_beta,
+                       float* workspace, int64_t workspace_floats, usf_stream_t stream);
+int usf_wgrad_bias_ok(int64_t M, int64_t N, int64_t K, int64_t ldy, int64_t lda, int32_t mode);
+int usf_colsum_f32(const float* Y, int64_t ldy, int64_t M, int64_t N, float* out, float alpha, float beta,
+                   float* workspace, int64_t workspace_floats, usf_stream_t stream);
+
+/*
+ * The weight gradient from PRE-SPLIT operands (ABI 32).  usf_wgrad_f32's loader waves split every fp32 operand value
+ * into its three bf16 planes again in each of the blocks that share its rows (seven times at 784 x 784); here Y and A
+ * arrive as the planes the layer's own GEMMs already made of them (usf_linear_desc::A_planes_out: the forward GEMM
+ * splits the layer input, the data-gradient GEMM the output gradient), or as usf_split_planes_f32 writes them:
+ *   plane p of an operand at base + p * plane_stride elements, each [ceil32(M), ld] bf16 row-major, ld % 8 == 0,
+ *   plane_stride % 8 == 0, plane_stride >= ceil32(M) * ld, 16-byte aligned base, rows [M, ceil32(M)) zero,
+ *   the three planes of one operand below 4 GiB; x == p0 + p1 + p2 exactly (round-to-nearest residual split).
+ * usf_wgrad_planes_f32: G[n,k] = alpha * sum_m Y[m, y_off + n] * A[m, a_off + k] + beta * G[n,k]  (y_off, a_off % 8 == 0)
+ *   -- the same six products per value pair in the same order as usf_wgrad_f32 mode 1, one block per CU over row ranges
+ *   of equal length, partial sums added in a fixed order (bitwise reproducible).  workspace: at least
+ *   usf_wgrad_planes_workspace_floats(M, N, K) floats.  usf_wgrad_planes_ok: 1 where the kernel pays (the loader-wave
+ *   kernel's cross-over: M >= 8192 and enough tiles), else 0 -- callers then keep usf_wgrad_f32.
+ *   colsum_out (may be NULL; needs usf_wgrad_planes_colsum_ok = K >= 64): colsum_out[n] = cs_alpha * sum_m Y[m, y_off + n]
+ *   + cs_beta * colsum_out[n] -- the layer's bias gradient (usf_colsum_f32) from the fragments the kernel holds anyway:
+ *   three more MFMAs per fragment row against an operand of ones in the blocks of tile column 0.
+ * usf_split_planes_f32: P[p][m][c] for m < ceil32(M), c < ldp: the planes of X[m, c] (zeros for m >= M or c >= N).
+ * Replaces: the weight-gradient half of autograd's F.linear backward (flows.py:196-203, transforms.py:913-962,
+ * networks.py:739-751) at training batches of thousands of rows.
+ */
+int usf_wgrad_planes_f32(const void* Y_planes, int64_t ldyp, int64_t y_plane_stride, int64_t y_off, const void* A_planes,
+                         int64_t ldap, int64_t a_plane_stride, int64_t a_off, int64_t M, int64_t N, int64_t K, float* G,
+                         int64_t ldg, float alpha, float beta, float* colsum_out, float cs_alpha, float cs_beta, float* workspace,
+                         int64_t workspace_floats, usf_stream_t stream);
+int64_t usf_wgrad_planes_workspace_floats(int64_t M, int64_t N, int64_t K);
+int usf_wgrad_planes_ok(int64_t M, int64_t N, int64_t K);
+int usf_wgrad_planes_colsum_ok(int64_t M, int64_t N, int64_t K);
+int usf_split_planes_f32(const float* X, int64_t ldx, int64_t M, int64_t N, void* planes, int64_t ldp, int64_t plane_stride,
+                         usf_stream_t stream);
+/* The same weight gradient with both operands in the BLOCKED planes format of the planes pipeline (ABI 33) -- the buffers the
+ * training forward's usf_gemm_planes_bf16x3 / usf_coupling_planes launches leave behind and the backward's launches write:
+ *   G[n,k] = alpha * sum_m Y[m, 32 y_kb0 + n] * A[m, 32 a_kb0 + k] + beta * G[n,k],   n < N, k < K  (LOGICAL positions),
+ * Y / A planes buffers of ceil(M/16) panels with y_nkb / a_nkb blocks per panel (USF_PLANES_BF16X3), N <= 32 (y_nkb - y_kb0),
+ * K <= 32 (a_nkb - a_kb0).  Rows [M, 16 ceil(M/16)) of Y must hold zeros (they do in every buffer whose producer chain
+ * starts at usf_pack_planes_f32 and has no bias); those of A must be finite.  Same kernel, schedule, order of products,
+ * workspace (usf_wgrad_planes_workspace_floats) and colsum_out semantics as usf_wgrad_planes_f32; a buffer must stay below
+ * 2 GiB.  Loader waves copy whole 1-KiB chunks; the MFMA waves' transposing reads un-do the slot order, so G comes out in
+ * logical order. */
+int usf_wgrad_blocked_f32(const void* Y_planes, int64_t y_nkb, int64_t y_kb0, const void* A_planes, int64_t a_nkb, int64_t a_kb0,
+                          int64_t M, int64_t N, int64_t K, float* G, int64_t ldg, float alpha, float beta, float* colsum_out,
+                          float cs_alpha, float cs_beta, float* workspace, int64_t workspace_floats, usf_stream_t stream);
+/* The reduction of usf_wgrad_blocked_f32 queued (round 5; large-batch training: 129 weight gradients per step end with a reduction of
+ * ~18 us each, one after the other although only the parameter update waits for them).  usf_wgrad_blocked_plan_f32 = the same call
+ * that launches the multiply kernel only and fills *job (HOST memory): G / colsum_out stay unwritten and the workspace stays in use
+ * until a usf_wgrad_reduce_jobs_f32 launch containing the job has run (jobs / block_job DEVICE arrays as for
+ * usf_partial_sum_jobs_f32: job j owns the blocks [first_block, first_block + blocks), first_block set by the caller).  Same
+ * additions in the same order as the undeferred call: same bits. */
+typedef struct usf_wreduce_job {
+  const float* part; float* out; const float* cs_part; float* cs_out;
+  int64_t rows, cols, ldo;
+  float alpha, beta, cs_alpha, cs_beta;
+  int32_t first_block, blocks;
+  unsigned char sched[64];                      /* the schedule's tile classes (opaque) */
+} usf_wreduce_job;
+int usf_wgrad_blocked_plan_f32(const void* Y_planes, int64_t y_nkb, int64_t y_kb0, const void* A_planes, int64_t a_nkb, int64_t a_kb0,
+                          int64_t M, int64_t N, int64_t K, float* G, int64_t ldg, float alpha, float beta, float* colsum_out,
+                          float cs_alpha, float cs_beta, float* workspace, int64_t workspace_floats, usf_wreduce_job* job, usf_stream_t stream);
+int usf_wgrad_reduce_jobs_f32(const usf_wreduce_job* jobs, const int32_t* block_job, int64_t n_blocks, usf_stream_t stream);
+
+/* Many small weight / bias gradients in ONE launch.  At the reference's training batch (32 rows, tests/explib/mnist.yaml:34)
+ * Flow.fit's backward pass (flows.py:196-199) asks for one weight and one bias gradient per F.linear on the path -- some
+ * hundreds of launches of a few microseconds whose dispatch, not their work, bounds the step.  `jobs` is a DEVICE array;
+ * `block_job` a DEVICE array with the job index of every block of the launch (n_blocks entries; job j owns the blocks
+ * first_block .. first_block + its own count - 1, in order):
+ *   A != NULL: G[n,k] = alpha * sum_m Y[m,n] A[m,k] + beta * G[n,k], ceil(N/128) * ceil(K/128) blocks, exact-f32 MFMA over
+ *              one row range -- bit-identical to usf_wgrad_f32 (mode 0) on the same operands for M <= 256; the alignment
+ *              rules of usf_wgrad_f32 apply;
+ *   A == NULL: G[n] = alpha * sum_m Y[m,n] + beta * G[n], ceil(N/64) blocks (fixed summation order: reproducible).
+ * Meant for M <= 256; jobs of one launch must not write what another job of the same launch reads or writes. */
+typedef struct usf_grad_job {
+  const float* Y;
+  const float* A;
+  float* G;
+  int64_t ldy, lda, ldg;
+  int32_t M, N, K, first_block;
+  float alpha, beta;
+} usf_grad_job;
+int usf_grad_jobs_f32(const usf_grad_job* jobs, const int32_t* block_job, int64_t n_blocks, usf_stream_t stream);
+
+/*
+ * SophiaG over all parameter tensors of a model in one launch (sophia.py:39-58 update_hessian, 151-199
+ * _single_tensor_sophiag -- the optimiser Flow.fit defaults to, flows.py:116).  `chunks` is a DEVICE array; a chunk is
+ * one block's share (any length; the host side cuts tensors into pieces of 16 384 elements) of one fp32 parameter
+ * tensor p with its gradient g, momentum m (exp_avg) and Hessian estimate h.
+ *   usf_sophiag_step_f32:    p *= decay (= 1 - lr * weight_decay);  m = m * beta1 + g * one_minus_beta1 (g negated with
+ *                            maximize);  ratio = min(|m| / (rho_bs * h + 1e-15), 1) (rho_bs = rho * bs);
+ *                            p += neg_lr * sign(m) * ratio
+ *   usf_sophiag_hessian_f32: h = h * beta2 + one_minus_beta2 * g * g
+ */
+typedef struct usf_mt_chunk {
+  float* p; const float* g; float* m; float* h;
+  int32_t n; int32_t reserved;
+} usf_mt_chunk;
+int usf_sophiag_step_f32(const usf_mt_chunk* chunks, int64_t n_chunks, float decay, float beta1, float one_minus_beta1,
+                         float rho_bs, float neg_lr, int32_t maximize, usf_stream_t stream);
+int usf_sophiag_hessian_f32(const usf_mt_chunk* chunks, int64_t n_chunks, float beta2, float one_minus_beta2,
+                            usf_stream_t stream);
+
+/* (Leaky)ReLU backward from the saved layer OUTPUT h: d[m,j] *= (h[m,j] > 0 ? 1 : slope), slope >= 0
+ * (ATen leaky_relu_backward on the pre-activation; sign(h) == sign(pre-activation)). networks.py:745-749 */
+int usf_act_grad_f32(float* d, int64_t ldd, const float* h, int64_t ldh, int64_t M, int64_t H, int32_t act, float slope,
+                     usf_stream_t stream);
+
+/* Backward of usf_base_logprob_f32: g[m,d] = g_lp[m] * d/dz base_d(z[m,d]) for d < D, 0 for D <= d < ldg
+ * (flows.py:245 through torch Laplace.log_prob / Normal.log_prob).  For the LPNORM* ids g_lp is the gradient at the
+ * radius r[m] = ||z[m,:] - loc||_p (RadialDistribution.log_prob, distributions.py:501-505) and `scale` carries that
+ * radius vector [M] (the forward kernel's output). */
+int usf_base_logprob_grad_f32(const float* z, int64_t ldz, const float* g_lp, int64_t M, int64_t D, int32_t base,
+                              const float* loc, const float* scale, float* g, int64_t ldg, usf_stream_t stream);
+
+/*
+ * The backward of usf_affine_prep_f32 (usflows_hip.h), same operands:
+ * usf_affine_prep_bwd_f32: from the forward pass's Minv and b and (dM, dMinv, db, dc, dladj) -- zeros where an output was
+ * not used -- the gradients of the
+ * parameters: dL_raw (strictly lower triangle, zeros elsewhere: the reference's gradient mask, transforms.py:1262-1268),
+ * dU_raw (upper triangle), dbias [n, C], dvk [n, nvs, C].  What autograd derives from the reference's matrix() /
+ * inverse_matrix() / bias() / log_abs_det_jacobian() chains, in two launches instead of some hundreds.
+ */
+int usf_affine_prep_bwd_f32(const float* save, const float* bias, const float* vk, const float* w0, const float* Minv,
+                            const float* b, const float* dM, const float* dMinv, const float* db, const float* dc,
+                            const float* dladj, int64_t n, int32_t C, int32_t nvs, float* dL_raw, float* dU_raw, float* dbias,
+                            float* dvk, usf_stream_t stream);
+
+/* Trainable Laplace / Normal base (the reference's distributions.Laplace / Normal modules, distributions.py:199-238, as a flow's
+ * base distribution under Flow.fit, flows.py:196-203) -- ABI 33:
+ *   d_loc_scale[d]     = sum_m g_lp[m] * d/dloc_d   base_d(z[m,d]; loc_d, scale_d)
+ *   d_loc_scale[D + d] = sum_m g_lp[m] * d/dscale_d base_d(...)          (scale = the CONSTRAINED scale the density uses;
+ * the caller applies softplus' for the modules' scale_unconstrained).  Laplace: sign(t)/b, |t|/b^2 - 1/b; Normal: t/s^2,
+ * t^2/s^3 - 1/s (t = z - loc).  Row ranges of 256 summed in a fixed order (bit-reproducible).  workspace: at least
+ * (ceil(M/256) + ceil(M/65536) + 4) * 2 D floats. */
+int usf_base_param_grad_f32(const float* z, int64_t ldz, const float* g_lp, int64_t M, int64_t D, int32_t base, const float* loc,
+                            const float* scale, float* d_loc_scale, float* workspace, int64_t workspace_floats, usf_stream_t stream);
+
+/* Measurement aid (bench.py: roofline.sustained_peak): ONE launch of a register-only loop of the planes GEMM's matrix-core
+ * instruction mix (v_mfma_f32_16x16x32_bf16, 10 x 2 accumulator tiles, six products per fp32-equivalent product; 512 threads,
+ * two waves per SIMD; no LDS, no memory traffic in the loop) -- `iters` slabs of 120 MFMAs per wave on `blocks` blocks
+ * (0: two per CU).  src1024: 1024 finite floats (device); sink: one float (device, never written); *flops_out (host, may be
+ * NULL): the bf16 MFMA flops of the launch (fp32-equivalent: / 6).  The caller times the launch with events on `stream`. */
+int usf_mfma_probe(const float* src1024, float* sink, int64_t iters, int64_t blocks, double* flops_out, usf_stream_t stream);
+/* Measurement aid (bench.py: roofline.clock_mhz): while dev_buf2 (device memory, two 64-bit counters, zeroed by the caller) is
+ * set, every block of usf_gemm_planes_bf16x3's kernel and of usf_mfma_probe adds its lifetime to it -- [0] in shader-clock cycles
+ * (s_memtime), [1] in ticks of the constant 100 MHz counter (s_memrealtime): 100 MHz x [0] / [1] is the clock the matrix cores ran
+ * at under that kernel (the nominal peaks assume 2400 MHz).  NULL: off (the default; the kernels then read no counter).
+ * One process-wide setting (not per device, not synchronised with launches in flight): set it, launch, synchronise, clear it. */
+int usf_set_clock_buffer(unsigned long long* dev_buf2);
+
+/* Tuning knobs of the kernels' host code (A/B switches, cross-overs): named integers, preset on first use from the environment
+ * variable USFLOWS_AMD_TUNE ("name=value,..."), changed at run time here.  usf_get_tuning(name, dflt): the value in force. */
+int usf_set_tuning(const char* name, int64_t value);
+int64_t usf_get_tuning(const char* name, int64_t dflt);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* USFLOWS_HIP_INTERNAL_H */

@@ -5,7 +5,7 @@ would receive -- with torch-CPU arithmetic, by mapping raw pointers back onto th
 tensors.  This lets the `-m "not gpu"` suite check the engine's layout permutation, mask-aware
 weight slicing, fusion and pointer arithmetic against the golden vectors without a GPU.
 It implements the *documented semantics* of ``usf_linear_f32`` / ``usf_coupling_additive_f32``
-(include/usflows_hip.h), not the kernels."""
+(the public header include/usflows_hip.h), not the kernels."""
 import ctypes as C
 
 import torch
@@ -600,7 +600,7 @@ def _emu_gated_norm_rows(skip, *, M, C_cols, c_pad=None, ld_skip=None, vg=None, 
 
 def _emu_gated_norm_rows_bwd(skip, dy, d_skip, *, M, C_cols, c_pad, ld_skip, ld_dy, ld_d_skip, vg=None, ld_vg=0, gate_off=0, d_vg=None,
                              ld_d_vg=0, gamma=None, eps=1e-5, dy_xh=None, ld_dy_xh=0, dtype=torch.float64):
-    """usf_gated_norm_rows_bwd_f32 (include/usflows_hip.h): the formulas of the header, not autograd"""
+    """usf_gated_norm_rows_bwd_f32 (include/usflows_hip_internal.h): the formulas of the header, not autograd"""
     Cn, Cp = C_cols, c_pad
     r = _view(skip, 0, M, Cn, ld_skip).to(dtype)
     val = sg = None

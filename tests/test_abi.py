@@ -1,19 +1,29 @@
-"""The C-ABI library loads on a CPU-only box and exports every symbol include/usflows_hip.h declares
-(no compute calls here: there is no GPU)."""
+"""The C-ABI library loads on a CPU-only box and exports every symbol include/usflows_hip.h (public) and
+include/usflows_hip_internal.h declare (no compute calls here: there is no GPU)."""
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "usflows_hip.h")
+INTERNAL_HEADER = os.path.join(ROOT, "include", "usflows_hip_internal.h")
 
 
-def _declared_functions():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(usf_[a-z0-9_]+)\s*\(", src)))
+def _declared_functions(*headers):
+    """the functions the given headers declare (default: both)"""
+    names = set()
+    for h in headers or (HEADER, INTERNAL_HEADER):
+        src = re.sub(r"/\*.*?\*/", "", open(h).read(), flags=re.S)
+        names |= set(re.findall(r"\b(usf_[a-z0-9_]+)\s*\(", src))
+    return sorted(names)
+
+
+def _define(header, name):
+    return int(re.search(rf"^#define {name} (\d+)\b", open(header).read(), flags=re.M).group(1))
 
 
 def test_header_declares_expected_entry_points():
@@ -23,16 +33,69 @@ def test_header_declares_expected_entry_points():
         assert must in names
 
 
-def test_library_exports_every_declared_symbol():
+def test_library_exports_every_symbol_either_header_declares():
+    """every function the public or the internal header declares is exported, and the binding's SYMBOLS are exactly these"""
     from usflows_amd import _ext
     if not _ext.lib_exists():
         import __graft_entry__
         __graft_entry__.build()
     lib = ctypes.CDLL(_ext.LIB_PATH)
     for name in _declared_functions():
-        assert hasattr(lib, name), f"{name} declared in the header but not exported"
+        assert hasattr(lib, name), f"{name} declared in a header but not exported"
     # and the python binding knows every one of them
     assert set(_declared_functions()) == set(_ext.SYMBOLS)
+
+
+def test_public_and_internal_headers_split_the_exports():
+    """include/usflows_hip.h is the stable boundary, include/usflows_hip_internal.h the rest: every export is declared in
+    exactly one of them, the binding's PUBLIC_SYMBOLS are the public header's, and the public header does not even name an
+    internal entry point"""
+    from usflows_amd import _ext
+    public, internal = set(_declared_functions(HEADER)), set(_declared_functions(INTERNAL_HEADER))
+    assert public | internal == set(_ext.SYMBOLS)
+    assert not public & internal
+    assert public == set(_ext.PUBLIC_SYMBOLS)
+    assert internal == set(_ext.INTERNAL_SYMBOLS)
+    text = open(HEADER).read()
+    assert not [n for n in sorted(internal) if re.search(rf"\b{n}\b", text)]
+    assert '#include "usflows_hip.h"' in open(INTERNAL_HEADER).read()
+    # INTEGRATION.md section B tabulates the public entry points only
+    md = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    rows = [ln for ln in md[md.index("## B."):].split("\n") if ln.startswith("| `")]
+    tabulated = {n for ln in rows for n in re.findall(r"`(usf_[a-z0-9_]+)", ln.split(" | ")[0])} & set(_ext.SYMBOLS)
+    assert rows and tabulated <= public
+
+
+def _c_compiler():
+    for cc in ("gcc", "cc", "clang", "/opt/rocm/llvm/bin/clang"):
+        if shutil.which(cc):
+            return cc
+    pytest.fail("no C compiler on PATH (the library's build needs one)")
+
+
+@pytest.mark.parametrize("header", [HEADER, INTERNAL_HEADER], ids=["public", "internal"])
+@pytest.mark.parametrize("lang", ["c", "c++"])
+def test_header_compiles_on_its_own(header, lang):
+    cc = _c_compiler()
+    std = ["-std=c99"] if lang == "c" else []
+    r = subprocess.run([cc, "-fsyntax-only", "-Wall", "-Werror", *std, "-x", lang, header], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
+def test_both_versions_are_checked_on_load(monkeypatch):
+    """USF_ABI_VERSION (public header) and USF_INTERNAL_VERSION (internal header): the headers, the binding and the library
+    agree, and load() refuses a library whose either number differs from the binding's"""
+    from usflows_amd import _ext
+    lib = _ext.load()
+    assert lib.usf_abi_version() == _ext.USF_ABI_VERSION == _define(HEADER, "USF_ABI_VERSION") == 36
+    assert lib.usf_internal_version() == _ext.USF_INTERNAL_VERSION == _define(INTERNAL_HEADER, "USF_INTERNAL_VERSION")
+    for name in ("USF_ABI_VERSION", "USF_INTERNAL_VERSION"):
+        with monkeypatch.context() as m:
+            m.setattr(_ext, "_lib", None)
+            m.setattr(_ext, name, getattr(_ext, name) + 1)
+            with pytest.raises(RuntimeError, match="ABI mismatch"):
+                _ext.load()
+    assert _ext.load() is lib
 
 
 def test_binding_struct_layout_matches_c():

@@ -1,4 +1,5 @@
-"""ctypes binding of ``libusflows_hip.so`` (C ABI in ``include/usflows_hip.h``).
+"""ctypes binding of ``libusflows_hip.so`` (C ABI in ``include/usflows_hip.h``, the stable public part, and
+``include/usflows_hip_internal.h``, the training path and the measurement aids).
 
 The library is built in-tree by ``usflows_amd/csrc/Makefile`` (``__graft_entry__.build()``)
 for gfx950.  There is NO fallback: if the library is missing or a call fails, a
@@ -20,7 +21,8 @@ from .config import config  # noqa: E402
 
 LIB_PATH = config.lib_path     # (USFLOWS_AMD_LIB: A/B builds)
 
-USF_ABI_VERSION = 36
+USF_ABI_VERSION = 36          # include/usflows_hip.h
+USF_INTERNAL_VERSION = 1      # include/usflows_hip_internal.h
 USF_MAX_HIDDEN = 4
 
 ACT_NONE, ACT_LEAKY_RELU, ACT_GATE = 0, 1, 2
@@ -183,22 +185,17 @@ class GradJob(C.Structure):
     ]
 
 
-# every symbol include/usflows_hip.h declares: (restype, argtypes)
-SYMBOLS = {
+# every symbol include/usflows_hip.h declares (the stable public ABI): (restype, argtypes)
+PUBLIC_SYMBOLS = {
     "usf_abi_version": (C.c_int, []),
-    "usf_set_tuning": (C.c_int, [C.c_char_p, C.c_int64]),
-    "usf_get_tuning": (C.c_int64, [C.c_char_p, C.c_int64]),
     "usf_sizeof_desc": (C.c_int, [C.c_int32]),
     "usf_last_error": (C.c_char_p, []),
     "usf_build_info": (C.c_char_p, []),
     "usf_linear_f32": (C.c_int, [C.POINTER(LinearDesc), C.c_void_p]),
-    "usf_linear_variant": (C.c_int, [C.POINTER(LinearDesc)]),
     "usf_pack_planes_f32": (C.c_int, [C.POINTER(PackPlanesDesc), C.c_void_p]),
     "usf_gemm_planes_bf16x3": (C.c_int, [C.POINTER(GemmPlanesDesc), C.c_void_p]),
-    "usf_gemm_planes_variant": (C.c_int, [C.POINTER(GemmPlanesDesc)]),
     "usf_coupling_planes": (C.c_int, [C.POINTER(CouplingPlanesDesc), C.c_void_p]),
     "usf_coupling_additive_f32": (C.c_int, [C.POINTER(CouplingDesc), C.c_void_p]),
-    "usf_coupling_variant": (C.c_int, [C.POINTER(CouplingDesc)]),
     "usf_coupling_max_width": (C.c_int, []),
     "usf_coupling_padded_width": (C.c_int, [C.c_int]),
     "usf_base_logprob_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _fp, _fp, C.c_float,
@@ -210,9 +207,6 @@ SYMBOLS = {
                                         C.c_uint64, C.c_int64, C.c_void_p]),
     "usf_radial_logprob_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int32, C.c_int32, _fp, _fp, _fp,
                                          C.c_double, C.c_float, _fp, _fp, _fp, _fp, C.c_void_p]),
-    "usf_radial_logprob_grad_workspace": (C.c_int64, [C.c_int64, C.c_int64]),
-    "usf_radial_logprob_grad_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int32, C.c_int32,
-                                              _fp, _fp, _fp, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_void_p]),
     "usf_variates_from_bits_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, C.c_void_p]),
     "usf_scale_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_int32, C.c_void_p]),
     "usf_affine_coupling_apply_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, C.c_int64, C.c_int64,
@@ -222,7 +216,6 @@ SYMBOLS = {
                                              C.c_float, C.c_void_p]),
     "usf_gated_residual_f32": (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int64, C.c_void_p]),
     "usf_gated_norm_rows_f32": (C.c_int, [C.POINTER(GatedNormDesc), C.c_void_p]),
-    "usf_gated_norm_rows_bwd_f32": (C.c_int, [C.POINTER(GatedNormBwdDesc), C.c_void_p]),
     "usf_pointwise_conv_supported": (C.c_int, [C.c_int64, C.c_int64, C.c_int32]),
     "usf_pointwise_conv_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, _fp, C.c_int32, C.c_float,
                                          C.c_int32, C.c_float, _fp, _fp, _fp, C.c_float, C.c_void_p]),
@@ -232,10 +225,41 @@ SYMBOLS = {
                                       C.c_int32, C.c_float, C.c_int32, C.c_float, _fp, C.c_int64, C.c_void_p]),
     "usf_conv2d_same_ctx_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, _fp, _fp,
                                           C.c_int32, C.c_float, C.c_int32, C.c_float, _fp, C.c_int64, _fp, C.c_void_p]),
-    "usf_conv_ctx_wgrad_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_void_p]),
     "usf_conv2d_same_res_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, _fp, _fp,
                                           C.c_int32, C.c_float, _fp, _fp, C.c_float, C.c_void_p]),
     "usf_masked_residual_f32": (C.c_int, [_fp, _fp, _fp, C.c_float, _fp, C.c_int64, C.c_int64, C.c_void_p]),
+    "usf_gated_tail_supported": (C.c_int, [C.c_int64]),
+    "usf_gated_tail_f32": (C.c_int, [_fp, _fp, _fp] + [C.c_int64] * 3 + [_fp, _fp, C.c_int32, C.c_float, C.c_int32, C.c_float, _fp, _fp,
+                                     C.c_float, C.c_void_p]),
+    "usf_conv2d_weight_planes_f32": (C.c_int, [_fp, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
+    "usf_gather_cols_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_void_p]),
+    "usf_run_ops": (C.c_int, [C.POINTER(Op), C.c_int32, C.c_void_p]),
+    "usf_lu_prepare_f64": (C.c_int, [C.POINTER(LuPrepDesc), C.c_void_p]),
+    "usf_gemm_f64": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int64, C.c_int64, C.c_int32,
+                               _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                               C.c_double, C.c_double, C.c_int32, C.c_void_p]),
+    "usf_householder_f64": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, _fp, C.c_void_p]),
+    "usf_pack_weight_f32": (C.c_int, [_fp, C.c_int32, C.c_int64, C.c_int32, _fp, C.c_int64, _fp, C.c_int64,
+                                      _fp, C.c_int64, _fp, C.c_int64, C.c_int64, C.c_void_p]),
+    "usf_pack_weights_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    "usf_pack_weights_t_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    "usf_affine_prep_f32": (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp,
+                                      C.c_void_p]),
+    "usf_matvec_f64": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, C.c_int64, _fp, C.c_double, _fp, _fp, C.c_void_p]),
+}
+# every symbol include/usflows_hip_internal.h declares (the engine's own plumbing, no stability promise)
+INTERNAL_SYMBOLS = {
+    "usf_internal_version": (C.c_int, []),
+    "usf_set_tuning": (C.c_int, [C.c_char_p, C.c_int64]),
+    "usf_get_tuning": (C.c_int64, [C.c_char_p, C.c_int64]),
+    "usf_linear_variant": (C.c_int, [C.POINTER(LinearDesc)]),
+    "usf_gemm_planes_variant": (C.c_int, [C.POINTER(GemmPlanesDesc)]),
+    "usf_coupling_variant": (C.c_int, [C.POINTER(CouplingDesc)]),
+    "usf_radial_logprob_grad_workspace": (C.c_int64, [C.c_int64, C.c_int64]),
+    "usf_radial_logprob_grad_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int32, C.c_int32,
+                                              _fp, _fp, _fp, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_void_p]),
+    "usf_gated_norm_rows_bwd_f32": (C.c_int, [C.POINTER(GatedNormBwdDesc), C.c_void_p]),
+    "usf_conv_ctx_wgrad_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_void_p]),
     "usf_conv2d_same_gate_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [C.c_void_p, _fp, C.c_float, _fp, _fp, C.c_void_p]),
     "usf_conv_wgrad_workspace": (C.c_int64, [C.c_int64] * 6),
     "usf_conv_wgrad_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [_fp, _fp, C.c_int32, C.c_float, _fp, _fp, _fp, C.c_int64,
@@ -251,23 +275,10 @@ SYMBOLS = {
                                                  _fp, _fp, C.c_int64, C.c_void_p]),
     "usf_gated_residual_bwd_f32": (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int64, C.c_void_p]),
     "usf_conv2d_weight_planes_batch_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "usf_gated_tail_supported": (C.c_int, [C.c_int64]),
     "usf_gated_tail_workspace": (C.c_int64, [C.c_int64] * 3),
-    "usf_gated_tail_f32": (C.c_int, [_fp, _fp, _fp] + [C.c_int64] * 3 + [_fp, _fp, C.c_int32, C.c_float, C.c_int32, C.c_float, _fp, _fp,
-                                     C.c_float, C.c_void_p]),
     "usf_gated_tail_bwd_f32": (C.c_int, [_fp] * 6 + [C.c_int64] * 3 + [_fp, _fp, C.c_int32, C.c_float, C.c_int32, C.c_float, _fp, _fp,
                                          C.c_float, _fp, _fp, C.c_int64, C.c_void_p, C.c_void_p]),
-    "usf_conv2d_weight_planes_f32": (C.c_int, [_fp, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
-    "usf_gather_cols_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_void_p]),
-    "usf_run_ops": (C.c_int, [C.POINTER(Op), C.c_int32, C.c_void_p]),
-    "usf_lu_prepare_f64": (C.c_int, [C.POINTER(LuPrepDesc), C.c_void_p]),
-    "usf_gemm_f64": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int64, C.c_int64, C.c_int32,
-                               _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
-                               C.c_double, C.c_double, C.c_int32, C.c_void_p]),
-    "usf_householder_f64": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, _fp, C.c_void_p]),
     "usf_lu_grad_finish_f64": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_int64, _fp, _fp, C.c_void_p]),
-    "usf_pack_weight_f32": (C.c_int, [_fp, C.c_int32, C.c_int64, C.c_int32, _fp, C.c_int64, _fp, C.c_int64,
-                                      _fp, C.c_int64, _fp, C.c_int64, C.c_int64, C.c_void_p]),
     "usf_wgrad_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_int64,
                                 C.c_float, C.c_float, C.c_int32, _fp, C.c_int64, C.c_void_p]),
     "usf_wgrad_workspace_floats": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
@@ -299,15 +310,11 @@ SYMBOLS = {
                                    C.c_void_p]),
     "usf_base_logprob_grad_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, C.c_int64, C.c_int32, _fp, _fp, _fp,
                                             C.c_int64, C.c_void_p]),
-    "usf_pack_weights_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
-    "usf_pack_weights_t_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
     "usf_grad_jobs_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_void_p]),
-    "usf_affine_prep_f32": (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp,
-                                      C.c_void_p]),
     "usf_affine_prep_bwd_f32": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_int32,
                                           C.c_int32, _fp, _fp, _fp, _fp, C.c_void_p]),
-    "usf_matvec_f64": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, C.c_int64, _fp, C.c_double, _fp, _fp, C.c_void_p]),
 }
+SYMBOLS = {**PUBLIC_SYMBOLS, **INTERNAL_SYMBOLS}
 
 _lib: Optional[C.CDLL] = None
 
@@ -333,6 +340,9 @@ def load() -> C.CDLL:
         fn.argtypes = args
     if lib.usf_abi_version() != USF_ABI_VERSION:
         raise RuntimeError(f"usflows_amd: ABI mismatch: library {lib.usf_abi_version()} != binding {USF_ABI_VERSION}")
+    if lib.usf_internal_version() != USF_INTERNAL_VERSION:
+        raise RuntimeError(f"usflows_amd: internal ABI mismatch: library {lib.usf_internal_version()} != binding "
+                           f"{USF_INTERNAL_VERSION}")
     for kind, st in ((OP_LINEAR, LinearDesc), (OP_COUPLING, CouplingDesc), (0, Op), (3, LuPrepDesc), (4, PackJob),
                      (OP_PACK_PLANES, PackPlanesDesc), (OP_GEMM_PLANES, GemmPlanesDesc),
                      (OP_COUPLING_PLANES, CouplingPlanesDesc), (8, MtChunk), (OP_GATED_NORM, GatedNormDesc), (OP_CALL, CallDesc),
@@ -917,7 +927,7 @@ def gated_norm_rows(skip, *, M, C_cols, c_pad=None, ld_skip=None, vg=None, ld_vg
 
 def gated_norm_rows_bwd(skip, dy, d_skip, *, M, C_cols, c_pad, ld_skip, ld_dy, ld_d_skip, vg=None, ld_vg=0, gate_off=0, d_vg=None,
                         ld_d_vg=0, gamma=None, eps=1e-5, dy_xh=None, ld_dy_xh=0):
-    """usf_gated_norm_rows_bwd_f32 on raw [M, ld] fp32 buffers (see include/usflows_hip.h)"""
+    """usf_gated_norm_rows_bwd_f32 on raw [M, ld] fp32 buffers (see include/usflows_hip_internal.h)"""
     d = GatedNormBwdDesc(skip=skip.data_ptr(), ld_skip=ld_skip, vg=ptr(vg), ld_vg=ld_vg, gate_off=gate_off, gamma=ptr(gamma),
                          dy=dy.data_ptr(), ld_dy=ld_dy, d_skip=d_skip.data_ptr(), ld_d_skip=ld_d_skip, d_vg=ptr(d_vg), ld_d_vg=ld_d_vg,
                          dy_xh=ptr(dy_xh), ld_dy_xh=ld_dy_xh, M=M, C=C_cols, c_pad=c_pad, eps=eps)
@@ -1582,7 +1592,7 @@ def wgrad(Y, A, G, *, M, N, K, ldy, lda, ldg, y_off=0, a_off=0, g_off=0, alpha=1
 
 
 def row_planes(M: int, cols: int, device) -> torch.Tensor:
-    """[3, ceil32(M), ceil32(cols)] bf16: the row-major operand planes of usf_wgrad_planes_f32 (include/usflows_hip.h)"""
+    """[3, ceil32(M), ceil32(cols)] bf16: the row-major operand planes of usf_wgrad_planes_f32 (include/usflows_hip_internal.h)"""
     return torch.zeros(3, -(-M // 32) * 32, -(-cols // 32) * 32, dtype=torch.bfloat16, device=device)
 
 

@@ -1,4 +1,4 @@
-// extern "C" surface of libusflows_hip.so (declared in include/usflows_hip.h).
+// extern "C" surface of libusflows_hip.so (declared in include/usflows_hip.h and include/usflows_hip_internal.h).
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
@@ -199,6 +199,7 @@ int radial_grad(const float* z, int64_t ldz, const float* r, const float* g_lp, 
 extern "C" {
 
 int usf_abi_version(void) { return USF_ABI_VERSION; }
+int usf_internal_version(void) { return USF_INTERNAL_VERSION; }
 int usf_set_tuning(const char* name, int64_t value) {
   if (!name || !*name || strlen(name) >= sizeof(usf::g_tune[0].name)) { usf::set_error("usf_set_tuning: bad name"); return -1; }
   usf::tune_init();
