@@ -650,7 +650,7 @@ int usf_affine_prep_f32(const float* L_raw, const float* U_raw, const float* bia
 int usf_abi_version(void);
 int usf_sizeof_desc(int32_t kind);      /* sizeof(usf_linear_desc|usf_coupling_desc|usf_op|usf_lu_prep_desc|usf_pack_job) for kind 1|2|0|3|4;
                                            usf_pack_planes_desc|usf_gemm_planes_desc|usf_coupling_planes_desc|usf_gated_norm_desc for 5|6|7|9,
-                                           usf_call_desc for 10 (8, 11, 12: structs of usflows_hip_internal.h):
+                                           usf_call_desc for 10 (8, 11 to 16: structs of usflows_hip_internal.h):
                                            binding self-check */
 const char* usf_last_error(void);
 const char* usf_build_info(void);       /* "gfx950 ..." */

@@ -16,7 +16,7 @@
 extern "C" {
 #endif
 
-#define USF_INTERNAL_VERSION 1
+#define USF_INTERNAL_VERSION 2
 
 /* USF_INTERNAL_VERSION of the header the library was built from (host only, launches nothing). */
 int usf_internal_version(void);
@@ -67,7 +67,8 @@ int usf_internal_version(void);
  *   Replaces autograd's backward of MaskedCoupling + its conditioner (transforms.py:277-306, networks.py:739-751) under
  *   Flow.fit (flows.py:196-203) at batches of thousands of rows.
  *
- * usf_sizeof_desc(kind) also reports sizeof(usf_mt_chunk|usf_grad_job|usf_psum_job) for kind 8|11|12.
+ * usf_sizeof_desc(kind) also reports sizeof(usf_mt_chunk|usf_grad_job|usf_psum_job) for kind 8|11|12 and
+ * sizeof(usf_gated_norm_bwd_desc|usf_wgrad_job|usf_wreduce_job|usf_wplanes_job) for kind 13|14|15|16.
  */
 
 /*

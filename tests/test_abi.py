@@ -104,6 +104,12 @@ def test_binding_struct_layout_matches_c():
     assert lib.usf_abi_version() == _ext.USF_ABI_VERSION
     assert lib.usf_sizeof_desc(_ext.OP_LINEAR) == ctypes.sizeof(_ext.LinearDesc)
     assert lib.usf_sizeof_desc(_ext.OP_COUPLING) == ctypes.sizeof(_ext.CouplingDesc)
+    # the kind table load() walks covers EVERY struct the binding declares: one added later cannot stay unchecked
+    from usflows_amd import _abi
+    structs = {v for v in vars(_abi).values() if isinstance(v, type) and issubclass(v, ctypes.Structure) and v is not ctypes.Structure}
+    assert len(structs) >= 17 and set(_abi.SIZEOF_KINDS.values()) == structs and len(_abi.SIZEOF_KINDS) == len(structs)
+    for kind, st in _abi.SIZEOF_KINDS.items():
+        assert lib.usf_sizeof_desc(kind) == ctypes.sizeof(st), st.__name__
     assert lib.usf_coupling_max_width() == 256
     assert [lib.usf_coupling_padded_width(h) for h in (1, 64, 65, 128, 200, 256, 257)] == [64, 64, 128, 128, 256, 256, -1]
 
@@ -146,31 +152,13 @@ def test_tiny_coupling_rule_of_the_engine_is_the_librarys():
     import itertools
     from usflows_amd import _ext
     from usflows_amd.engine import FlowEngine
-    lib = _ext.load()
-
-    def variant(B, n_pass, hidden, n_trans):
-        d = _ext.CouplingDesc()
-        d.z = d.out = 0x10000
-        d.ldz = d.ldo = 512
-        d.M, d.off_pass, d.n_pass, d.off_trans, d.n_trans = B, 0, n_pass, 256, n_trans
-        d.n_hidden = len(hidden)
-        k = n_pass
-        r32 = lambda v: (v + 31) // 32 * 32
-        for i, h in enumerate(hidden):
-            d.hidden[i] = h
-        d.W_in, d.ldw_in, d.b_in = 0x20000, r32(n_pass), 0x30000
-        for i in range(1, len(hidden)):
-            d.W_hid[i - 1], d.ldw_hid[i - 1], d.b_hid[i - 1] = 0x40000 + 0x10000 * i, 64, 0x30000
-        d.W_out, d.ldw_out, d.b_out = 0x80000, 64, 0x30000
-        d.sign, d.slope, d.act = 1.0, 0.01, _ext.ACT_LEAKY_RELU
-        return lib.usf_coupling_variant(d)
-
+    _ext.load()
     n_checked = n_tiny = 0
     for B, n_pass, n_trans, hidden in itertools.product([1, 32, 256, 257, 4096], [4, 8, 52, 64, 68], [4, 5, 48, 64, 100],
                                                         [[32], [32, 32], [64, 64], [64, 64, 64], [7, 5], [65], [48, 32, 40]]):
         cp = dict(hidden=hidden, pass_n=n_pass, tr_n=n_trans)
         py = FlowEngine.tiny_coupling(None, cp, B)
-        both = variant(B, n_pass, hidden, n_trans) == 3 and variant(B, n_trans, hidden[::-1], n_pass) == 3
+        both = _coupling_variant(B, n_pass, hidden, n_trans) == 3 and _coupling_variant(B, n_trans, hidden[::-1], n_pass) == 3
         assert py == both, (B, n_pass, n_trans, hidden, py, both)
         n_checked += 1
         n_tiny += int(py)
@@ -194,6 +182,7 @@ def _coupling_variant(B, n_pass, hidden, n_trans):
     d.W_out, d.ldw_out, d.b_out = 0x80000, 64, 0x30000
     d.sign, d.slope, d.act = 1.0, 0.01, _ext.ACT_LEAKY_RELU
     return _ext.load().usf_coupling_variant(d)
+
 
 def test_tiny_coupling_decision_of_the_engine_follows_the_library_knob():
     """usf_set_tuning("coupling_tiny", 0) switches the tiny-layer kernel off in the library: the engine must not emit the fused

@@ -18,303 +18,15 @@ import torch  # noqa: F401  -- must be imported first: the .so binds to torch's 
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 from .config import config  # noqa: E402
+from ._abi import (  # noqa: E402,F401  -- the declarations, re-exported: callers say _ext.LinearDesc, _ext.ACT_GATE, ...
+    USF_ABI_VERSION, USF_INTERNAL_VERSION, USF_MAX_HIDDEN, ACT_NONE, ACT_LEAKY_RELU, ACT_GATE, BASE_LAPLACE, BASE_NORMAL,
+    BASE_LPNORM1, BASE_LPNORM2, BASE_LPNORMINF, BASE_ROWSUM, NORM_LOGNORMAL, NORM_GAMMA, NORM_RAW_PARAMS, RADIAL_MAX_K, OP_LINEAR,
+    OP_COUPLING, OP_PACK_PLANES, OP_GEMM_PLANES, OP_COUPLING_PLANES, OP_GATED_NORM, OP_CALL, PLANES_BF16X3, PLANES_F16X2, CALL_FNS,
+    _fp, LinearDesc, CouplingDesc, PackPlanesDesc, GemmPlanesDesc, CouplingPlanesDesc, MtChunk, GatedNormDesc, GatedNormBwdDesc,
+    CallDesc, _OpUnion, Op, LuPrepDesc, PackJob, PsumJob, WgradJob, WReduceJob, WPlanesJob, GradJob, SIZEOF_KINDS, PUBLIC_SYMBOLS,
+    INTERNAL_SYMBOLS, SYMBOLS)
 
 LIB_PATH = config.lib_path     # (USFLOWS_AMD_LIB: A/B builds)
-
-USF_ABI_VERSION = 36          # include/usflows_hip.h
-USF_INTERNAL_VERSION = 1      # include/usflows_hip_internal.h
-USF_MAX_HIDDEN = 4
-
-ACT_NONE, ACT_LEAKY_RELU, ACT_GATE = 0, 1, 2
-BASE_LAPLACE, BASE_NORMAL, BASE_LPNORM1, BASE_LPNORM2, BASE_LPNORMINF, BASE_ROWSUM = 0, 1, 2, 3, 4, 5
-NORM_LOGNORMAL, NORM_GAMMA, NORM_RAW_PARAMS = 0, 1, 0x100
-RADIAL_MAX_K = 64
-OP_LINEAR, OP_COUPLING, OP_PACK_PLANES, OP_GEMM_PLANES, OP_COUPLING_PLANES, OP_GATED_NORM, OP_CALL = 1, 2, 5, 6, 7, 9, 10
-
-_fp = C.c_void_p  # device pointers travel as integers
-
-
-class LinearDesc(C.Structure):
-    _fields_ = [
-        ("A", _fp), ("lda", C.c_int64),
-        ("W", _fp), ("ldw", C.c_int64),
-        ("bias", _fp), ("pre_div", _fp), ("pre_sub", _fp),
-        ("residual", _fp), ("ldr", C.c_int64),
-        ("addend", _fp), ("ldadd", C.c_int64),
-        ("post_mul", _fp),
-        ("C", _fp), ("ldc", C.c_int64),
-        ("M", C.c_int64), ("N", C.c_int64), ("K", C.c_int64),
-        ("res_sign", C.c_float), ("slope", C.c_float),
-        ("act", C.c_int32), ("reserved", C.c_int32),
-        ("W_split", _fp), ("ldw_split", C.c_int64), ("split_plane_stride", C.c_int64),
-        ("A_planes_out", _fp), ("ldp_out", C.c_int64), ("planes_out_stride", C.c_int64),
-    ]
-
-
-class CouplingDesc(C.Structure):
-    _fields_ = [
-        ("z", _fp), ("ldz", C.c_int64),
-        ("out", _fp), ("ldo", C.c_int64),
-        ("M", C.c_int64),
-        ("off_pass", C.c_int64), ("n_pass", C.c_int64),
-        ("off_trans", C.c_int64), ("n_trans", C.c_int64),
-        ("n_hidden", C.c_int32), ("hidden", C.c_int32 * USF_MAX_HIDDEN),
-        ("W_in", _fp), ("ldw_in", C.c_int64), ("b_in", _fp),
-        ("W_hid", _fp * USF_MAX_HIDDEN), ("b_hid", _fp * USF_MAX_HIDDEN), ("ldw_hid", C.c_int64 * USF_MAX_HIDDEN),
-        ("W_out", _fp), ("ldw_out", C.c_int64), ("b_out", _fp),
-        ("context", _fp), ("W_ctx", _fp), ("b_ctx", _fp),
-        ("post_sub", _fp),
-        ("sign", C.c_float), ("slope", C.c_float),
-        ("act", C.c_int32), ("reserved", C.c_int32),
-        ("split_in", _fp), ("split_in_ld", C.c_int64), ("split_in_plane", C.c_int64),
-        ("split_hid", _fp * USF_MAX_HIDDEN), ("split_hid_ld", C.c_int64), ("split_hid_plane", C.c_int64),
-        ("split_out", _fp), ("split_out_ld", C.c_int64), ("split_out_plane", C.c_int64),
-        ("hidden_out", _fp * USF_MAX_HIDDEN), ("ld_hidden_out", C.c_int64),
-        ("gate", _fp * USF_MAX_HIDDEN), ("ld_gate", C.c_int64),
-    ]
-
-
-class PackPlanesDesc(C.Structure):
-    _fields_ = [("src", _fp), ("ld", C.c_int64), ("M", C.c_int64), ("nkb", C.c_int64), ("idx", _fp),
-                ("pre_div", _fp), ("pre_sub", _fp), ("planes", _fp), ("format", C.c_int32), ("reserved", C.c_int32), ("range_flag", _fp),
-                ("src_cols", C.c_int64), ("row_weight", _fp), ("loc", _fp), ("scale", _fp), ("grad_base", C.c_int32),
-                ("reserved2", C.c_int32)]
-
-
-class GemmPlanesDesc(C.Structure):
-    _fields_ = [("A", _fp), ("a_nkb", C.c_int64), ("a_kb0", C.c_int64), ("nk", C.c_int64),
-                ("W_planes", _fp), ("ldw", C.c_int64), ("w_plane_stride", C.c_int64), ("w_rows", C.c_int64),
-                ("bias", _fp), ("post_mul", _fp), ("residual", _fp),
-                ("C_planes", _fp), ("c_nkb", C.c_int64), ("c_kb0", C.c_int64), ("c_kbn", C.c_int64),
-                ("C_f32", _fp), ("ldc", C.c_int64), ("N", C.c_int64), ("M", C.c_int64),
-                ("res_sign", C.c_float), ("slope", C.c_float), ("act", C.c_int32), ("format", C.c_int32), ("range_flag", _fp),
-                ("base_tab", _fp), ("base_tab_stride", C.c_int64), ("base_part", _fp), ("base", C.c_int32), ("reserved", C.c_int32)]
-
-
-class CouplingPlanesDesc(C.Structure):
-    _fields_ = [("z", _fp), ("z_nkb", C.c_int64), ("M", C.c_int64),
-                ("kb_p0", C.c_int64), ("nk_p", C.c_int64), ("kb_t0", C.c_int64), ("nk_t", C.c_int64),
-                ("n_hidden", C.c_int32), ("hidden_padded", C.c_int32),
-                ("W_in", _fp), ("ldw_in", C.c_int64), ("w_in_plane", C.c_int64), ("b_in", _fp),
-                ("W_hid", _fp * 2), ("b_hid", _fp * 2), ("ldw_hid", C.c_int64), ("w_hid_plane", C.c_int64),
-                ("W_out", _fp), ("ldw_out", C.c_int64), ("w_out_plane", C.c_int64), ("b_out", _fp),
-                ("sign", C.c_float), ("slope", C.c_float), ("act", C.c_int32), ("format", C.c_int32),
-                ("range_flag", _fp), ("hidden_out", _fp * 2), ("gate", _fp * 2)]
-
-
-class MtChunk(C.Structure):
-    """usf_mt_chunk: one block's share of one parameter tensor (SophiaG multi-tensor kernels)"""
-    _fields_ = [("p", _fp), ("g", _fp), ("m", _fp), ("h", _fp), ("n", C.c_int32), ("reserved", C.c_int32)]
-
-
-class GatedNormDesc(C.Structure):
-    """usf_gated_norm_desc: row pass of the vector ConvNet conditioner (gate, layer norm, activation)"""
-    _fields_ = [("skip", _fp), ("ld_skip", C.c_int64), ("vg", _fp), ("ld_vg", C.c_int64), ("gate_off", C.c_int64),
-                ("gamma", _fp), ("beta", _fp), ("out", _fp), ("ld_out", C.c_int64), ("out_act", _fp), ("ld_act", C.c_int64),
-                ("M", C.c_int64), ("C", C.c_int64), ("c_pad", C.c_int64), ("eps", C.c_float), ("slope", C.c_float),
-                ("act", C.c_int32), ("reserved", C.c_int32)]
-
-
-class GatedNormBwdDesc(C.Structure):
-    """usf_gated_norm_bwd_desc: the backward twin of the row pass"""
-    _fields_ = [("skip", _fp), ("ld_skip", C.c_int64), ("vg", _fp), ("ld_vg", C.c_int64), ("gate_off", C.c_int64),
-                ("gamma", _fp), ("dy", _fp), ("ld_dy", C.c_int64), ("d_skip", _fp), ("ld_d_skip", C.c_int64),
-                ("d_vg", _fp), ("ld_d_vg", C.c_int64), ("dy_xh", _fp), ("ld_dy_xh", C.c_int64),
-                ("M", C.c_int64), ("C", C.c_int64), ("c_pad", C.c_int64), ("eps", C.c_float), ("reserved", C.c_float)]
-
-
-class CallDesc(C.Structure):
-    """usf_call_desc: one entry-point call inside an op list, arguments as 64-bit words"""
-    _fields_ = [("fn", C.c_int32), ("n_args", C.c_int32), ("a", C.c_uint64 * 20)]
-
-
-class _OpUnion(C.Union):
-    _fields_ = [("linear", LinearDesc), ("coupling", CouplingDesc), ("pack_planes", PackPlanesDesc),
-                ("gemm_planes", GemmPlanesDesc), ("coupling_planes", CouplingPlanesDesc), ("gated_norm", GatedNormDesc),
-                ("call", CallDesc)]
-
-
-class Op(C.Structure):
-    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("u", _OpUnion)]
-
-
-class LuPrepDesc(C.Structure):
-    _fields_ = [
-        ("n", C.c_int64), ("D", C.c_int64),
-        ("L_raw", C.POINTER(C.c_void_p)), ("U_raw", C.POINTER(C.c_void_p)),
-        ("tri", _fp), ("tri_inv", _fp), ("work", _fp), ("M", _fp), ("Minv", _fp), ("ladj", _fp),
-    ]
-
-
-class PackJob(C.Structure):
-    _fields_ = [
-        ("src", _fp), ("out_idx", _fp), ("in_idx", _fp), ("W", _fp), ("planes", _fp),
-        ("ld_src", C.c_int64), ("n_out", C.c_int64), ("n_in", C.c_int64), ("ldw", C.c_int64),
-        ("ld_planes", C.c_int64), ("plane_stride", C.c_int64),
-        ("src_is_f32", C.c_int32), ("transpose", C.c_int32),
-    ]
-
-
-class PsumJob(C.Structure):
-    """usf_psum_job: one deferred sum of per-wave partial slots (usf_conv_wgrad_deferred_f32 / usf_partial_sum_jobs_f32)"""
-    _fields_ = [("part", _fp), ("out", _fp), ("out2", _fp),
-                ("nparts", C.c_int32), ("n", C.c_int32), ("mode", C.c_int32), ("cin", C.c_int32), ("cout", C.c_int32),
-                ("CIT", C.c_int32), ("T", C.c_int32), ("ntile", C.c_int32), ("first_block", C.c_int32), ("per", C.c_int32),
-                ("rows", C.c_int32), ("vec4", C.c_int32)]
-
-
-class WgradJob(C.Structure):
-    """usf_wgrad_job: one queued weight-gradient launch (usf_conv_wgrad_plan_f32 / usf_conv_wgrad_jobs_f32)"""
-    _fields_ = [("args", C.c_ubyte * 192), ("CIT", C.c_int32), ("COT", C.c_int32), ("T", C.c_int32), ("blocks", C.c_int32),
-                ("lds_bytes", C.c_int32), ("first_block", C.c_int32)]
-
-
-class WReduceJob(C.Structure):
-    """usf_wreduce_job: one queued reduction of usf_wgrad_blocked_plan_f32 (usf_wgrad_reduce_jobs_f32)"""
-    _fields_ = [("part", _fp), ("out", _fp), ("cs_part", _fp), ("cs_out", _fp), ("rows", C.c_int64), ("cols", C.c_int64),
-                ("ldo", C.c_int64), ("alpha", C.c_float), ("beta", C.c_float), ("cs_alpha", C.c_float), ("cs_beta", C.c_float),
-                ("first_block", C.c_int32), ("blocks", C.c_int32), ("sched", C.c_ubyte * 64)]
-
-
-class GradJob(C.Structure):
-    _fields_ = [
-        ("Y", _fp), ("A", _fp), ("G", _fp),
-        ("ldy", C.c_int64), ("lda", C.c_int64), ("ldg", C.c_int64),
-        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("first_block", C.c_int32),
-        ("alpha", C.c_float), ("beta", C.c_float),
-    ]
-
-
-# every symbol include/usflows_hip.h declares (the stable public ABI): (restype, argtypes)
-PUBLIC_SYMBOLS = {
-    "usf_abi_version": (C.c_int, []),
-    "usf_sizeof_desc": (C.c_int, [C.c_int32]),
-    "usf_last_error": (C.c_char_p, []),
-    "usf_build_info": (C.c_char_p, []),
-    "usf_linear_f32": (C.c_int, [C.POINTER(LinearDesc), C.c_void_p]),
-    "usf_pack_planes_f32": (C.c_int, [C.POINTER(PackPlanesDesc), C.c_void_p]),
-    "usf_gemm_planes_bf16x3": (C.c_int, [C.POINTER(GemmPlanesDesc), C.c_void_p]),
-    "usf_coupling_planes": (C.c_int, [C.POINTER(CouplingPlanesDesc), C.c_void_p]),
-    "usf_coupling_additive_f32": (C.c_int, [C.POINTER(CouplingDesc), C.c_void_p]),
-    "usf_coupling_max_width": (C.c_int, []),
-    "usf_coupling_padded_width": (C.c_int, [C.c_int]),
-    "usf_base_logprob_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _fp, _fp, C.c_float,
-                                       _fp, _fp, _fp, C.c_void_p]),
-    "usf_base_tables_f32": (C.c_int, [C.c_int32, _fp, _fp, C.c_int64, _fp, C.c_int64, C.c_void_p]),
-    "usf_base_sample_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _fp, _fp, C.c_uint64,
-                                      C.c_uint64, C.c_int64, C.c_void_p]),
-    "usf_radial_sample_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _fp, _fp, C.c_uint64,
-                                        C.c_uint64, C.c_int64, C.c_void_p]),
-    "usf_radial_logprob_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int32, C.c_int32, _fp, _fp, _fp,
-                                         C.c_double, C.c_float, _fp, _fp, _fp, _fp, C.c_void_p]),
-    "usf_variates_from_bits_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, C.c_void_p]),
-    "usf_scale_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_int32, C.c_void_p]),
-    "usf_affine_coupling_apply_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, C.c_int64, C.c_int64,
-                                                C.c_float, C.c_int32, _fp, C.c_void_p]),
-    "usf_channel_affine_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, C.c_int64, _fp, _fp, _fp, C.c_void_p]),
-    "usf_layernorm_channels_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, C.c_int64, _fp, _fp, C.c_float, C.c_int32,
-                                             C.c_float, C.c_void_p]),
-    "usf_gated_residual_f32": (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int64, C.c_void_p]),
-    "usf_gated_norm_rows_f32": (C.c_int, [C.POINTER(GatedNormDesc), C.c_void_p]),
-    "usf_pointwise_conv_supported": (C.c_int, [C.c_int64, C.c_int64, C.c_int32]),
-    "usf_pointwise_conv_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, _fp, C.c_int32, C.c_float,
-                                         C.c_int32, C.c_float, _fp, _fp, _fp, C.c_float, C.c_void_p]),
-    "usf_conv2d_weight_elems": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
-    "usf_conv2d_same_fits": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
-    "usf_conv2d_same_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, _fp, _fp,
-                                      C.c_int32, C.c_float, C.c_int32, C.c_float, _fp, C.c_int64, C.c_void_p]),
-    "usf_conv2d_same_ctx_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, _fp, _fp,
-                                          C.c_int32, C.c_float, C.c_int32, C.c_float, _fp, C.c_int64, _fp, C.c_void_p]),
-    "usf_conv2d_same_res_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, _fp, _fp,
-                                          C.c_int32, C.c_float, _fp, _fp, C.c_float, C.c_void_p]),
-    "usf_masked_residual_f32": (C.c_int, [_fp, _fp, _fp, C.c_float, _fp, C.c_int64, C.c_int64, C.c_void_p]),
-    "usf_gated_tail_supported": (C.c_int, [C.c_int64]),
-    "usf_gated_tail_f32": (C.c_int, [_fp, _fp, _fp] + [C.c_int64] * 3 + [_fp, _fp, C.c_int32, C.c_float, C.c_int32, C.c_float, _fp, _fp,
-                                     C.c_float, C.c_void_p]),
-    "usf_conv2d_weight_planes_f32": (C.c_int, [_fp, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
-    "usf_gather_cols_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_void_p]),
-    "usf_run_ops": (C.c_int, [C.POINTER(Op), C.c_int32, C.c_void_p]),
-    "usf_lu_prepare_f64": (C.c_int, [C.POINTER(LuPrepDesc), C.c_void_p]),
-    "usf_gemm_f64": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int64, C.c_int64, C.c_int32,
-                               _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
-                               C.c_double, C.c_double, C.c_int32, C.c_void_p]),
-    "usf_householder_f64": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, _fp, C.c_void_p]),
-    "usf_pack_weight_f32": (C.c_int, [_fp, C.c_int32, C.c_int64, C.c_int32, _fp, C.c_int64, _fp, C.c_int64,
-                                      _fp, C.c_int64, _fp, C.c_int64, C.c_int64, C.c_void_p]),
-    "usf_pack_weights_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
-    "usf_pack_weights_t_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
-    "usf_affine_prep_f32": (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp,
-                                      C.c_void_p]),
-    "usf_matvec_f64": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, C.c_int64, _fp, C.c_double, _fp, _fp, C.c_void_p]),
-}
-# every symbol include/usflows_hip_internal.h declares (the engine's own plumbing, no stability promise)
-INTERNAL_SYMBOLS = {
-    "usf_internal_version": (C.c_int, []),
-    "usf_set_tuning": (C.c_int, [C.c_char_p, C.c_int64]),
-    "usf_get_tuning": (C.c_int64, [C.c_char_p, C.c_int64]),
-    "usf_linear_variant": (C.c_int, [C.POINTER(LinearDesc)]),
-    "usf_gemm_planes_variant": (C.c_int, [C.POINTER(GemmPlanesDesc)]),
-    "usf_coupling_variant": (C.c_int, [C.POINTER(CouplingDesc)]),
-    "usf_radial_logprob_grad_workspace": (C.c_int64, [C.c_int64, C.c_int64]),
-    "usf_radial_logprob_grad_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int32, C.c_int32,
-                                              _fp, _fp, _fp, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_void_p]),
-    "usf_gated_norm_rows_bwd_f32": (C.c_int, [C.POINTER(GatedNormBwdDesc), C.c_void_p]),
-    "usf_conv_ctx_wgrad_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_void_p]),
-    "usf_conv2d_same_gate_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [C.c_void_p, _fp, C.c_float, _fp, _fp, C.c_void_p]),
-    "usf_conv_wgrad_workspace": (C.c_int64, [C.c_int64] * 6),
-    "usf_conv_wgrad_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [_fp, _fp, C.c_int32, C.c_float, _fp, _fp, _fp, C.c_int64,
-                                     C.c_void_p]),
-    "usf_conv_wgrad_deferred_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [_fp, _fp, C.c_int32, C.c_float, _fp, _fp, _fp, C.c_int64,
-                                              C.POINTER(PsumJob), C.c_void_p]),
-    "usf_conv_wgrad_plan_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [_fp, _fp, C.c_int32, C.c_float, _fp, _fp, _fp, C.c_int64,
-                                          C.c_void_p, C.c_void_p, C.c_void_p]),
-    "usf_conv_wgrad_jobs_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),      # (job: two entries)
-    "usf_partial_sum_jobs_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_void_p]),
-    "usf_layernorm_channels_bwd_workspace": (C.c_int64, [C.c_int64] * 3),
-    "usf_layernorm_channels_bwd_f32": (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_float, C.c_int32, C.c_float,
-                                                 _fp, _fp, C.c_int64, C.c_void_p]),
-    "usf_gated_residual_bwd_f32": (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int64, C.c_void_p]),
-    "usf_conv2d_weight_planes_batch_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "usf_gated_tail_workspace": (C.c_int64, [C.c_int64] * 3),
-    "usf_gated_tail_bwd_f32": (C.c_int, [_fp] * 6 + [C.c_int64] * 3 + [_fp, _fp, C.c_int32, C.c_float, C.c_int32, C.c_float, _fp, _fp,
-                                         C.c_float, _fp, _fp, C.c_int64, C.c_void_p, C.c_void_p]),
-    "usf_lu_grad_finish_f64": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_int64, _fp, _fp, C.c_void_p]),
-    "usf_wgrad_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_int64,
-                                C.c_float, C.c_float, C.c_int32, _fp, C.c_int64, C.c_void_p]),
-    "usf_wgrad_workspace_floats": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
-    "usf_wgrad_bias_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_int64,
-                                     C.c_float, C.c_float, C.c_int32, _fp, C.c_float, C.c_float, _fp, C.c_int64, _fp]),
-    "usf_wgrad_bias_ok": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
-    "usf_wgrad_planes_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
-                                       C.c_int64, C.c_int64, _fp, C.c_int64, C.c_float, C.c_float, _fp, C.c_float, C.c_float,
-                                       _fp, C.c_int64, _fp]),
-    "usf_wgrad_blocked_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp,
-                                        C.c_int64, C.c_float, C.c_float, _fp, C.c_float, C.c_float, _fp, C.c_int64, _fp]),
-    "usf_wgrad_blocked_plan_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp,
-                                             C.c_int64, C.c_float, C.c_float, _fp, C.c_float, C.c_float, _fp, C.c_int64, C.c_void_p, _fp]),
-    "usf_wgrad_reduce_jobs_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "usf_base_param_grad_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, C.c_int64, C.c_int32, _fp, _fp, _fp, _fp, C.c_int64, C.c_void_p]),
-    "usf_mfma_probe": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, C.POINTER(C.c_double), C.c_void_p]),
-    "usf_set_clock_buffer": (C.c_int, [_fp]),
-    "usf_wgrad_planes_colsum_ok": (C.c_int, [C.c_int64, C.c_int64, C.c_int64]),
-    "usf_wgrad_planes_workspace_floats": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
-    "usf_wgrad_planes_ok": (C.c_int, [C.c_int64, C.c_int64, C.c_int64]),
-    "usf_split_planes_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_int64, C.c_int64, _fp]),
-    "usf_wgrad_variant": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
-    "usf_sophiag_step_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32,
-                                       C.c_void_p]),
-    "usf_sophiag_hessian_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p]),
-    "usf_colsum_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_float, C.c_float, _fp, C.c_int64,
-                                 C.c_void_p]),
-    "usf_act_grad_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_float,
-                                   C.c_void_p]),
-    "usf_base_logprob_grad_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, C.c_int64, C.c_int32, _fp, _fp, _fp,
-                                            C.c_int64, C.c_void_p]),
-    "usf_grad_jobs_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_void_p]),
-    "usf_affine_prep_bwd_f32": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_int32,
-                                          C.c_int32, _fp, _fp, _fp, _fp, C.c_void_p]),
-}
-SYMBOLS = {**PUBLIC_SYMBOLS, **INTERNAL_SYMBOLS}
 
 _lib: Optional[C.CDLL] = None
 
@@ -343,10 +55,7 @@ def load() -> C.CDLL:
     if lib.usf_internal_version() != USF_INTERNAL_VERSION:
         raise RuntimeError(f"usflows_amd: internal ABI mismatch: library {lib.usf_internal_version()} != binding "
                            f"{USF_INTERNAL_VERSION}")
-    for kind, st in ((OP_LINEAR, LinearDesc), (OP_COUPLING, CouplingDesc), (0, Op), (3, LuPrepDesc), (4, PackJob),
-                     (OP_PACK_PLANES, PackPlanesDesc), (OP_GEMM_PLANES, GemmPlanesDesc),
-                     (OP_COUPLING_PLANES, CouplingPlanesDesc), (8, MtChunk), (OP_GATED_NORM, GatedNormDesc), (OP_CALL, CallDesc),
-                     (11, GradJob), (12, PsumJob)):
+    for kind, st in SIZEOF_KINDS.items():
         if lib.usf_sizeof_desc(kind) != C.sizeof(st):
             raise RuntimeError(f"usflows_amd: struct layout mismatch for {st.__name__}: "
                                f"C {lib.usf_sizeof_desc(kind)} vs ctypes {C.sizeof(st)}")
@@ -424,11 +133,6 @@ def _timed_call(fn, args, name):
 
 
 # ---- a layer loop's calls as ONE op list (USF_OP_CALL; flows.py: image-shaped flows) ------------------------------------
-CALL_FNS = {"usf_scale_f32": 1, "usf_channel_affine_f32": 2, "usf_layernorm_channels_f32": 3, "usf_gated_residual_f32": 4,
-            "usf_masked_residual_f32": 5, "usf_pointwise_conv_f32": 6, "usf_conv2d_same_f32": 7, "usf_conv2d_same_res_f32": 8,
-            "usf_base_logprob_f32": 9, "usf_radial_logprob_f32": 10, "usf_gated_tail_f32": 11, "usf_conv2d_same_ctx_f32": 12}
-
-
 class CallList:
     """the entry-point calls of one pass, recorded while they run (``with recording_calls(cl)``): (function id, argument
     words, which of them are pointers).  ``bad`` names the first call that has no USF_OP_CALL form."""
@@ -484,25 +188,28 @@ class recording_calls:
         return False
 
 
-def _launch(name: str, args: tuple, keep=None) -> None:
+def _launch(name: str, args: tuple, keep=None, *, tape: bool = True, unserved_ok: bool = False) -> int:
+    """THE way an entry point that takes a stream is called: `args` is the positional tuple the C function receives.  Every
+    call is recorded into an open CallList and bracketed by HIP events when launch_timing asks for its name.  tape: also
+    appended to the innermost recording tape (with `keep` alive as long as the tape), so that ``replay`` re-issues it.
+    unserved_ok: rc 1 ("this shape is not served") is returned instead of raised, and the call is recorded into the
+    CallList only once it has returned 0.  Returns rc: 0, or 1 where allowed; anything else raises through ``check``."""
     fn = getattr(load(), name)
-    rec = _tls.rec
-    if rec and rec[-1] is not None:
-        rec[-1].entries.append((fn, args, name, keep))
+    if tape:
+        rec = _tls.rec
+        if rec and rec[-1] is not None:
+            rec[-1].entries.append((fn, args, name, keep))
     cl = getattr(_tls, "calls", None)
-    if cl is not None:
+    if cl is not None and not unserved_ok:
         cl.add(name, args)
     rc = _timed_call(fn, args, name)
     if rc != 0:
+        if rc == 1 and unserved_ok:
+            return rc
         check(rc, name)
-
-
-def _direct(name: str, *args) -> None:
-    """call entry point `name` now (never taped); bracketed by HIP events when launch_timing asks for this name"""
-    cl = getattr(_tls, "calls", None)
-    if cl is not None:
+    elif cl is not None and unserved_ok:
         cl.add(name, args)
-    check(_timed_call(getattr(load(), name), args, name), name)
+    return rc
 
 
 def host_op(fn) -> None:
@@ -569,8 +276,6 @@ def planes_bytes(M: int, nkb: int, fmt: int = 0) -> int:
     """size of a planes buffer of M rows and nkb 32-feature blocks (include/usflows_hip.h)"""
     return (-(-M // 16)) * nkb * (2048 if fmt == 1 else 3072)
 
-
-PLANES_BF16X3, PLANES_F16X2 = 0, 1
 
 
 def pack_planes(src, planes, *, M, nkb, idx, ld=None, pre_div=None, pre_sub=None, fmt=PLANES_BF16X3, range_flag=None, src_cols=0,
@@ -644,38 +349,38 @@ def radial_logprob_grad(z, ldz, r, g_lp, M, D, p_id, loc, norm, K, par_a, par_b,
 
 
 def base_sample(z, ldz, M, D, base, loc, scale, seed, offset, row_offset=0):
-    check(load().usf_base_sample_f32(z.data_ptr(), ldz, M, D, base, ptr(loc), ptr(scale), seed, offset,
-                                     row_offset, current_stream(z.device)), "usf_base_sample_f32")
+    _launch("usf_base_sample_f32", (z.data_ptr(), ldz, M, D, base, ptr(loc), ptr(scale), seed, offset, row_offset,
+                                    current_stream(z.device)), tape=False)
 
 
 def radial_sample(z, ldz, M, D, base, loc, r, seed, offset, row_offset=0):
-    check(load().usf_radial_sample_f32(z.data_ptr(), ldz, M, D, base, loc.data_ptr(), r.data_ptr(), seed, offset,
-                                       row_offset, current_stream(z.device)), "usf_radial_sample_f32")
+    _launch("usf_radial_sample_f32", (z.data_ptr(), ldz, M, D, base, loc.data_ptr(), r.data_ptr(), seed, offset, row_offset,
+                                      current_stream(z.device)), tape=False)
 
 
 def variates_from_bits(bits, u=None, laplace=None, exponential=None):
     """the head kernels' word -> variate maps on caller-supplied int32/uint32 words (include/usflows_hip.h)"""
-    check(load().usf_variates_from_bits_f32(bits.data_ptr(), bits.numel(), ptr(u), ptr(laplace), ptr(exponential),
-                                            current_stream(bits.device)), "usf_variates_from_bits_f32")
+    _launch("usf_variates_from_bits_f32", (bits.data_ptr(), bits.numel(), ptr(u), ptr(laplace), ptr(exponential),
+                                           current_stream(bits.device)), tape=False)
 
 
 def scale(x, ldx, y, ldy, M, D, s, divide):
-    _direct("usf_scale_f32", x.data_ptr(), ldx, y.data_ptr(), ldy, M, D, s.data_ptr(), int(divide), current_stream(x.device))
+    _launch("usf_scale_f32", (x.data_ptr(), ldx, y.data_ptr(), ldy, M, D, s.data_ptr(), int(divide), current_stream(x.device)), tape=False)
 
 
 def affine_coupling_apply(z, ldz, t, ldt, s, lds, M, n, bound, inverse, logdet=None, z_off=0, t_off=0, s_off=0):
     """usf_affine_coupling_apply_f32 (element offsets *_off into the fp32 tensors)"""
-    check(load().usf_affine_coupling_apply_f32(z.data_ptr() + 4 * z_off, ldz, t.data_ptr() + 4 * t_off, ldt,
-                                               s.data_ptr() + 4 * s_off, lds, M, n, float(bound), int(inverse),
-                                               ptr(logdet), current_stream(z.device)), "usf_affine_coupling_apply_f32")
+    _launch("usf_affine_coupling_apply_f32", (z.data_ptr() + 4 * z_off, ldz, t.data_ptr() + 4 * t_off, ldt,
+                                              s.data_ptr() + 4 * s_off, lds, M, n, float(bound), int(inverse), ptr(logdet),
+                                              current_stream(z.device)), tape=False)
 
 
 def channel_affine(x, y, W, *, pre_sub=None, bias=None):
     """usf_channel_affine_f32 on a contiguous [B, C, *spatial] fp32 tensor (1 x 1 convolution over the channel axis)"""
     B, Cc = x.shape[0], x.shape[1]
     P = math.prod(x.shape[2:])            # (from the shape, not from numel: an empty batch still has pixels)
-    _direct("usf_channel_affine_f32", x.data_ptr(), y.data_ptr(), B, Cc, P, W.data_ptr(), ptr(pre_sub), ptr(bias),
-                                        current_stream(x.device))
+    _launch("usf_channel_affine_f32", (x.data_ptr(), y.data_ptr(), B, Cc, P, W.data_ptr(), ptr(pre_sub), ptr(bias),
+            current_stream(x.device)), tape=False)
 
 
 def layernorm_channels(x, gamma, beta, eps, act=ACT_NONE, slope=0.0):
@@ -683,9 +388,31 @@ def layernorm_channels(x, gamma, beta, eps, act=ACT_NONE, slope=0.0):
     B, Cc = x.shape[0], x.shape[1]
     P = math.prod(x.shape[2:])            # (from the shape, not from numel: an empty batch still has pixels)
     y = torch.empty_like(x)
-    _direct("usf_layernorm_channels_f32", x.data_ptr(), y.data_ptr(), B, Cc, P, gamma.data_ptr(), beta.data_ptr(), float(eps),
-                                            int(act), float(slope), current_stream(x.device))
+    _launch("usf_layernorm_channels_f32", (x.data_ptr(), y.data_ptr(), B, Cc, P, gamma.data_ptr(), beta.data_ptr(), float(eps),
+            int(act), float(slope), current_stream(x.device)), tape=False)
     return y
+
+
+def _job_table(jobs, blocks_of):
+    """(raw, off_blocks, n_blocks): the table the *_jobs_f32 / *_batch_f32 kernels read, block b working on job map[b] --
+    bytes(array of the jobs' struct) | zero pad to 16 | int32 map[n_blocks] at byte off_blocks.  Job i gets blocks_of(job)
+    consecutive blocks; its ``first_block`` is set here"""
+    block_job = []
+    for i, j in enumerate(jobs):
+        j.first_block = len(block_job)
+        block_job.extend([i] * blocks_of(j))
+    raw = bytearray(bytes((type(jobs[0]) * len(jobs))(*jobs)))
+    raw += b"\0" * ((-len(raw)) % 16)
+    off = len(raw)
+    raw += struct.pack(f"<{len(block_job)}i", *block_job)
+    return raw, off, len(block_job)
+
+
+def conv2d_planes_shape(rows: int, cols: int, k: int):
+    """(3, coutp, kp): the planes of a [rows, cols, k, k] convolution weight -- columns padded to a multiple of 8 per tap, rows
+    to 16, the K axis (k * k * padded columns) to 32 (include/usflows_hip.h: usf_conv2d_weight_elems)"""
+    cp = (cols + 7) // 8 * 8
+    return 3, (rows + 15) // 16 * 16, (k * k * cp + 31) // 32 * 32
 
 
 def conv2d_weight_planes_pair(weight: torch.Tensor):
@@ -694,22 +421,12 @@ def conv2d_weight_planes_pair(weight: torch.Tensor):
     cout, cin, k, _ = weight.shape
     lib = load()
     w = weight.detach().contiguous()
-    shapes = []
-    for rows, cols in ((cout, cin), (cin, cout)):
-        cp, coutp = (cols + 7) // 8 * 8, (rows + 15) // 16 * 16
-        shapes.append((3, coutp, (k * k * cp + 31) // 32 * 32))
+    shapes = conv2d_planes_shape(cout, cin, k), conv2d_planes_shape(cin, cout, k)
     n_f, n_t = math.prod(shapes[0]), math.prod(shapes[1])
     assert n_f == lib.usf_conv2d_weight_elems(cin, cout, k) and n_t == lib.usf_conv2d_weight_elems(cout, cin, k)
     buf = torch.empty(n_f + n_t, dtype=torch.bfloat16, device=weight.device)
-    check(lib.usf_conv2d_weight_planes_f32(w.data_ptr(), buf.data_ptr(), cin, cout, k, 2, current_stream(weight.device)),
-          "usf_conv2d_weight_planes_f32")
+    _launch("usf_conv2d_weight_planes_f32", (w.data_ptr(), buf.data_ptr(), cin, cout, k, 2, current_stream(weight.device)), tape=False)
     return buf[:n_f].view(shapes[0]), buf[n_f:].view(shapes[1])
-
-
-class WPlanesJob(C.Structure):
-    """usf_wplanes_job"""
-    _fields_ = [("w", C.c_void_p), ("out_off", C.c_int64), ("cin", C.c_int32), ("cout", C.c_int32), ("ks", C.c_int32),
-                ("first_block", C.c_int32)]
 
 
 class WeightPlanesBatch:
@@ -720,25 +437,17 @@ class WeightPlanesBatch:
     def __init__(self, weights):
         self.key = tuple((w.data_ptr(), tuple(w.shape)) for w in weights)
         self.device = weights[0].device
-        jobs, block_job, self.views, off, first = [], [], [], 0, 0
-        for i, w in enumerate(weights):
+        jobs, blocks, self.views, off = [], {}, [], 0
+        for w in weights:
             cout, cin, k, _ = w.shape
-            shapes = []
-            for rows, cols in ((cout, cin), (cin, cout)):
-                cp, coutp = (cols + 7) // 8 * 8, (rows + 15) // 16 * 16
-                shapes.append((3, coutp, (k * k * cp + 31) // 32 * 32))
+            shapes = conv2d_planes_shape(cout, cin, k), conv2d_planes_shape(cin, cout, k)
             n_f, n_t = math.prod(shapes[0]), math.prod(shapes[1])
-            nb = (max(n_f, n_t) // 3 + 255) // 256
-            jobs.append(WPlanesJob(w.data_ptr(), off, cin, cout, k, first))
-            block_job.extend([i] * nb)
+            jobs.append(WPlanesJob(w.data_ptr(), off, cin, cout, k, 0))
+            blocks[off] = (max(n_f, n_t) // 3 + 255) // 256
             self.views.append((off, n_f, shapes[0], n_t, shapes[1]))
             off += n_f + n_t
-            first += nb
-        self.total, self.n_blocks = off, first
-        raw = bytearray(bytes((WPlanesJob * len(jobs))(*jobs)))
-        raw += b"\0" * ((-len(raw)) % 16)
-        self.off_blocks = len(raw)
-        raw += struct.pack(f"<{len(block_job)}i", *block_job)
+        self.total = off
+        raw, self.off_blocks, self.n_blocks = _job_table(jobs, lambda j: blocks[j.out_off])
         self.host = torch.frombuffer(raw, dtype=torch.uint8)
         self.table = None
 
@@ -769,11 +478,10 @@ def conv2d_weight_planes(weight: torch.Tensor, gate_channels: int = 0, transpose
         lib = load()
         w = weight.detach().contiguous()
         rows, cols = (cin, cout) if transposed else (cout, cin)
-        cp, coutp = (cols + 7) // 8 * 8, (rows + 15) // 16 * 16
-        planes = torch.empty(3, coutp, (k * k * cp + 31) // 32 * 32, dtype=torch.bfloat16, device=weight.device)
+        planes = torch.empty(conv2d_planes_shape(rows, cols, k), dtype=torch.bfloat16, device=weight.device)
         assert planes.numel() == lib.usf_conv2d_weight_elems(cols, rows, k)
-        check(lib.usf_conv2d_weight_planes_f32(w.data_ptr(), planes.data_ptr(), cin, cout, k, int(transposed),
-                                               current_stream(weight.device)), "usf_conv2d_weight_planes_f32")
+        _launch("usf_conv2d_weight_planes_f32", (w.data_ptr(), planes.data_ptr(), cin, cout, k, int(transposed),
+                                                 current_stream(weight.device)), tape=False)
         return planes
     if transposed:
         weight = weight.detach().flip(2, 3).transpose(0, 1).contiguous()
@@ -820,9 +528,9 @@ def conv2d_same(x, planes, cout, ks, bias=None, in_mul=None, in_act=ACT_NONE, in
     B, cin, H, W = x.shape
     gc = 0 if gate_x is None else gate_x.shape[1]
     y = torch.empty(B, gc if gc else cout, H, W, dtype=torch.float32, device=x.device)
-    _direct("usf_conv2d_same_f32", x.data_ptr(), y.data_ptr(), B, cin, cout, H, W, ks, planes.data_ptr(), ptr(bias),
-                                     ptr(in_mul), int(in_act), float(in_slope), int(out_act), float(out_slope),
-                                     ptr(gate_x), gc, current_stream(x.device))
+    _launch("usf_conv2d_same_f32", (x.data_ptr(), y.data_ptr(), B, cin, cout, H, W, ks, planes.data_ptr(), ptr(bias),
+            ptr(in_mul), int(in_act), float(in_slope), int(out_act), float(out_slope),
+            ptr(gate_x), gc, current_stream(x.device)), tape=False)
     return y
 
 
@@ -836,9 +544,9 @@ def conv2d_same_ctx(x, planes, cout, ks, ctx, w_ctx, bias=None, in_mul=None, in_
     assert ctx.is_cuda and ctx.dtype == torch.float32 and ctx.is_contiguous() and n in (1, B), (ctx.shape, B)
     assert w_ctx.dtype == torch.float32 and w_ctx.is_contiguous() and w_ctx.numel() == cout * ks * ks
     y = torch.empty(B, cout, H, W, dtype=torch.float32, device=x.device)
-    _direct("usf_conv2d_same_ctx_f32", x.data_ptr(), y.data_ptr(), B, cin, cout, H, W, ks, planes.data_ptr(), ptr(bias),
+    _launch("usf_conv2d_same_ctx_f32", (x.data_ptr(), y.data_ptr(), B, cin, cout, H, W, ks, planes.data_ptr(), ptr(bias),
             ptr(in_mul), int(in_act), float(in_slope), int(out_act), float(out_slope), ctx.data_ptr(), 1 if (n == B and B > 1) else 0,
-            w_ctx.data_ptr(), current_stream(x.device))
+            w_ctx.data_ptr(), current_stream(x.device)), tape=False)
     return y
 
 
@@ -850,8 +558,8 @@ def conv_ctx_wgrad(dy, ctx, ks):
     assert ctx.is_cuda and ctx.dtype == torch.float32 and ctx.is_contiguous() and n in (1, B), (ctx.shape, B)
     dy = dy.contiguous()
     dwc = torch.empty(cout, ks * ks, dtype=torch.float32, device=dy.device)
-    _direct("usf_conv_ctx_wgrad_f32", dy.data_ptr(), ctx.data_ptr(), 1 if (n == B and B > 1) else 0, B, cout, H, W, ks,
-            dwc.data_ptr(), current_stream(dy.device))
+    _launch("usf_conv_ctx_wgrad_f32", (dy.data_ptr(), ctx.data_ptr(), 1 if (n == B and B > 1) else 0, B, cout, H, W, ks,
+            dwc.data_ptr(), current_stream(dy.device)), tape=False)
     return dwc
 
 
@@ -860,17 +568,10 @@ def conv2d_same_res(x, planes, cout, ks, res_x, res_mul, res_sign, bias=None, in
     res_x + res_sign * (res_mul * conv(x)) as a new tensor, or None when the fused form does not serve the shape"""
     B, cin, H, W = x.shape
     y = torch.empty(B, cout, H, W, dtype=torch.float32, device=x.device)
-    fn = load().usf_conv2d_same_res_f32
-    args = (x.data_ptr(), y.data_ptr(), B, cin, cout, H, W, ks, planes.data_ptr(), ptr(bias), ptr(in_mul), int(in_act),
-            float(in_slope), res_x.data_ptr(), res_mul.data_ptr(), float(res_sign), current_stream(x.device))
-    rc = _timed_call(fn, args, "usf_conv2d_same_res_f32")
-    if rc == 1:
-        return None
-    cl = getattr(_tls, "calls", None)
-    if cl is not None and rc == 0:
-        cl.add("usf_conv2d_same_res_f32", args)
-    check(rc, "usf_conv2d_same_res_f32")
-    return y
+    rc = _launch("usf_conv2d_same_res_f32", (x.data_ptr(), y.data_ptr(), B, cin, cout, H, W, ks, planes.data_ptr(), ptr(bias),
+                                             ptr(in_mul), int(in_act), float(in_slope), res_x.data_ptr(), res_mul.data_ptr(),
+                                             float(res_sign), current_stream(x.device)), tape=False, unserved_ok=True)
+    return None if rc else y
 
 
 def conv2d_same_gate(x, planes, cout, ks, gate_h, gate_slope, gate_mul=None, gate_add=None):
@@ -879,13 +580,10 @@ def conv2d_same_gate(x, planes, cout, ks, gate_h, gate_slope, gate_mul=None, gat
     output stream), or None when not served"""
     B, cin, H, W = x.shape
     y = torch.empty(B, cout, H, W, dtype=torch.float32, device=x.device)
-    args = (x.data_ptr(), y.data_ptr(), B, cin, cout, H, W, ks, planes.data_ptr(), gate_h.data_ptr(), float(gate_slope), ptr(gate_mul),
-            ptr(gate_add), current_stream(x.device))
-    rc = _timed_call(load().usf_conv2d_same_gate_f32, args, "usf_conv2d_same_gate_f32")
-    if rc == 1:
-        return None
-    check(rc, "usf_conv2d_same_gate_f32")
-    return y
+    rc = _launch("usf_conv2d_same_gate_f32", (x.data_ptr(), y.data_ptr(), B, cin, cout, H, W, ks, planes.data_ptr(), gate_h.data_ptr(),
+                                              float(gate_slope), ptr(gate_mul), ptr(gate_add), current_stream(x.device)),
+                 tape=False, unserved_ok=True)
+    return None if rc else y
 
 
 def pointwise_conv_supported(cin: int, cout: int, gated: bool = False) -> bool:
@@ -900,10 +598,10 @@ def pointwise_conv(x, W, bias=None, in_act=ACT_NONE, in_slope=0.0, out_act=ACT_N
     cout = W.shape[0]
     P = math.prod(x.shape[2:])
     y = torch.empty_like(gate_x) if gate_x is not None else torch.empty((B, cout) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
-    _direct("usf_pointwise_conv_f32", x.data_ptr(), y.data_ptr(), B, cin, cout, P, W.data_ptr(), ptr(bias), int(in_act),
-                                        float(in_slope), int(out_act), float(out_slope), ptr(gate_x),
-                                        None if ln is None else ln[0].data_ptr(), None if ln is None else ln[1].data_ptr(),
-                                        0.0 if ln is None else float(ln[2]), current_stream(x.device))
+    _launch("usf_pointwise_conv_f32", (x.data_ptr(), y.data_ptr(), B, cin, cout, P, W.data_ptr(), ptr(bias), int(in_act),
+            float(in_slope), int(out_act), float(out_slope), ptr(gate_x),
+            None if ln is None else ln[0].data_ptr(), None if ln is None else ln[1].data_ptr(),
+            0.0 if ln is None else float(ln[2]), current_stream(x.device)), tape=False)
     return y
 
 
@@ -912,7 +610,7 @@ def gated_residual(x, vg):
     B = x.shape[0]
     CP = math.prod(x.shape[1:])
     y = torch.empty_like(x)
-    _direct("usf_gated_residual_f32", x.data_ptr(), vg.data_ptr(), y.data_ptr(), B, CP, current_stream(x.device))
+    _launch("usf_gated_residual_f32", (x.data_ptr(), vg.data_ptr(), y.data_ptr(), B, CP, current_stream(x.device)), tape=False)
     return y
 
 
@@ -946,8 +644,8 @@ def masked_residual(x, t, one_minus_mask, sign):
     B = t.shape[0]
     CP = math.prod(t.shape[1:])
     y = torch.empty_like(t)
-    _direct("usf_masked_residual_f32", ptr(x), t.data_ptr(), one_minus_mask.data_ptr(), float(sign), y.data_ptr(), B,
-                                         CP, current_stream(t.device))
+    _launch("usf_masked_residual_f32", (ptr(x), t.data_ptr(), one_minus_mask.data_ptr(), float(sign), y.data_ptr(), B,
+            CP, current_stream(t.device)), tape=False)
     return y
 
 
@@ -1077,15 +775,7 @@ def flush_partial_sums(task: int, final: bool = True) -> None:
         if w is not None:
             groups.setdefault((w.CIT, w.COT, w.T), []).append((w, j[2]))
     for (cit, cot, t_), members in groups.items():
-        block_job, first = [], 0
-        for i, (w, _keep) in enumerate(members):
-            w.first_block = first
-            block_job.extend([i] * w.blocks)
-            first += w.blocks
-        raw = bytearray(bytes((WgradJob * len(members))(*[w for w, _ in members])))
-        raw += b"\0" * ((-len(raw)) % 16)
-        off = len(raw)
-        raw += struct.pack(f"<{len(block_job)}i", *block_job)
+        raw, off, first = _job_table([w for w, _ in members], lambda w: w.blocks)
         table = _device_table(torch.frombuffer(raw, dtype=torch.uint8), device)
         if table is None:
             raise RuntimeError("usflows_amd: deferred weight gradients inside a stream capture without a capture_tables buffer")
@@ -1097,19 +787,9 @@ def flush_partial_sums(task: int, final: bool = True) -> None:
         part = [(j[stage], j[2]) for j in jobs if j[stage] is not None]
         if not part:
             continue
-        block_job, first = [], 0
-        for i, (j, _keep) in enumerate(part):
-            nb = ((j.n + 255) // 256 if j.vec4 else (j.n + 63) // 64) * j.rows
-            j.first_block = first
-            block_job.extend([i] * nb)
-            first += nb
-        arr = (PsumJob * len(part))(*[j for j, _ in part])
-        raw = bytearray(bytes(arr))
-        raw += b"\0" * ((-len(raw)) % 16)
-        off = len(raw)
-        raw += struct.pack(f"<{len(block_job)}i", *block_job)
-        host = torch.frombuffer(raw, dtype=torch.uint8)
-        table = _device_table(host, device)
+        raw, off, first = _job_table([j for j, _ in part],
+                                     lambda j: ((j.n + 255) // 256 if j.vec4 else (j.n + 63) // 64) * j.rows)
+        table = _device_table(torch.frombuffer(raw, dtype=torch.uint8), device)
         if table is None:
             raise RuntimeError("usflows_amd: deferred partial sums inside a stream capture without a capture_tables buffer")
         _launch("usf_partial_sum_jobs_f32", (table.data_ptr(), table.data_ptr() + off, first, current_stream(device)),
@@ -1184,36 +864,27 @@ def conv_wgrad(x, dy, ks, in_mul=None, pre_sub=None, in_act=ACT_NONE, in_slope=0
     ws = torch.empty(ws_n, dtype=torch.float32, device=x.device)
     dW = torch.empty(cout, cin, ks, ks, dtype=torch.float32, device=x.device)
     db = torch.empty(cout, dtype=torch.float32, device=x.device) if want_bias else None
-    if defer and _psum_may_defer(x, owners):
-        job2 = (PsumJob * 2)()
-        if config.wgrad_jobs:
-            # the weight-gradient launch itself is queued too (one launch per tile shape when the pass ends); the direct kernel-1
-            # form is launched here (wjob.blocks == 0) and only its sums wait
-            wjob = WgradJob()
-            rc = lib.usf_conv_wgrad_plan_f32(x.data_ptr(), dy.data_ptr(), B, cin, cout, H, W, ks, ptr(in_mul), ptr(pre_sub), int(in_act),
-                                             float(in_slope), dW.data_ptr(), ptr(db), ws.data_ptr(), ws_n, C.addressof(job2),
-                                             C.addressof(wjob), current_stream(x.device))
-            if rc == 1:
-                return None
-            check(rc, "usf_conv_wgrad_plan_f32")
-            if wjob.blocks > 0:
-                _psum_queue(job2, (ws, x, dy, in_mul, pre_sub), wjob)
-            else:
-                _psum_queue(job2, (ws,))
-            return dW, db
-        rc = lib.usf_conv_wgrad_deferred_f32(x.data_ptr(), dy.data_ptr(), B, cin, cout, H, W, ks, ptr(in_mul), ptr(pre_sub), int(in_act),
-                                             float(in_slope), dW.data_ptr(), ptr(db), ws.data_ptr(), ws_n, job2, current_stream(x.device))
-        if rc == 1:
-            return None
-        check(rc, "usf_conv_wgrad_deferred_f32")
-        _psum_queue(job2, (ws,))
-        return dW, db
     args = (x.data_ptr(), dy.data_ptr(), B, cin, cout, H, W, ks, ptr(in_mul), ptr(pre_sub), int(in_act), float(in_slope),
-            dW.data_ptr(), ptr(db), ws.data_ptr(), ws_n, current_stream(x.device))
-    rc = _timed_call(lib.usf_conv_wgrad_f32, args, "usf_conv_wgrad_f32")
-    if rc == 1:
+            dW.data_ptr(), ptr(db), ws.data_ptr(), ws_n)
+    stream = current_stream(x.device)
+    if not (defer and _psum_may_defer(x, owners)):
+        rc = _launch("usf_conv_wgrad_f32", args + (stream,), tape=False, unserved_ok=True)
+        return None if rc else (dW, db)
+    job2 = (PsumJob * 2)()
+    if config.wgrad_jobs:
+        # the weight-gradient launch itself is queued too (one launch per tile shape when the pass ends); the direct kernel-1
+        # form is launched here (wjob.blocks == 0) and only its sums wait
+        wjob = WgradJob()
+        if _launch("usf_conv_wgrad_plan_f32", args + (C.addressof(job2), C.addressof(wjob), stream), tape=False, unserved_ok=True):
+            return None
+        if wjob.blocks > 0:
+            _psum_queue(job2, (ws, x, dy, in_mul, pre_sub), wjob)
+        else:
+            _psum_queue(job2, (ws,))
+        return dW, db
+    if _launch("usf_conv_wgrad_deferred_f32", args + (job2, stream), tape=False, unserved_ok=True):
         return None
-    check(rc, "usf_conv_wgrad_f32")
+    _psum_queue(job2, (ws,))
     return dW, db
 
 
@@ -1226,8 +897,8 @@ def layernorm_channels_bwd(x, dy, gamma, eps, act=ACT_NONE, slope=0.0):
     ws = torch.empty(max(1, ws_n), dtype=torch.float32, device=x.device)
     dx = torch.empty_like(x)
     dgb = torch.empty(2 * Cc, dtype=torch.float32, device=x.device)
-    _direct("usf_layernorm_channels_bwd_f32", x.data_ptr(), dy.data_ptr(), dx.data_ptr(), B, Cc, P, gamma.data_ptr(), float(eps),
-            int(act), float(slope), dgb.data_ptr(), ws.data_ptr(), ws_n, current_stream(x.device))
+    _launch("usf_layernorm_channels_bwd_f32", (x.data_ptr(), dy.data_ptr(), dx.data_ptr(), B, Cc, P, gamma.data_ptr(), float(eps),
+            int(act), float(slope), dgb.data_ptr(), ws.data_ptr(), ws_n, current_stream(x.device)), tape=False)
     return dx, dgb[:Cc], dgb[Cc:]
 
 
@@ -1236,7 +907,7 @@ def gated_residual_bwd(dy, vg):
     B = dy.shape[0]
     CP = math.prod(dy.shape[1:])
     dvg = torch.empty_like(vg)
-    _direct("usf_gated_residual_bwd_f32", dy.data_ptr(), vg.data_ptr(), dvg.data_ptr(), B, CP, current_stream(dy.device))
+    _launch("usf_gated_residual_bwd_f32", (dy.data_ptr(), vg.data_ptr(), dvg.data_ptr(), B, CP, current_stream(dy.device)), tape=False)
     return dvg
 
 
@@ -1251,8 +922,8 @@ def gated_tail(h, x, W, bias, in_act=ACT_NONE, in_slope=0.0, post_act=ACT_NONE, 
     P = math.prod(x.shape[2:])
     y = torch.empty_like(x)
     g, bt, eps = ln if ln is not None else (None, None, 0.0)
-    _direct("usf_gated_tail_f32", h.data_ptr(), x.data_ptr(), y.data_ptr(), B, Cc, P, W.data_ptr(), ptr(bias), int(in_act),
-            float(in_slope), int(post_act), float(post_slope), ptr(g), ptr(bt), float(eps), current_stream(x.device))
+    _launch("usf_gated_tail_f32", (h.data_ptr(), x.data_ptr(), y.data_ptr(), B, Cc, P, W.data_ptr(), ptr(bias), int(in_act),
+            float(in_slope), int(post_act), float(post_slope), ptr(g), ptr(bt), float(eps), current_stream(x.device)), tape=False)
     return y
 
 
@@ -1275,7 +946,7 @@ def gated_tail_bwd(h, x, dy, W, bias, in_act=ACT_NONE, in_slope=0.0, post_act=AC
     args = (h.data_ptr(), x.data_ptr(), dy.data_ptr(), dx.data_ptr(), dh.data_ptr(), ptr(dvg), B, Cc, P, W.data_ptr(), ptr(bias),
             int(in_act), float(in_slope), int(post_act), float(post_slope), ptr(g), ptr(bt), float(eps), dpar.data_ptr(), ws.data_ptr(),
             ws_n, C.cast(job2, C.c_void_p) if job2 is not None else None, current_stream(x.device))
-    check(_timed_call(lib.usf_gated_tail_bwd_f32, args, "usf_gated_tail_bwd_f32"), "usf_gated_tail_bwd_f32")
+    _launch("usf_gated_tail_bwd_f32", args, tape=False)
     if job2 is not None:
         _psum_queue(job2, (ws,))
     dW, db = dpar[:nW].view(2 * Cc, Cc), dpar[nW: nW + 2 * Cc]
@@ -1298,8 +969,8 @@ def affine_prep(Lr, Ur, bias, vk=None, w0=None):
     M, Minv, b, c = MM[:n], MM[n:], bc[:n], bc[n:]
     ladj = torch.empty(n, dtype=torch.float32, device=dev)
     save = torch.empty(n, 7, Cc, Cc, dtype=torch.float32, device=dev)
-    _direct("usf_affine_prep_f32", Lr.data_ptr(), Ur.data_ptr(), bias.data_ptr(), ptr(vk), ptr(w0), n, Cc, nvs, M.data_ptr(),
-            Minv.data_ptr(), b.data_ptr(), c.data_ptr(), ladj.data_ptr(), save.data_ptr(), current_stream(dev))
+    _launch("usf_affine_prep_f32", (Lr.data_ptr(), Ur.data_ptr(), bias.data_ptr(), ptr(vk), ptr(w0), n, Cc, nvs, M.data_ptr(),
+            Minv.data_ptr(), b.data_ptr(), c.data_ptr(), ladj.data_ptr(), save.data_ptr(), current_stream(dev)), tape=False)
     return M, Minv, b, c, ladj, save
 
 
@@ -1312,15 +983,15 @@ def affine_prep_bwd(save, bias, vk, w0, Minv, b, dM, dMinv, db, dc, dladj):
     dUr = torch.empty_like(dLr)
     dbias = torch.empty(n, Cc, dtype=torch.float32, device=dev)
     dvk = torch.empty(n, nvs, Cc, dtype=torch.float32, device=dev) if nvs else None
-    _direct("usf_affine_prep_bwd_f32", save.data_ptr(), bias.data_ptr(), ptr(vk), ptr(w0), Minv.data_ptr(), b.data_ptr(),
+    _launch("usf_affine_prep_bwd_f32", (save.data_ptr(), bias.data_ptr(), ptr(vk), ptr(w0), Minv.data_ptr(), b.data_ptr(),
             dM.data_ptr(), dMinv.data_ptr(), db.data_ptr(), dc.data_ptr(), dladj.data_ptr(), n, Cc, nvs, dLr.data_ptr(),
-            dUr.data_ptr(), dbias.data_ptr(), ptr(dvk), current_stream(dev))
+            dUr.data_ptr(), dbias.data_ptr(), ptr(dvk), current_stream(dev)), tape=False)
     return dLr, dUr, dbias, dvk
 
 
 def gather_cols(src, lds, dst, ldd, M, n, idx):
-    check(load().usf_gather_cols_f32(src.data_ptr(), lds, dst.data_ptr(), ldd, M, n, idx.data_ptr(),
-                                     current_stream(src.device)), "usf_gather_cols_f32")
+    _launch("usf_gather_cols_f32", (src.data_ptr(), lds, dst.data_ptr(), ldd, M, n, idx.data_ptr(), current_stream(src.device)),
+            tape=False)
 
 
 def coupling_op(op, device):
@@ -1339,7 +1010,7 @@ def mfma_probe(device, iters: int = 400, repeats: int = 5) -> dict:
     for i in range(repeats + 1):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        check(load().usf_mfma_probe(src.data_ptr(), sink.data_ptr(), iters, 0, C.byref(flops), current_stream(device)), "usf_mfma_probe")
+        _launch("usf_mfma_probe", (src.data_ptr(), sink.data_ptr(), iters, 0, C.byref(flops), current_stream(device)), tape=False)
         e1.record()
         e1.synchronize()
         if i:
@@ -1376,7 +1047,7 @@ def coupling_planes_op(op, device):
 
 
 def run_ops(ops_array, n, device=None):
-    check(load().usf_run_ops(ops_array, n, current_stream(device)), "usf_run_ops")
+    _launch("usf_run_ops", (ops_array, n, current_stream(device)), tape=False)
 
 
 # ---- parameter prep (usf_prep.hip) -------------------------------------------------
@@ -1486,22 +1157,15 @@ class batch_jobs:
             _launch(entry, (table.data_ptr(), len(part), max_rows, max_cols, current_stream(self.device)),
                     (table, [j[1] for j in part]))
 
-
     def _flush_grads(self):
         gj, self.grad_jobs = self.grad_jobs, []
         if not gj:
             return
-        block_job, first = [], 0
-        for i, (j, _keep) in enumerate(gj):
-            nb = ((j.N + 127) // 128) * ((j.K + 127) // 128) if j.A else (j.N + 63) // 64
-            j.first_block = first
-            block_job.extend([i] * nb)
-            first += nb
-        arr = (GradJob * len(gj))(*[j[0] for j in gj])
-        table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
-        bj = torch.tensor(block_job, dtype=torch.int32).to(self.device)
-        _launch("usf_grad_jobs_f32", (table.data_ptr(), bj.data_ptr(), first, current_stream(self.device)),
-                (table, bj, [j[1] for j in gj]))
+        raw, off, first = _job_table([j for j, _ in gj],
+                                     lambda j: ((j.N + 127) // 128) * ((j.K + 127) // 128) if j.A else (j.N + 63) // 64)
+        table = torch.frombuffer(raw, dtype=torch.uint8).to(self.device)
+        _launch("usf_grad_jobs_f32", (table.data_ptr(), table.data_ptr() + off, first, current_stream(self.device)),
+                (table, [k for _, k in gj]))
 
 
 GRAD_JOB_MAX_ROWS = 256      # usf_grad_jobs_f32 runs one row range per job (usf_wgrad_f32 splits the batch above this)
@@ -1651,15 +1315,7 @@ def wgrad_reduce_flush(queue, device) -> None:
     built once -- the queued pointers are plan-owned buffers, the same on every replay)"""
     if not queue:
         return
-    block_job, first = [], 0
-    for i, (j, _keep) in enumerate(queue):
-        j.first_block = first
-        block_job.extend([i] * j.blocks)
-        first += j.blocks
-    raw = bytearray(bytes((WReduceJob * len(queue))(*[j for j, _ in queue])))
-    raw += b"\0" * ((-len(raw)) % 16)
-    off = len(raw)
-    raw += struct.pack(f"<{len(block_job)}i", *block_job)
+    raw, off, first = _job_table([j for j, _ in queue], lambda j: j.blocks)
     table = torch.frombuffer(raw, dtype=torch.uint8).to(device)
     _launch("usf_wgrad_reduce_jobs_f32", (table.data_ptr(), table.data_ptr() + off, first, current_stream(device)),
             (table, [k for _, k in queue]))

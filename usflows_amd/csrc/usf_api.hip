@@ -222,6 +222,10 @@ int usf_sizeof_desc(int32_t kind) {
     case USF_OP_CALL: return (int)sizeof(usf_call_desc);
     case 11: return (int)sizeof(usf_grad_job);
     case 12: return (int)sizeof(usf_psum_job);
+    case 13: return (int)sizeof(usf_gated_norm_bwd_desc);
+    case 14: return (int)sizeof(usf_wgrad_job);
+    case 15: return (int)sizeof(usf_wreduce_job);
+    case 16: return (int)sizeof(usf_wplanes_job);
     default: return -1;
   }
 }
