@@ -16,7 +16,7 @@
 extern "C" {
 #endif
 
-#define USF_INTERNAL_VERSION 2
+#define USF_INTERNAL_VERSION 3
 
 /* USF_INTERNAL_VERSION of the header the library was built from (host only, launches nothing). */
 int usf_internal_version(void);
@@ -106,6 +106,30 @@ int usf_radial_logprob_grad_f32(const float* z, int64_t ldz, const float* r, con
                                 const float* loc, int32_t norm, int32_t K, const float* par_a, const float* par_b,
                                 const float* logits, float* g, int64_t ldg, float* d_loc, float* d_a, float* d_b, float* d_logits,
                                 void* workspace, int64_t workspace_bytes, usf_stream_t stream);
+
+/*
+ * usf_coupling_planes_ctx (internal version 3): usf_coupling_planes (usflows_hip.h) whose conditioner is a ConditionalDenseNN
+ * with context_dim == 1 (networks.py:739-751: layers[1](context) is added to the first layer's pre-activation).  The first
+ * layer's accumulators start at
+ *     b_in[h] + b_ctx[h] + ctx[m * ctx_stride] * w_ctx[h]                  (row m, hidden unit h)
+ * instead of b_in[h] -- a rank-1 term: no matrix instruction, no LDS, nothing in the K loops.  ctx: fp32, one value per row
+ * (ctx_stride == 1, M values) or one for all rows (ctx_stride == 0); nothing is read outside ctx, and a launch with a context
+ * leaves the rows of z's last panel beyond M as they are (usf_coupling_planes rewrites them from their own values).
+ * w_ctx / b_ctx: [256] fp32 (layers[1].weight[:, 0] / layers[1].bias), zero beyond the real width, 16-byte aligned.
+ * Inference and the training forward (hidden_out) in both plane formats, n_hidden 1..3 as usf_coupling_planes serves them;
+ * USF_ACT_GATE with a context is rejected (the backward chain has no context term: the context enters no data gradient).
+ * ctx == NULL: exactly usf_coupling_planes (same kernels, same bits).  Arguments are validated before any launch.
+ *
+ * Inside an op list (usf_run_ops): the public usf_op union does not grow.  A USF_OP_CALL op with fn ==
+ * USF_FN_COUPLING_PLANES_CTX and n_args == 4 carries (ctx, ctx_stride, w_ctx, b_ctx) as its words a[0..3] and applies to the
+ * USF_OP_COUPLING_PLANES op that must follow it directly: the pair is ONE usf_coupling_planes_ctx launch.  (Function ids from
+ * USF_FN_INTERNAL_BASE on are internal; usflows_hip.h's run 1..12 and must stay below it: the library asserts that at compile
+ * time.)  A list that ends behind the prefix op, or whose next op is of another kind, is rejected.
+ */
+#define USF_FN_INTERNAL_BASE 64
+#define USF_FN_COUPLING_PLANES_CTX 64
+int usf_coupling_planes_ctx(const usf_coupling_planes_desc* d, const float* ctx, int64_t ctx_stride, const float* w_ctx,
+                            const float* b_ctx, usf_stream_t stream);
 
 /* usf_conv_ctx_wgrad_f32 (ABI 36): the weight gradient of the context channel of usf_conv2d_same_ctx_f32 (usflows_hip.h;
  * reference networks.py:513-680 under autograd),

@@ -22,6 +22,7 @@ from ._abi import (  # noqa: E402,F401  -- the declarations, re-exported: caller
     USF_ABI_VERSION, USF_INTERNAL_VERSION, USF_MAX_HIDDEN, ACT_NONE, ACT_LEAKY_RELU, ACT_GATE, BASE_LAPLACE, BASE_NORMAL,
     BASE_LPNORM1, BASE_LPNORM2, BASE_LPNORMINF, BASE_ROWSUM, NORM_LOGNORMAL, NORM_GAMMA, NORM_RAW_PARAMS, RADIAL_MAX_K, OP_LINEAR,
     OP_COUPLING, OP_PACK_PLANES, OP_GEMM_PLANES, OP_COUPLING_PLANES, OP_GATED_NORM, OP_CALL, PLANES_BF16X3, PLANES_F16X2, CALL_FNS,
+    FN_COUPLING_PLANES_CTX,
     _fp, LinearDesc, CouplingDesc, PackPlanesDesc, GemmPlanesDesc, CouplingPlanesDesc, MtChunk, GatedNormDesc, GatedNormBwdDesc,
     CallDesc, _OpUnion, Op, LuPrepDesc, PackJob, PsumJob, WgradJob, WReduceJob, WPlanesJob, GradJob, SIZEOF_KINDS, PUBLIC_SYMBOLS,
     INTERNAL_SYMBOLS, SYMBOLS)
@@ -1044,6 +1045,26 @@ class clock_meter:
 def coupling_planes_op(op, device):
     """one usf_coupling_planes launch from an Op built by the engine (taped like every launch)"""
     _launch("usf_coupling_planes", (C.byref(op.u.coupling_planes), current_stream(device)), op)
+
+
+def coupling_planes_ctx_op(op, ctx, ctx_stride, w_ctx, b_ctx, device):
+    """usf_coupling_planes_ctx: usf_coupling_planes with the conditioner's context term (ctx None: exactly coupling_planes_op)"""
+    _launch("usf_coupling_planes_ctx", (C.byref(op.u.coupling_planes), ptr(ctx), int(ctx_stride), ptr(w_ctx), ptr(b_ctx),
+                                        current_stream(device)), (op, ctx, w_ctx, b_ctx))
+
+
+def coupling_planes_ctx_prefix(ctx, ctx_stride, w_ctx, b_ctx) -> "Op":
+    """the USF_OP_CALL op (USF_FN_COUPLING_PLANES_CTX) that hands the USF_OP_COUPLING_PLANES op behind it its context arguments"""
+    op = Op()
+    op.kind = OP_CALL
+    op.u.call.fn, op.u.call.n_args = FN_COUPLING_PLANES_CTX, 4
+    for j, w in enumerate((ctx.data_ptr(), int(ctx_stride), w_ctx.data_ptr(), b_ctx.data_ptr())):
+        op.u.call.a[j] = w
+    return op
+
+
+def is_ctx_prefix(op) -> bool:
+    return op.kind == OP_CALL and op.u.call.fn == FN_COUPLING_PLANES_CTX
 
 
 def run_ops(ops_array, n, device=None):

@@ -88,6 +88,8 @@ int pack_planes(const usf_pack_planes_desc* d, hipStream_t stream);
 int gemm_planes(const usf_gemm_planes_desc* d, hipStream_t stream);
 int gemm_planes_variant(const usf_gemm_planes_desc* d);
 int coupling_planes(const usf_coupling_planes_desc* d, hipStream_t stream);
+int coupling_planes_ctx(const usf_coupling_planes_desc* d, const float* ctx, int64_t ctx_stride, const float* w_ctx, const float* b_ctx,
+                        hipStream_t stream);
 int lu_prepare(const usf_lu_prep_desc* d, hipStream_t stream);
 int gemm_f64(const double* A, int64_t lda, int64_t sA, int transA, const double* B, int64_t ldb, int64_t sB, int transB,
              double* C, int64_t ldc, int64_t sC, int64_t M, int64_t N, int64_t K, int64_t batch, double alpha,
@@ -246,6 +248,10 @@ int usf_pack_planes_f32(const usf_pack_planes_desc* d, usf_stream_t stream) { re
 int usf_gemm_planes_bf16x3(const usf_gemm_planes_desc* d, usf_stream_t stream) { return usf::gemm_planes(d, (hipStream_t)stream); }
 
 int usf_coupling_planes(const usf_coupling_planes_desc* d, usf_stream_t stream) { return usf::coupling_planes(d, (hipStream_t)stream); }
+int usf_coupling_planes_ctx(const usf_coupling_planes_desc* d, const float* ctx, int64_t ctx_stride, const float* w_ctx, const float* b_ctx,
+                            usf_stream_t stream) {
+  return usf::coupling_planes_ctx(d, ctx, ctx_stride, w_ctx, b_ctx, (hipStream_t)stream);
+}
 int usf_gemm_planes_variant(const usf_gemm_planes_desc* d) { return usf::gemm_planes_variant(d); }
 int usf_coupling_variant(const usf_coupling_desc* d) { return usf::coupling_variant(d); }
 int usf_coupling_max_width(void) { return usf::coupling_max_width(); }
@@ -571,7 +577,11 @@ static int run_call(const usf_call_desc* c, usf_stream_t stream) {
 #define J(i) ((int32_t)a[i])
   auto F = [&](int i) { float f; uint32_t u = (uint32_t)a[i]; memcpy(&f, &u, 4); return f; };
   auto Dbl = [&](int i) { double d; uint64_t u = a[i]; memcpy(&d, &u, 8); return d; };
+  // this table holds the public ids of usflows_hip.h, which stay below USF_FN_INTERNAL_BASE: the ids from there on belong to
+  // usflows_hip_internal.h and are served by usf_run_ops itself (they apply to the op behind them)
   static const int nargs[] = {0, 8, 8, 10, 5, 7, 16, 17, 16, 11, 17, 15, 18};
+  static_assert(sizeof(nargs) / sizeof(nargs[0]) == USF_FN_CONV2D_SAME_CTX + 1, "one entry per public function id");
+  static_assert(USF_FN_CONV2D_SAME_CTX < USF_FN_INTERNAL_BASE, "a public function id ran into the internal range");
   if (c->fn < 1 || c->fn > USF_FN_CONV2D_SAME_CTX || c->n_args != nargs[c->fn]) {
     usf::set_error("usf_run_ops: call op with unknown function %d or %d arguments", c->fn, c->n_args);
     return -2;
@@ -624,7 +634,22 @@ int usf_run_ops(const usf_op* ops, int32_t n_ops, usf_stream_t stream) {
       case USF_OP_GEMM_PLANES: rc = usf::gemm_planes(&ops[i].u.gemm_planes, (hipStream_t)stream); break;
       case USF_OP_COUPLING_PLANES: rc = usf::coupling_planes(&ops[i].u.coupling_planes, (hipStream_t)stream); break;
       case USF_OP_GATED_NORM: rc = usf::gated_norm_rows(&ops[i].u.gated_norm, (hipStream_t)stream); break;
-      case USF_OP_CALL: rc = run_call(&ops[i].u.call, stream); break;
+      case USF_OP_CALL:
+        if (ops[i].u.call.fn == USF_FN_COUPLING_PLANES_CTX) {
+          // the context arguments of the USF_OP_COUPLING_PLANES op that follows (usflows_hip_internal.h): one launch for the pair
+          const usf_call_desc* c = &ops[i].u.call;
+          if (c->n_args != 4 || i + 1 >= n_ops || ops[i + 1].kind != USF_OP_COUPLING_PLANES) {
+            usf::set_error("usf_run_ops: op %d (USF_FN_COUPLING_PLANES_CTX) needs 4 arguments and a USF_OP_COUPLING_PLANES op behind it", i);
+            return -2;
+          }
+          rc = usf::coupling_planes_ctx(&ops[i + 1].u.coupling_planes, reinterpret_cast<const float*>((uintptr_t)c->a[0]), (int64_t)c->a[1],
+                                        reinterpret_cast<const float*>((uintptr_t)c->a[2]), reinterpret_cast<const float*>((uintptr_t)c->a[3]),
+                                        (hipStream_t)stream);
+          ++i;
+          break;
+        }
+        rc = run_call(&ops[i].u.call, stream);
+        break;
       default: usf::set_error("usf_run_ops: op %d has unknown kind %d", i, ops[i].kind); return -2;
     }
     if (rc != 0) return rc;

@@ -82,6 +82,8 @@ struct CplPArgs {
   // layer l's activations (MODE 1) resp. the gradients at its pre-activations (MODE 2); gate[l]: MODE 2, the saved
   // activations whose sign gates layer l (leaky_relu_backward from the saved output; only plane 0 is read)
   char* hout[2]; const char* gate[2];
+  // context term of the first layer (CTX instantiations only; usf_coupling_planes_ctx): ctx[row * ctx_stride], w_ctx / b_ctx [256]
+  const float* ctx; int ctx_stride; const float* w_ctx; const float* b_ctx;
 };
 
 #ifdef USF_STAMP
@@ -95,7 +97,10 @@ struct CplPArgs {
 // backward launch).  MODE 2 (training backward: the launch runs the conditioner's transposed chain on the gradient
 // buffer, usf_coupling_planes_desc::gate): the activation is leaky_relu_backward from the saved activations gate[l], and
 // hout[l] receives the gated values (the gradients at the pre-activations).
-template <int NPL, int NH, int MODE = 0>
+// CTX (MODE 0 / 1): ConditionalDenseNN's context layer (networks.py:739-751, context_dim 1) -- the first layer's accumulators
+// start at b_in[h] + b_ctx[h] + ctx[row] * w_ctx[h] instead of b_in[h]: a rank-1 term, no MFMA, no LDS, nothing in the K loops.
+// The CTX = false instantiations are the instruction streams they were without the flag.
+template <int NPL, int NH, int MODE = 0, bool CTX = false>
 __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs p) {
   typedef CPlanes<NPL> PT;
   typedef typename PT::vec vec8;
@@ -121,6 +126,8 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
   const int panel = blockIdx.x * 8 + wave;                       // this wave's 16 rows
   const int panc = min(panel, p.npanels - 1);
   const bool live = panel < p.npanels;
+  // the rows this lane writes back into z: a context launch leaves the last panel's rows beyond M as they are
+  const bool live_z = CTX ? (live && 16 * panel + lj < p.M) : live;
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   constexpr unsigned CHB = NPL * 1024u;
   const size_t zbase = ((size_t)panc * p.z_nkb) * CHB + (size_t)lane * 16;
@@ -172,6 +179,18 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
   f32x4 X1[T], X2[T];
 #pragma unroll
   for (int t = 0; t < T; ++t) X1[t] = *reinterpret_cast<const f32x4*>(p.b_in + t * 16 + 4 * lg);
+  if (CTX) {
+    // lane (lj, lg) holds hidden units 16 t + 4 lg + e of row 16 panel + lj; rows beyond M read the last row's context
+    const int crow = min(16 * panc + lj, p.M - 1);
+    const float c = p.ctx[(size_t)crow * p.ctx_stride];
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      const f32x4 wc = *reinterpret_cast<const f32x4*>(p.w_ctx + t * 16 + 4 * lg);
+      const f32x4 bc = *reinterpret_cast<const f32x4*>(p.b_ctx + t * 16 + 4 * lg);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) X1[t][e] = __builtin_fmaf(c, wc[e], X1[t][e] + bc[e]);
+    }
+  }
 
   // conditioning features: the B operand straight from the planes
   auto load_z = [&](int kb, vec8 (&dst)[NPL]) {
@@ -349,7 +368,7 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
       }
       vec8 o[NPL];
       PT::split(v[0], v[1], o);
-      if (live) {
+      if (live_z) {
 #pragma unroll
         for (int q = 0; q < NPL; ++q)
           *reinterpret_cast<vec8*>(p.z + zbase + (size_t)(p.kb_t0 + nt) * CHB + q * 1024) = o[q];
@@ -410,8 +429,17 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
 unsigned long long* g_cdbg = nullptr;
 #endif
 
-int coupling_planes(const usf_coupling_planes_desc* d, hipStream_t stream) {
+int coupling_planes_ctx(const usf_coupling_planes_desc* d, const float* ctx, int64_t ctx_stride, const float* w_ctx,
+                        const float* b_ctx, hipStream_t stream) {
   if (!d) { set_error("usf_coupling_planes: null descriptor"); return -1; }
+  if (ctx) {
+    if (d->act == USF_ACT_GATE) { set_error("usf_coupling_planes_ctx: USF_ACT_GATE takes no context (the context enters no data gradient)"); return -2; }
+    if (ctx_stride != 0 && ctx_stride != 1) { set_error("usf_coupling_planes_ctx: ctx_stride must be 0 or 1 (got %lld)", (long long)ctx_stride); return -2; }
+    if (!w_ctx || !b_ctx || !aligned16(w_ctx) || !aligned16(b_ctx)) {
+      set_error("usf_coupling_planes_ctx: w_ctx / b_ctx must be [256] fp32 vectors, 16-byte aligned");
+      return -2;
+    }
+  }
   if (d->M < 0 || d->M > 0x7fffffff || d->z_nkb <= 0 || d->n_hidden < 1 || d->n_hidden > 3 || d->nk_p <= 0 || d->nk_t <= 0 ||
       d->kb_p0 < 0 || d->kb_t0 < 0 || d->kb_p0 + d->nk_p > d->z_nkb || d->kb_t0 + d->nk_t > d->z_nkb) {
     set_error("usf_coupling_planes: bad sizes / block ranges");
@@ -443,6 +471,7 @@ int coupling_planes(const usf_coupling_planes_desc* d, hipStream_t stream) {
   a.ld_hid = d->ldw_hid; a.pl_hid = d->w_hid_plane;
   a.Wout = reinterpret_cast<const char*>(d->W_out); a.ld_out = d->ldw_out; a.pl_out = d->w_out_plane; a.b_out = d->b_out;
   a.sign = d->sign; a.slope = d->slope; a.act = d->act; a.range_flag = d->range_flag;
+  a.ctx = ctx; a.ctx_stride = (int)ctx_stride; a.w_ctx = w_ctx; a.b_ctx = b_ctx;
   a.dbg = nullptr;
 #ifdef USF_STAMP
   a.dbg = g_cdbg;
@@ -466,20 +495,33 @@ int coupling_planes(const usf_coupling_planes_desc* d, hipStream_t stream) {
     }
     const dim3 block(512);
 #define USF_CPT(NH_, MODE_) hipLaunchKernelGGL((coupling_planes_kernel<3, NH_, MODE_>), grid, block, 0, stream, a)
+#define USF_CPTC(NH_) hipLaunchKernelGGL((coupling_planes_kernel<3, NH_, 1, true>), grid, block, 0, stream, a)
     if (gated) { if (d->n_hidden == 1) USF_CPT(1, 2); else USF_CPT(2, 2); }
+    else if (ctx) { if (d->n_hidden == 1) USF_CPTC(1); else USF_CPTC(2); }
     else { if (d->n_hidden == 1) USF_CPT(1, 1); else USF_CPT(2, 1); }
+#undef USF_CPTC
 #undef USF_CPT
     return check_launch("usf_coupling_planes");
   }
   const dim3 block(512);
 #define USF_CPL(NPL_, NH_) hipLaunchKernelGGL((coupling_planes_kernel<NPL_, NH_>), grid, block, 0, stream, a)
-  if (npl == 2) {
+#define USF_CPLC(NPL_, NH_) hipLaunchKernelGGL((coupling_planes_kernel<NPL_, NH_, 0, true>), grid, block, 0, stream, a)
+  if (ctx) {
+    if (npl == 2) {
+      switch (d->n_hidden) { case 1: USF_CPLC(2, 1); break; case 2: USF_CPLC(2, 2); break; default: USF_CPLC(2, 3); break; }
+    } else {
+      switch (d->n_hidden) { case 1: USF_CPLC(3, 1); break; case 2: USF_CPLC(3, 2); break; default: USF_CPLC(3, 3); break; }
+    }
+  } else if (npl == 2) {
     switch (d->n_hidden) { case 1: USF_CPL(2, 1); break; case 2: USF_CPL(2, 2); break; default: USF_CPL(2, 3); break; }
   } else {
     switch (d->n_hidden) { case 1: USF_CPL(3, 1); break; case 2: USF_CPL(3, 2); break; default: USF_CPL(3, 3); break; }
   }
+#undef USF_CPLC
 #undef USF_CPL
   return check_launch("usf_coupling_planes");
 }
+
+int coupling_planes(const usf_coupling_planes_desc* d, hipStream_t stream) { return coupling_planes_ctx(d, nullptr, 0, nullptr, nullptr, stream); }
 
 }  // namespace usf

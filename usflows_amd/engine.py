@@ -320,6 +320,13 @@ class FlowEngine(PlanesPlanMixin):
         # usf_wgrad_blocked_f32.  USFLOWS_AMD_TRAIN_PLANES=0 keeps the fp32-row path of rounds 3 / 4.
         self.use_train_planes = config.train_planes
         self.train_planes_min_rows = 16384
+        # a context on the planes plans (usf_coupling_planes_ctx): smallest batch at which a flow WITH a context
+        # takes the planes plan in automatic mode (use_planes = None) resp. the planes training step, on top of the conditions
+        # above.  None = never: the context form has not been timed against the fp32-activation plan / the fp32-row path, which
+        # serve these flows as before, and goes on by default only behind a measured cross-over (tools/bench_ctx_planes.py).
+        # use_planes = True forces the inference plans as for every flow; training has no forced mode, so set the second knob
+        self.ctx_planes_min_rows = None
+        self.train_ctx_planes_min_rows = None
         self.use_graphs = bool(config.engine_graph)
         self.graph_max_rows = 1024
         self._layout_from_masks()
@@ -895,7 +902,7 @@ class FlowEngine(PlanesPlanMixin):
         pk = self.pack(device)
         with self._pk_record(pk), _ext.batch_jobs(device):
             if self._planes_ok(direction, B, has_ctx, train):
-                return self._build_plan_planes(direction, B, device, final, train)
+                return self._build_plan_planes(direction, B, device, final, train, has_ctx)
             return self._build_plan_body(direction, B, device, has_ctx, final, train)
 
     def _build_plan_body(self, direction: str, B: int, device, has_ctx: bool, final: str, train: bool = False) -> dict:
@@ -1407,7 +1414,8 @@ class FlowEngine(PlanesPlanMixin):
         pk = self.pack(device)   # may invalidate plans
         key = (direction, B, str(device), has_ctx, final, self.use_fused_coupling, self.gemm_mode, self.fused_min_rows,
                config.tiny_coupling, config.get_lib("coupling_tiny", 1), train, self.use_planes, self.planes_min_rows, self._planes_fmt(), self.planes_min_rows_bf16x3,
-               (not train) and self._merge_on(direction), train and self.use_train_planes, train and self.train_planes_min_rows)
+               (not train) and self._merge_on(direction), train and self.use_train_planes, train and self.train_planes_min_rows,
+               has_ctx and (self.train_ctx_planes_min_rows if train else self.ctx_planes_min_rows))
         plan = self._plans.get(key)
         if plan is None:
             plan = self._build_plan(direction, B, device, has_ctx, final, train)
@@ -1428,6 +1436,10 @@ class FlowEngine(PlanesPlanMixin):
             self.f16_fallbacks += 1
             self._f16_overflow = True
             try:
+                if final.startswith("base") and not self._planes_ok(direction, B, context is not None, False):
+                    # the bf16x3 redo is no planes plan (a context on a conditioner bf16x3 does not run fused): nothing reduces
+                    # the base density in an epilogue there -- latent_base_sums hands the batch back to latent + the density pass
+                    return None
                 plan = self._plan(direction, B, x.device, context is not None, final)
                 self._run(plan, x, out, context)
             finally:
@@ -1466,9 +1478,7 @@ class FlowEngine(PlanesPlanMixin):
                 ws["out_static"] = torch.empty(B, self.D, dtype=torch.float32, device=x.device)
             os_ = ws["out_static"]
         if context is not None:
-            c = context.reshape(B).to(torch.float32)
-            ws["ctx4"][:, 0].copy_(c)
-            ws["ctx"].copy_(c)
+            self._fill_context(plan, context, B)
         g = plan.get("graph")
         if g is None:
             if plan.get("graph_warm", 0) < 1:
@@ -1488,14 +1498,23 @@ class FlowEngine(PlanesPlanMixin):
         if out is not None:
             out.copy_(os_)
 
+    @staticmethod
+    def _fill_context(plan, context, B: int):
+        """the context columns of the workspace: one value per row ([B] / [B, 1]), or ONE value spread over the rows (the plans'
+        launches read them with stride 1; stride 0 of usf_coupling_planes_ctx is for direct callers of the entry point)"""
+        ws = plan["ws"]
+        c = context.reshape(-1).to(torch.float32)
+        if c.numel() == 1 and B > 1:
+            c = c.expand(B)
+        ws["ctx4"][:, 0].copy_(c)
+        ws["ctx"].copy_(c)
+
     def _execute_plain(self, plan, x: torch.Tensor, out: Optional[torch.Tensor], context):
         ws = plan["ws"]
         B = x.shape[0]
         dev = x.device
         if context is not None:
-            c = context.reshape(B).to(torch.float32)
-            ws["ctx4"][:, 0].copy_(c)
-            ws["ctx"].copy_(c)
+            self._fill_context(plan, context, B)
         arr = plan["arr"]
         for idx, member, field in plan["patch_in"]:
             setattr(getattr(arr[idx].u, member), field, x.data_ptr())
@@ -1509,9 +1528,14 @@ class FlowEngine(PlanesPlanMixin):
             nonlocal pos
             if end > pos and self.op_timing is not None:
                 # instrumented mode: one launch per call, bracketed by HIP events on the launch stream
-                for j in range(pos, end):
+                j = pos
+                while j < end:
                     op = arr[j]
-                    if op.kind == _ext.OP_LINEAR:
+                    n_run = 2 if _ext.is_ctx_prefix(op) else 1       # (a context prefix and its coupling op are ONE launch)
+                    if n_run == 2:
+                        c_ = arr[j + 1].u.coupling_planes
+                        tag = ("coupling_planes_ctx", c_.M, 32 * c_.nk_t, 32 * c_.nk_p)
+                    elif op.kind == _ext.OP_LINEAR:
                         kind = "linear_bf16x3" if op.u.linear.W_split else "linear"
                         tag = (kind, op.u.linear.M, op.u.linear.N, op.u.linear.K)
                     elif op.kind == _ext.OP_GEMM_PLANES:
@@ -1527,9 +1551,10 @@ class FlowEngine(PlanesPlanMixin):
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record()
                     sub = C.cast(C.byref(arr, j * C.sizeof(_ext.Op)), C.POINTER(_ext.Op))
-                    _ext.check(lib.usf_run_ops(sub, 1, stream), "usf_run_ops")
+                    _ext.check(lib.usf_run_ops(sub, n_run, stream), "usf_run_ops")
                     e1.record()
                     self.op_timing.append((tag, e0, e1))
+                    j += n_run
                 self.launch_count += 1
                 pos = end
             elif end > pos:
@@ -1606,24 +1631,27 @@ class FlowEngine(PlanesPlanMixin):
         buf = plan["ws"][plan["out_buf"][0]]
         return buf, plan["out_buf"][2], plan["pk"]["ladj_total"]
 
-    def latent_base_sums(self, x: torch.Tensor, base: int, loc: torch.Tensor, scale: torch.Tensor):
+    def latent_base_sums(self, x: torch.Tensor, base: int, loc: torch.Tensor, scale: torch.Tensor, context=None):
         """backward pass with the Laplace / Normal base density reduced by the last GEMM's epilogue (planes plans, D <= 1024):
         (partial sums [B, 8], how many of the 8 are used, the flow's LogDet) -- ``usf_base_logprob_f32(USF_BASE_ROWSUM)`` finishes
         the rows; None when this batch does not take a planes plan (the caller runs ``latent`` + the density pass)."""
         from .config import config
         x = self._check_input(x)
         B = x.shape[0]
-        if not (config.base_in_epilogue and self.D <= 1024 and self._planes_ok("backward", B, False, False)):
+        has_ctx = context is not None
+        if not (config.base_in_epilogue and self.D <= 1024 and self._planes_ok("backward", B, has_ctx, False)):
             return None
-        if self.merge_affine == "auto":
+        if self.merge_affine == "auto" and not has_ctx:
             self.resolve_merge("backward", x)
         final = f"base{int(base)}"
-        plan = self._plan("backward", B, x.device, False, final)
+        plan = self._plan("backward", B, x.device, has_ctx, final)
         if plan.get("n_part", 0) < 1:
             return None
         ws = plan["ws"]
         _ext.base_tables(base, loc, scale, self.D, ws["btab"], ws["btab"].numel() // 3)
-        plan = self._run_guarded("backward", x, None, None, final)
+        plan = self._run_guarded("backward", x, None, context, final)
+        if plan is None:
+            return None
         return plan["ws"]["bpart"], plan["n_part"], plan["pk"]["ladj_total"]
 
     def ladj_total(self, device) -> float:

@@ -39,6 +39,8 @@ class PlanesPlanMixin:
     def _planes_ok(self, direction: str, B: int, has_ctx: bool, train: bool) -> bool:
         if self.use_planes is None:
             use = self.gemm_mode == "f16x2" or B >= self.planes_min_rows_bf16x3 or self._has_wide_conditioner()
+            if has_ctx:        # (off until measured: engine.py, ctx_planes_min_rows)
+                use = use and self.ctx_planes_min_rows is not None and B >= self.ctx_planes_min_rows
         else:
             use = bool(self.use_planes)
         if train:
@@ -47,9 +49,12 @@ class PlanesPlanMixin:
             # train_planes_min_rows rows; every planes buffer below 2 GiB (usf_wgrad_blocked_f32's offsets)
             use = (self.use_train_planes and direction == "backward" and self.gemm_mode == "bf16x3" and self.use_fused_coupling
                    and B >= max(self.train_planes_min_rows, self.fused_min_rows)
-                   and (-(-B // 16)) * (self.LDp // 32) * 3072 < 2 ** 31 and self._train_planes_conditioners_ok())
-        if (has_ctx or not use or self._general_cond or self.gemm_mode not in ("bf16x3", "f16x2")
+                   and (-(-B // 16)) * (self.LDp // 32) * 3072 < 2 ** 31 and self._train_planes_conditioners_ok()
+                   and (not has_ctx or (self.train_ctx_planes_min_rows is not None and B >= self.train_ctx_planes_min_rows)))
+        if (not use or self._general_cond or self.gemm_mode not in ("bf16x3", "f16x2")
                 or B < self.planes_min_rows or (-(-B // 16)) * (self.LDp // 32) * 3072 >= 2 ** 32):
+            return False
+        if has_ctx and not self._planes_ctx_ok(B):
             return False
         # (the structure check does not depend on which runs are merged: a merged run is an affine step like its parts)
         prims = self._primitive_ops(direction, merge=False)
@@ -62,6 +67,22 @@ class PlanesPlanMixin:
         body = [k_ for k_ in kinds if not k_.startswith("scale")]
         # the last layer must be an affine (it writes the fp32 result) and the chain needs at least two GEMM-sized ops
         return len(body) >= 2 and body[-1].startswith("affine")
+
+    def _planes_coupling_fused(self, h, B: int, fmt: int) -> bool:
+        """a coupling whose conditioner has the hidden widths h runs as ONE usf_coupling_planes launch in a planes plan of B rows"""
+        return (self.use_fused_coupling and B >= self.fused_min_rows and len(h) <= 3 and max(h) <= 256
+                and not (fmt == _ext.PLANES_BF16X3 and len(h) == 3))
+
+    def _planes_ctx_ok(self, B: int) -> bool:
+        """a context rides the planes pipeline only inside the fused coupling launch (usf_coupling_planes_ctx: a start value of
+        the first layer's accumulators): every conditioner WITH a context layer must run fused.  Otherwise -- bf16x3 with three
+        hidden layers, conditioners wider than 256, use_fused_coupling off -- the flow keeps the fp32-activation plan."""
+        fmt = self._planes_fmt()
+        for s_ in self.steps:
+            if s_.kind == "coupling" and isinstance(s_.module.conditioner, ConditionalDenseNN):
+                if not self._planes_coupling_fused([int(w) for w in s_.module.conditioner.hidden_dims], B, fmt):
+                    return False
+        return True
 
     def _train_planes_conditioners_ok(self) -> bool:
         # (the weight-gradient kernel carries the bias sums along only for operands of >= 64 columns -- usf_wgrad_planes_colsum_ok --:
@@ -189,7 +210,7 @@ class PlanesPlanMixin:
                                        lambda o, src=src, sel=sel_dev: o.copy_(self._perm_vec(src.double(), sel, pad)))
         return vecs[key]
 
-    def _build_plan_planes(self, direction: str, B: int, device, final: str, train: bool = False) -> dict:
+    def _build_plan_planes(self, direction: str, B: int, device, final: str, train: bool = False, has_ctx: bool = False) -> dict:
         """Launch list of the planes pipeline: pack -> (GEMM on planes)* -> GEMM with fp32 output.
 
         Every layer is the same kernel: an affine block one GEMM, an additive coupling the chain of its conditioner's
@@ -348,8 +369,8 @@ class PlanesPlanMixin:
             feat_t = torch.where((pos >= lo_t) & (pos < hi_t), segp, torch.full_like(segp, -1))
             layers = [raw["first"]] + list(raw["hidden"]) + [raw["last"]]
             h = list(raw["h"])
-            if (self.use_fused_coupling and B >= self.fused_min_rows and len(h) <= 3 and max(h) <= 256
-                    and not (fmt == _ext.PLANES_BF16X3 and len(h) == 3)):
+            use_ctx = bool(has_ctx and cp["has_ctx"])
+            if self._planes_coupling_fused(h, B, fmt):
                 # ONE launch per layer: usf_coupling_planes (hidden activations stay in registers; widths padded to 256)
                 def pad256(n_valid):
                     t = torch.full((256,), -1, dtype=torch.long)
@@ -374,21 +395,28 @@ class PlanesPlanMixin:
                 c.W_out, c.ldw_out, c.w_out_plane = Wo.data_ptr(), Wo.shape[2], Wo.shape[1] * Wo.shape[2]
                 c.b_out = self._planes_vec(pk, ("pl_coutb", i), layers[-1][1], out_sel).data_ptr()
                 c.sign, c.slope, c.act, c.format, c.range_flag = sign, cp["slope"], cp["act"], fmt, flag
+                if use_ctx:
+                    # ConditionalDenseNN's context layer (context_dim 1): the launch becomes usf_coupling_planes_ctx -- a prefix
+                    # op hands the coupling op behind it ws["ctx"] and layers[1]'s weight column / bias as 256-wide vectors
+                    Wc, bc = raw["ctx"]
+                    w_ctx = self._planes_vec(pk, ("pl_cctxw", i), Wc, pad256(h[0]))
+                    b_ctx = self._planes_vec(pk, ("pl_cctxb", i), bc, pad256(h[0]))
+                    ops.append(_ext.coupling_planes_ctx_prefix(ws["ctx"], 1, w_ctx, b_ctx))
                 if train:
                     # the lane-local splits of the hidden activations also go to planes buffers of the layer's own (8 blocks:
                     # 2 x B x 256 x 6 bytes per coupling): operands of the conditioner's weight gradients, gates of its backward
                     hnames = [f"pHs{j}_{i}" for j in range(len(h))]
                     for j, hn in enumerate(hnames):
                         c.hidden_out[j] = planes_buf(hn, 8).data_ptr()
-                    meta.append(dict(kind="coupling", op=len(ops), step=i, buf=znames[cur], sign=sign, use_ctx=False,
+                    meta.append(dict(kind="coupling", op=len(ops), step=i, buf=znames[cur], sign=sign, use_ctx=use_ctx,
                                      kb_p0=kb_p0, nk_p=kb_p1 - kb_p0, kb_t0=kb_t0, nk_t=kb_t1 - kb_t0, hidden_planes=hnames,
                                      feat_p=feat_p, feat_t=feat_t))
                 ops.append(op)
                 k += 1
                 continue
-            if train:
+            if train or use_ctx:
                 from .engine import EngineUnsupported
-                raise EngineUnsupported("training on the planes pipeline needs the fused coupling launch")
+                raise EngineUnsupported("training / a context on the planes pipeline needs the fused coupling launch")
             hbufs = [planes_buf("pH1", Hp // 32), planes_buf("pH2", Hp // 32)]
             src_buf, src_nkb, src_kb0, src_nk = z, nkb, kb_p0, kb_p1 - kb_p0
             in_sel = self._phys(feat_p[32 * kb_p0: 32 * kb_p1])
@@ -425,4 +453,5 @@ class PlanesPlanMixin:
             tn = (_ext.load().usf_gemm_planes_variant(arr[len(ops) - 1].u.gemm_planes) - 5000) // 10
             n_part = -(-self.D // (32 * tn))
         return dict(arr=arr, n=len(ops), patch_in=patch_in, patch_out=patch_out, side=[], final_gather=None, n_part=n_part,
-                    out_buf=out_buf, ws=ws, pk=pk, meta=meta, planes=True, planes_fmt=fmt, planes_train=bool(train))
+                    out_buf=out_buf, ws=ws, pk=pk, meta=meta, planes=True, planes_fmt=fmt, planes_train=bool(train),
+                    has_ctx=bool(has_ctx))

@@ -190,18 +190,28 @@ class Flow(LayerLoopMixin, FitMixin, torch.nn.Module):
         return info
 
     # ---- the hot path ----------------------------------------------------------------------
-    def _forward(self, x: torch.Tensor):
-        if self._on_device_fast_path(x):
-            return self.engine().transform(x, "forward")
+    @staticmethod
+    def _engine_context_ok(context, n: int, device) -> bool:
+        """contexts the device engine takes (context_dim 1): None, or a tensor [n], [n, 1] or of one element, on the device,
+        without grad"""
+        if context is None:
+            return True
+        if not (torch.is_tensor(context) and context.device == device and not context.requires_grad):
+            return False
+        return context.numel() == 1 or tuple(context.shape) in ((n,), (n, 1))
+
+    def _forward(self, x: torch.Tensor, context: Optional[torch.Tensor] = None):
+        if self._on_device_fast_path(x, context) and self._engine_context_ok(context, x.shape[0], x.device):
+            return self.engine().transform(x, "forward", context)
         for layer in self.layers:
-            x = layer.forward(x)
+            x = layer.forward(x, context=context) if context is not None else layer.forward(x)
         return x
 
-    def backward(self, x: torch.Tensor):
-        if self._on_device_fast_path(x):
-            return self.engine().transform(x, "backward")
+    def backward(self, x: torch.Tensor, context: Optional[torch.Tensor] = None):
+        if self._on_device_fast_path(x, context) and self._engine_context_ok(context, x.shape[0], x.device):
+            return self.engine().transform(x, "backward", context)
         for layer in reversed(self.layers):
-            x = layer.backward(x)
+            x = layer.backward(x, context=context) if context is not None else layer.backward(x)
         return x
 
     def _train_path(self, x: torch.Tensor, context=None):
@@ -277,10 +287,10 @@ class Flow(LayerLoopMixin, FitMixin, torch.nn.Module):
         if B == 0:
             return out
         info = self._base_info(x.device)
-        if info is not None and info[0] in ("laplace", "normal") and context is None:
+        if info is not None and info[0] in ("laplace", "normal"):
             # large batches on the planes pipeline: the base density is reduced in the last layer's epilogue (z is never stored)
             base = _ext.BASE_LAPLACE if info[0] == "laplace" else _ext.BASE_NORMAL
-            fused = eng.latent_base_sums(x, base, info[1], info[2])
+            fused = eng.latent_base_sums(x, base, info[1], info[2], context)
             if fused is not None:
                 part, n_part, logdet = fused
                 _ext.base_logprob(part, 8, B, n_part, _ext.BASE_ROWSUM, None, None, 0.0, out, sum_out, logdet_dev=logdet.neg_dev)
@@ -321,10 +331,12 @@ class Flow(LayerLoopMixin, FitMixin, torch.nn.Module):
         if sample_shape is None:
             sample_shape = [1]
         dev = self._param_device()
-        if dev.type == "cuda" and context is None and not _needs_grad(self) and self.engine() is not None:
+        shape = tuple(sample_shape)
+        n = int(np.prod(shape)) if len(shape) else 1
+        if dev.type == "cuda" and self._engine_context_ok(context, n, dev) and not _needs_grad(self) and self.engine() is not None:
+            # (with a context -- conditional generation, a soft-trained flow at a noise level: the same Philox / radial head,
+            # then the fused forward plan with the context)
             info = self._base_info(dev)
-            shape = tuple(sample_shape)
-            n = int(np.prod(shape)) if len(shape) else 1
             eng = self.engine()
             if info is not None and info[0] in ("laplace", "normal"):
                 if seed is None:
@@ -343,7 +355,7 @@ class Flow(LayerLoopMixin, FitMixin, torch.nn.Module):
                 _ext.radial_sample(z, eng.D, n, eng.D, base, info[1], r.contiguous(), seed, 0, row_offset)
             else:
                 z = self.base_distribution.sample(shape).to(dev).reshape(n, eng.D).float()
-            x = eng.transform(z, "forward")
+            x = eng.transform(z, "forward", context)
             return x.reshape(*shape, eng.D)
         y = None
         if dev.type == "cuda" and not _needs_grad(self) and self.engine() is None:

@@ -633,6 +633,15 @@ class TrainPath:
                     eng.planes_coupling_bwd(pk, m)
                 elif m is not first_meta:
                     eng.planes_dgrad_image(pk, m)
+        if any(m["kind"] == "coupling" and m["use_ctx"] for m in plan["meta"]):
+            # the context as a one-block planes buffer (column 0 = ctx, the rest zero), packed once per step: the operand of every
+            # context layer's weight gradient (usf_wgrad_blocked_f32 against the gradients at the first pre-activations)
+            key = ("ctx_col", str(dev))
+            if key not in self._inv:
+                t = torch.full((32,), -1, dtype=torch.int32)
+                t[0] = 0
+                self._inv[key] = t.to(dev)
+            _ext.pack_planes(ws["ctx"], self._planes_buf(ws, "pctx", B, 1), M=B, nkb=1, idx=self._inv[key], ld=1)
         self._defer = False
         # the reductions that end the weight gradients are queued (each with a workspace of its own) and leave as ONE launch behind
         # the layer loop, in front of the batched un-permute jobs that read their outputs (config.wreduce_jobs)
@@ -744,6 +753,16 @@ class TrainPath:
                            colsum=gb, cs_alpha=sign, **self._wq(ws, f"c{m['step']}i", B, h[0], n_p))
         self._scatter_weight(grads, first_l.weight, gW, None, h[0], self._seg_sel(m, "p", dev), eng.D)
         self._scatter_vec(grads, first_l.bias, gb, None, h[0])
+        if has_ctx and m["use_ctx"]:
+            # the context layer (layers[1], context_dim 1) adds ctx * W_ctx + b_ctx to the first pre-activation: d b_ctx is the
+            # column sum d b_in already holds, d W_ctx[h] = sign * sum_rows ctx[row] * d_h0[row, h] -- column 0 of the weight
+            # gradient against the context planes.  (A context layer that sees no context gets no gradient, as under autograd.)
+            ctx_l = lin[1]
+            self._scatter_vec(grads, ctx_l.bias, gb, None, h[0])
+            gWc = gimg("ctx")
+            _ext.wgrad_blocked(dh[0], 8, 0, ws["pctx"], 1, 0, gWc, M=B, N=h[0], K=32, ldg=gWc.shape[1], alpha=sign,
+                               **self._wq(ws, f"c{m['step']}c", B, h[0], 32))
+            self._scatter_weight(grads, ctx_l.weight, gWc, None, h[0], None, 1)
 
     def _prepare_images(self, plan, first_meta):
         """every weight image the backward reads (unfused conditioner layers, transposed images of the data-gradient
