@@ -31,16 +31,9 @@ from torch import nn
 from . import _ext
 from . import transforms as T
 from .config import config
+from ._plan_util import EngineUnsupported, _image_triple, _refreshed, _round_up, kperm  # noqa: F401  -- EngineUnsupported: re-exported
 from .networks import ConditionalDenseNN, ConvNet, DenseNN
 from .engine_planes import PlanesPlanMixin
-
-
-class EngineUnsupported(Exception):
-    """The layer list contains something the fused device path cannot express."""
-
-
-def _round_up(n: int, m: int) -> int:
-    return (n + m - 1) // m * m
 
 
 def _activation_of(f) -> Optional[Tuple[int, float]]:
@@ -61,6 +54,15 @@ def conditioner_supported(cond: nn.Module) -> bool:
     if isinstance(cond, ConvNet):        # vector path: plain chain of Linears, or GatedMLP / LayerNormVector blocks
         return cond.is_vector and _activation_of(cond.f) is not None     # (spatial path: image-shaped flows, the layer loop)
     return False
+
+
+def conditioner_layers(cond: nn.Module):
+    """(first, context layer | None, hidden layers, last) of a DenseNN's / ConditionalDenseNN's ``layers``: the context
+    layer (context_dim 1) sits behind the first"""
+    lin = list(cond.layers)
+    if isinstance(cond, ConditionalDenseNN):
+        return lin[0], lin[1], lin[2:-1], lin[-1]
+    return lin[0], None, lin[1:-1], lin[-1]
 
 
 @dataclass
@@ -150,13 +152,6 @@ class LogDet:
 
 
 _PERM_CONST: dict = {}      # FlowEngine._perm_vec: constants of a (layout index, padding) pair
-
-
-def _refreshed(shape, dtype, device, fn) -> torch.Tensor:
-    """persistent tensor filled by fn(out) now and again on every replay of the pack tape"""
-    out = torch.empty(shape, dtype=dtype, device=device)
-    _ext.host_op(lambda: fn(out))
-    return out
 
 
 def prepare_affine_blocks(blocks: Sequence[nn.Module], device=None, keep_factors: bool = False) -> Dict[int, dict]:
@@ -520,7 +515,7 @@ class FlowEngine(PlanesPlanMixin):
 
     def _pack_coupling(self, i: int, layer, device) -> dict:
         """Static description of one coupling layer + handles to its raw conditioner parameters; the weight images
-        themselves (unfused: ``_unfused_pack``, fused: ``_fused_pack`` / ``_fused_split``) are built on first use
+        themselves (unfused: ``_unfused_pack``, fused: ``_fused_pack`` / ``_fused_pack_bwd``) are built on first use
         by ``usf_pack_weight_f32`` launches (mask-aware column / row selection, zero padding, bf16x3 planes)."""
         cond = layer.conditioner
         flip = self._flip[i]
@@ -533,7 +528,6 @@ class FlowEngine(PlanesPlanMixin):
             tr_off, tr_n, tr_idx = self.n0a, self.n1, self.seg_idx[self.n0a: self.n0a + self.n1]
         act, slope = _activation_of(cond.f)
         has_ctx = isinstance(cond, ConditionalDenseNN)
-        ctx_l = None
         if isinstance(cond, ConvNet) and not cond.is_plain_mlp():
             # Linear, [GatedMLP | (f, Linear)] [+ LayerNormVector] x n, Linear (networks.py:287-308)
             first, blocks, final = cond.block_view()
@@ -551,11 +545,8 @@ class FlowEngine(PlanesPlanMixin):
             first, hidden, (W_last, b_last), widths = cond.mlp_view()
             W_last, b_last = W_last.to(device).contiguous(), b_last.to(device).contiguous()
         else:
-            lin = list(cond.layers)
-            first = lin[0]
-            ctx_l = lin[1] if has_ctx else None
-            hidden = lin[2:-1] if has_ctx else lin[1:-1]
-            W_last, b_last = _param(lin[-1].weight, device), _param(lin[-1].bias, device)
+            first, ctx_l, hidden, last = conditioner_layers(cond)
+            W_last, b_last = _param(last.weight, device), _param(last.bias, device)
             widths = cond.hidden_dims
         h = [int(x) for x in widths]
         hp = [_round_up(x, 4) for x in h]
@@ -1255,158 +1246,102 @@ class FlowEngine(PlanesPlanMixin):
 
     def _fused_pack(self, cp) -> dict:
         """weights re-laid out for the fused kernel's padding contract (include/usflows_hip.h)"""
-        lib = _ext.load()
-        raw = cp["raw"]
-        dev, h = raw["device"], raw["h"]
-        Hp = lib.usf_coupling_padded_width(max(cp["hidden"]))
-        Kp = _round_up(cp["pass_n"], 32)
-        Np = _round_up(cp["tr_n"], 32)
+        Hp = _ext.load().usf_coupling_padded_width(max(cp["hidden"]))
         split = self.gemm_mode in ("bf16x3", "f16x2") and Hp == 256
         if "fused" in cp and (not split or "split" in cp["fused"]):
             return cp["fused"]
         with self._pk_record(self._pack):
-            return self._fused_pack_build(cp, Hp, Kp, Np, split)
-
-    def _fused_pack_build(self, cp, Hp, Kp, Np, split) -> dict:
-        raw = cp["raw"]
-        dev, h = raw["device"], raw["h"]
-        pass_sel = self._sel(raw["pass_idx"], Kp, dev)
-        tr_sel = self._sel(raw["tr_idx"], Np, dev)
-        s3 = dict(hid=[]) if split else None
-        # hidden (K) axes of the split hidden / output planes in the accumulator order of the kernel
-        perm_sel = {}
-
-        def kperm(n_valid):
-            if n_valid not in perm_sel:
-                g, j = torch.arange(4)[:, None], torch.arange(8)[None, :]
-                within = torch.where(j < 4, 4 * g + j, 16 + 4 * g + (j - 4)).reshape(-1)          # [32]
-                perm = (torch.arange(0, Hp, 32)[:, None] + within[None, :]).reshape(-1)
-                perm = torch.where(perm < n_valid, perm, torch.full_like(perm, -1))
-                perm_sel[n_valid] = perm.to(device=dev, dtype=torch.int32)
-            return perm_sel[n_valid]
-
-        W, b = raw["first"]
-        rows0 = self._iarange(h[0], Hp, dev)
-        W_in, P = self._packed(W, rows0, Hp, pass_sel, Kp, planes_ld=Kp if split else 0)
-        if split:
-            s3["in"] = P
-        f = dict(Hp=Hp, W_in=W_in, b_in=self._packed_vec(b, rows0, Hp), hid=[])
-        for j, (W, b) in enumerate(raw["hidden"]):
-            rows = self._iarange(h[j + 1], Hp, dev)
-            Wp, P = self._packed(W, rows, Hp, self._iarange(h[j], Hp, dev), Hp,
-                                 planes_sel=kperm(h[j]) if split else None, planes_ld=Hp if split else 0)
-            f["hid"].append((Wp, self._packed_vec(b, rows, Hp)))
-            if split:
-                s3["hid"].append(P)
-        W, b = raw["last"]
-        f["W_out"], P = self._packed(W, tr_sel, Np, self._iarange(h[-1], Hp, dev), Hp,
-                                     planes_sel=kperm(h[-1]) if split else None, planes_ld=Hp if split else 0)
-        f["b_out"] = self._packed_vec(b, tr_sel, Np)
-        if split:
-            s3["out"] = P
-            f["split"] = s3
-        if cp["has_ctx"]:
-            Wc, bc = raw["ctx"]
-            f["W_ctx"] = self._packed_vec(Wc, rows0, Hp)        # layers[1].weight is [h0, 1]: one column
-            f["b_ctx"] = self._packed_vec(bc, rows0, Hp)
-        cp["fused"] = f
-        return f
+            cp["fused"] = self._fused_images(cp, Hp, split)
+        return cp["fused"]
 
     def _fused_pack_bwd(self, pk, cp) -> dict:
         """the conditioner's weights transposed and re-laid out for the fused kernel run BACKWARDS (usf_coupling_desc::gate):
         W_in = W_last^T [hidden, trans], hidden matrices reversed and transposed, W_out = W_first^T [pass, hidden], zero biases"""
-        if "fused_bwd" in cp:
-            return cp["fused_bwd"]
-        lib = _ext.load()
+        if "fused_bwd" not in cp:
+            Hp = _ext.load().usf_coupling_padded_width(max(cp["hidden"]))
+            with self._pk_record(pk):
+                cp["fused_bwd"] = self._fused_images(cp, Hp, True, backward=True)
+        return cp["fused_bwd"]
+
+    def _fused_images(self, cp, Hp: int, split: bool, backward: bool = False) -> dict:
+        """the fused kernel's image set in one direction: W_in / hid [(W, b)] / W_out with their biases (backward: one shared zero
+        vector, and the roles of the column segments swap), and with ``split`` the bf16x3 planes of every matrix"""
         raw = cp["raw"]
         dev, h = raw["device"], raw["h"]
-        Hp = lib.usf_coupling_padded_width(max(cp["hidden"]))
-        Kp, Np = _round_up(cp["tr_n"], 32), _round_up(cp["pass_n"], 32)      # the roles of the column segments swap
-        tr_sel, pass_sel = self._sel(raw["tr_idx"], Kp, dev), self._sel(raw["pass_idx"], Np, dev)
-
-        def kperm(n_valid):
-            g, j = torch.arange(4)[:, None], torch.arange(8)[None, :]
-            within = torch.where(j < 4, 4 * g + j, 16 + 4 * g + (j - 4)).reshape(-1)
-            perm = (torch.arange(0, Hp, 32)[:, None] + within[None, :]).reshape(-1)
-            return torch.where(perm < n_valid, perm, torch.full_like(perm, -1)).to(device=dev, dtype=torch.int32)
-
-        with self._pk_record(pk):
-            zeros = torch.zeros(max(Hp, Np), dtype=torch.float32, device=dev)
-            W, _b = raw["last"]                                   # [features, h_last]
-            W_in, P_in = self._packed(W, self._iarange(h[-1], Hp, dev), Hp, tr_sel, Kp, planes_ld=Kp, transpose=True)
-            f = dict(Hp=Hp, W_in=W_in, zeros=zeros, hid=[], split=dict(hid=[]))
-            f["split"]["in"] = P_in
-            for j in range(len(raw["hidden"]) - 1, -1, -1):       # hidden matrix j maps layer j -> j + 1: backwards j + 1 -> j
-                W, _b = raw["hidden"][j]                          # [h_{j+1}, h_j]
-                Wp, P = self._packed(W, self._iarange(h[j], Hp, dev), Hp, self._iarange(h[j + 1], Hp, dev), Hp,
-                                     planes_sel=kperm(h[j + 1]), planes_ld=Hp, transpose=True)
-                f["hid"].append(Wp)
-                f["split"]["hid"].append(P)
-            W, _b = raw["first"]                                  # [h_0, features]
-            f["W_out"], f["split"]["out"] = self._packed(W, pass_sel, Np, self._iarange(h[0], Hp, dev), Hp,
-                                                         planes_sel=kperm(h[0]), planes_ld=Hp, transpose=True)
-        cp["fused_bwd"] = f
+        layers = [raw["first"]] + list(raw["hidden"]) + [raw["last"]]
+        n = len(layers)
+        # the index set (and its padded width) at both ends of every layer: layer j maps ends[j] -> ends[j + 1]
+        wid = [_round_up(cp["pass_n"], 32)] + [Hp] * len(h) + [_round_up(cp["tr_n"], 32)]
+        ends = ([self._sel(raw["pass_idx"], wid[0], dev)] + [self._iarange(w, Hp, dev) for w in h]
+                + [self._sel(raw["tr_idx"], wid[-1], dev)])
+        zeros = torch.zeros(max(Hp, wid[0]), dtype=torch.float32, device=dev) if backward else None
+        mats, planes, vecs = [], [], []
+        for at, j in enumerate(reversed(range(n)) if backward else range(n)):
+            o, k = (j, j + 1) if backward else (j + 1, j)           # the ends on the image's rows / on its K axis
+            # hidden (K) axes of the split hidden / output planes in the accumulator order of the kernel
+            psel = kperm(h[k - 1], Hp, dev) if (split and at > 0) else None
+            W, P = self._packed(layers[j][0], ends[o], wid[o], ends[k], wid[k], planes_sel=psel, planes_ld=wid[k] if split else 0,
+                                transpose=backward)
+            mats.append(W)
+            planes.append(P)
+            vecs.append(zeros if backward else self._packed_vec(layers[j][1], ends[o], wid[o]))
+        f = dict(Hp=Hp, W_in=mats[0], b_in=vecs[0], hid=list(zip(mats[1:-1], vecs[1:-1])), W_out=mats[-1], b_out=vecs[-1])
+        if split:
+            f["split"] = dict(hid=planes[1:-1])
+            f["split"]["in"], f["split"]["out"] = planes[0], planes[-1]
+        if backward:
+            f["zeros"] = zeros
+        elif cp["has_ctx"]:
+            Wc, bc = raw["ctx"]
+            f["W_ctx"] = self._packed_vec(Wc, ends[1], Hp)        # layers[1].weight is [h0, 1]: one column
+            f["b_ctx"] = self._packed_vec(bc, ends[1], Hp)
         return f
 
-    def coupling_backward_op(self, pk, cp, gptr, ld, B, sign, gates, d_out, act=_ext.ACT_GATE) -> _ext.Op:
-        """ONE launch for the data-gradient chain of a coupling layer's conditioner: g[:, pass] += sign * MLP^T(g[:, trans]) with
-        the (Leaky)ReLU backward from the saved activations `gates` (layer order of the forward); d_out[l] receives the gradient
-        at hidden activation l (forward order)"""
-        f = self._fused_pack_bwd(pk, cp)
-        nl = len(cp["hidden"])
+    def _fused_op(self, cp, f, zptr, ld, B, sign, act, backward: bool = False, split: bool = True) -> _ext.Op:
+        """the ``coupling`` descriptor on the image set f (_fused_images), in place on the rows at zptr: segments and hidden
+        widths (backward: swapped / reversed), the plain weight fields and, with ``split``, the split-plane ones"""
         op = _ext.Op()
         op.kind = _ext.OP_COUPLING
         d = op.u.coupling
-        d.z, d.ldz, d.out, d.ldo, d.M = gptr, ld, gptr, ld, B
-        d.off_pass, d.n_pass, d.off_trans, d.n_trans = cp["tr_off"], cp["tr_n"], cp["pass_off"], cp["pass_n"]
-        d.n_hidden = nl
-        for j in range(nl):
-            d.hidden[j] = cp["hidden"][nl - 1 - j]
-            d.gate[j] = gates[nl - 1 - j].data_ptr()
-            d.hidden_out[j] = d_out[nl - 1 - j].data_ptr()
-        d.ld_gate = gates[0].shape[1]
-        d.ld_hidden_out = d_out[0].shape[1]
-        z = f["zeros"].data_ptr()
-        d.W_in, d.ldw_in, d.b_in = f["W_in"].data_ptr(), f["W_in"].shape[1], z
-        for j, W in enumerate(f["hid"]):
-            d.W_hid[j], d.b_hid[j], d.ldw_hid[j] = W.data_ptr(), z, W.shape[1]
-        d.W_out, d.ldw_out, d.b_out = f["W_out"].data_ptr(), f["W_out"].shape[1], z
-        d.sign, d.slope, d.act = sign, cp["slope"], act
-        s3 = f["split"]
-        d.split_in, d.split_in_ld, d.split_in_plane = s3["in"].data_ptr(), s3["in"].shape[2], s3["in"].shape[1] * s3["in"].shape[2]
-        for j, P in enumerate(s3["hid"]):
-            d.split_hid[j] = P.data_ptr()
-        if s3["hid"]:
-            d.split_hid_ld, d.split_hid_plane = s3["hid"][0].shape[2], s3["hid"][0].shape[1] * s3["hid"][0].shape[2]
-        d.split_out, d.split_out_ld, d.split_out_plane = s3["out"].data_ptr(), s3["out"].shape[2], s3["out"].shape[1] * s3["out"].shape[2]
-        return op
-
-    def _coupling_op(self, cp, zptr, B, sign, ws_ctx) -> _ext.Op:
-        f = self._fused_pack(cp)
-        op = _ext.Op()
-        op.kind = _ext.OP_COUPLING
-        d = op.u.coupling
-        d.z, d.ldz, d.out, d.ldo, d.M = zptr, self.LD, zptr, self.LD, B
-        d.off_pass, d.n_pass, d.off_trans, d.n_trans = cp["pass_off"], cp["pass_n"], cp["tr_off"], cp["tr_n"]
-        d.n_hidden = len(cp["hidden"])
-        for j, hh in enumerate(cp["hidden"]):
+        d.z, d.ldz, d.out, d.ldo, d.M = zptr, ld, zptr, ld, B
+        seg_p, seg_t = (cp["pass_off"], cp["pass_n"]), (cp["tr_off"], cp["tr_n"])
+        (d.off_pass, d.n_pass), (d.off_trans, d.n_trans) = (seg_t, seg_p) if backward else (seg_p, seg_t)
+        hidden = cp["hidden"][::-1] if backward else cp["hidden"]
+        d.n_hidden = len(hidden)
+        for j, hh in enumerate(hidden):
             d.hidden[j] = hh
         d.W_in, d.ldw_in, d.b_in = f["W_in"].data_ptr(), f["W_in"].shape[1], f["b_in"].data_ptr()
         for j, (W, b) in enumerate(f["hid"]):
             d.W_hid[j], d.b_hid[j], d.ldw_hid[j] = W.data_ptr(), b.data_ptr(), W.shape[1]
         d.W_out, d.ldw_out, d.b_out = f["W_out"].data_ptr(), f["W_out"].shape[1], f["b_out"].data_ptr()
+        d.sign, d.slope, d.act = sign, cp["slope"], act
+        if split:
+            s3 = f["split"]
+            d.split_in, d.split_in_ld, d.split_in_plane = _image_triple(s3["in"])
+            for j, P in enumerate(s3["hid"]):
+                d.split_hid[j], d.split_hid_ld, d.split_hid_plane = _image_triple(P)
+            d.split_out, d.split_out_ld, d.split_out_plane = _image_triple(s3["out"])
+        return op
+
+    def coupling_backward_op(self, pk, cp, gptr, ld, B, sign, gates, d_out, act=_ext.ACT_GATE) -> _ext.Op:
+        """ONE launch for the data-gradient chain of a coupling layer's conditioner: g[:, pass] += sign * MLP^T(g[:, trans]) with
+        the (Leaky)ReLU backward from the saved activations `gates` (layer order of the forward); d_out[l] receives the gradient
+        at hidden activation l (forward order)"""
+        op = self._fused_op(cp, self._fused_pack_bwd(pk, cp), gptr, ld, B, sign, act, backward=True)
+        d = op.u.coupling
+        for j, (gt, do) in enumerate(zip(gates[::-1], d_out[::-1])):
+            d.gate[j], d.hidden_out[j] = gt.data_ptr(), do.data_ptr()
+        d.ld_gate, d.ld_hidden_out = gates[0].shape[1], d_out[0].shape[1]
+        return op
+
+    def _coupling_op(self, cp, zptr, B, sign, ws_ctx) -> _ext.Op:
+        f = self._fused_pack(cp)
+        op = self._fused_op(cp, f, zptr, self.LD, B, sign, cp["act"],
+                            split=self.gemm_mode in ("bf16x3", "f16x2") and "split" in f)
         if ws_ctx is not None:
+            d = op.u.coupling
             d.context = ws_ctx["ctx"].data_ptr()
             d.W_ctx, d.b_ctx = f["W_ctx"].data_ptr(), f["b_ctx"].data_ptr()
-        d.sign, d.slope, d.act = sign, cp["slope"], cp["act"]
-        if self.gemm_mode in ("bf16x3", "f16x2") and "split" in f:
-            s3 = f["split"]
-            d.split_in, d.split_in_ld, d.split_in_plane = s3["in"].data_ptr(), s3["in"].shape[2], s3["in"].shape[1] * s3["in"].shape[2]
-            for j, P in enumerate(s3["hid"]):
-                d.split_hid[j] = P.data_ptr()
-            if s3["hid"]:
-                d.split_hid_ld, d.split_hid_plane = s3["hid"][0].shape[2], s3["hid"][0].shape[1] * s3["hid"][0].shape[2]
-            d.split_out, d.split_out_ld, d.split_out_plane = s3["out"].data_ptr(), s3["out"].shape[2], s3["out"].shape[1] * s3["out"].shape[2]
         return op
 
     # ---- execution ----------------------------------------------------------------------------

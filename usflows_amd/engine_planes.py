@@ -9,11 +9,8 @@ from typing import List
 import torch
 
 from . import _ext
+from ._plan_util import EngineUnsupported, _image_triple, _refreshed, _round_up, arange_padded
 from .networks import ConditionalDenseNN, ConvNet, DenseNN
-
-
-def _round_up(n: int, m: int) -> int:
-    return (n + m - 1) // m * m
 
 
 class PlanesPlanMixin:
@@ -126,72 +123,6 @@ class PlanesPlanMixin:
             mats[key] = P
         return mats[key]
 
-    # ---- training on the planes pipeline: the backward launches' weight images (training.py `_backward_body_planes`) ----
-    def planes_dgrad_image(self, pk, m) -> torch.Tensor:
-        """weight planes of an affine layer's data gradient g_in = g_out W as a usf_gemm_planes_bf16x3 operand: rows = the
-        positions of the layer's INPUT layout (segp), K axis = the slots of its OUTPUT layout"""
-        blk = m["blk"]
-        which = "Minv" if m["prim"] == "affine_bwd" else "M"
-        out_phys = self._phys(self.natp_idx if m["out_layout"] == "natp" else self.segp_idx)
-        return self._planes_image(pk, ("pl_aff_t", id(blk), which, m["out_layout"]), self._affine_entry(pk, blk)[which],
-                                  self.segp_idx, out_phys, _ext.PLANES_BF16X3, transpose=True)
-
-    def planes_coupling_bwd(self, pk, m) -> dict:
-        """the conditioner's weights for usf_coupling_planes run BACKWARDS (USF_ACT_GATE): W_in = W_last^T [256, slots of the
-        transformed blocks], hidden matrices reversed and transposed, W_out = W_first^T [positions of the conditioning blocks,
-        256], zero biases"""
-        i = m["step"]
-        cp = pk["coupling"][i]
-        if "planes_bwd" in cp:
-            return cp["planes_bwd"]
-        raw = cp["raw"]
-        h = list(raw["h"])
-        layers = [raw["first"]] + list(raw["hidden"]) + [raw["last"]]
-        fmt = _ext.PLANES_BF16X3
-
-        def pad256(n_valid):
-            t = torch.full((256,), -1, dtype=torch.long)
-            t[:n_valid] = torch.arange(n_valid)
-            return t
-        ft = m["feat_t"][32 * m["kb_t0"]: 32 * (m["kb_t0"] + m["nk_t"])]
-        fp = m["feat_p"][32 * m["kb_p0"]: 32 * (m["kb_p0"] + m["nk_p"])]
-        dev = raw["device"]
-        f = dict(zeros=torch.zeros(max(256, int(fp.numel())), dtype=torch.float32, device=dev), hid=[])
-        f["W_in"] = self._planes_image(pk, ("pl_cin_t", i), layers[-1][0], pad256(h[-1]), self._phys(ft), fmt, transpose=True)
-        for j in range(len(h) - 1, 0, -1):        # forward hidden matrix j maps layer j - 1 -> j: backwards j -> j - 1
-            f["hid"].append(self._planes_image(pk, ("pl_chid_t", i, j), layers[j][0], pad256(h[j - 1]), self._phys(pad256(h[j])),
-                                               fmt, transpose=True))
-        f["W_out"] = self._planes_image(pk, ("pl_cout_t", i), layers[0][0], fp, self._phys(pad256(h[0])), fmt, transpose=True)
-        cp["planes_bwd"] = f
-        return f
-
-    def planes_coupling_bwd_op(self, pk, m, g, g_nkb: int, B: int, gates, d_out) -> _ext.Op:
-        """ONE launch for the data-gradient chain of a coupling layer's conditioner on the gradient planes buffer g:
-        g[:, conditioning blocks] += sign * MLP^T(g[:, transformed blocks]); gates / d_out: planes buffers (8 blocks per panel)
-        in the FORWARD's layer order -- the saved activations resp. the gradients at the pre-activations"""
-        cp = pk["coupling"][m["step"]]
-        f = self.planes_coupling_bwd(pk, m)
-        nl = len(cp["hidden"])
-        op = _ext.Op()
-        op.kind = _ext.OP_COUPLING_PLANES
-        c = op.u.coupling_planes
-        c.z, c.z_nkb, c.M = g.data_ptr(), g_nkb, B
-        c.kb_p0, c.nk_p, c.kb_t0, c.nk_t = m["kb_t0"], m["nk_t"], m["kb_p0"], m["nk_p"]      # the roles of the block ranges swap
-        c.n_hidden, c.hidden_padded = nl, 256
-        z = f["zeros"].data_ptr()
-        Wi = f["W_in"]
-        c.W_in, c.ldw_in, c.w_in_plane, c.b_in = Wi.data_ptr(), Wi.shape[2], Wi.shape[1] * Wi.shape[2], z
-        for j, Wh in enumerate(f["hid"]):
-            c.W_hid[j], c.b_hid[j] = Wh.data_ptr(), z
-            c.ldw_hid, c.w_hid_plane = Wh.shape[2], Wh.shape[1] * Wh.shape[2]
-        Wo = f["W_out"]
-        c.W_out, c.ldw_out, c.w_out_plane, c.b_out = Wo.data_ptr(), Wo.shape[2], Wo.shape[1] * Wo.shape[2], z
-        c.sign, c.slope, c.act, c.format, c.range_flag = m["sign"], cp["slope"], _ext.ACT_GATE, _ext.PLANES_BF16X3, 0
-        for l in range(nl):
-            c.gate[l] = gates[nl - 1 - l].data_ptr()
-            c.hidden_out[l] = d_out[nl - 1 - l].data_ptr()
-        return op
-
     def _planes_vec(self, pk, key, src, sel: torch.Tensor, pad: float = 0.0) -> torch.Tensor:
         """cached fp32 vector src[sel] (-1: pad) of length len(sel)"""
         vecs = pk["vecs"]
@@ -205,10 +136,78 @@ class PlanesPlanMixin:
                 vecs[key] = out
             else:
                 sel_dev = sel.to(dev)                    # (once: a host index in the refresh would synchronise every step)
-                from .engine import _refreshed                    # (engine imports this module: late import)
                 vecs[key] = _refreshed((n,), torch.float32, dev,
                                        lambda o, src=src, sel=sel_dev: o.copy_(self._perm_vec(src.double(), sel, pad)))
         return vecs[key]
+
+    # ---- a coupling on planes: its block ranges, its weight images (both directions), its descriptor --------------------
+    def _coupling_geometry(self, cp) -> dict:
+        """where a coupling layer lives in a planes buffer of the segment layout: the block ranges of its conditioning (p) and
+        transformed (t) features, their valid widths relative to the range's first block, and the feature number of every
+        position of the buffer that belongs to either set (-1 elsewhere).  Goes into the coupling's ``meta`` entry as it is."""
+        segp = self.segp_idx
+        lo_p, hi_p = cp["pass_off"], cp["pass_off"] + int((cp["raw"]["pass_idx"] >= 0).sum())
+        lo_t, hi_t = cp["tr_off"], cp["tr_off"] + cp["tr_n"]
+        kb_p0, kb_t0 = lo_p // 32, lo_t // 32
+        pos = torch.arange(self.LDp)
+        none = torch.full_like(segp, -1)
+        return dict(kb_p0=kb_p0, nk_p=-(-hi_p // 32) - kb_p0, kb_t0=kb_t0, nk_t=-(-hi_t // 32) - kb_t0,
+                    n_p=hi_p - 32 * kb_p0, n_t=hi_t - 32 * kb_t0,
+                    feat_p=torch.where((pos >= lo_p) & (pos < hi_p), segp, none),
+                    feat_t=torch.where((pos >= lo_t) & (pos < hi_t), segp, none))
+
+    def _coupling_planes_images(self, pk, i: int, geo: dict, fmt: int, backward: bool = False) -> dict:
+        """the weight images of usf_coupling_planes for coupling step i (hidden widths padded to 256, K axes in slot order).
+        Forward: the conditioner's layers in order with their bias vectors.  backward (USF_ACT_GATE): the same chain run from
+        the transformed blocks to the conditioning blocks -- W_in = W_last^T, the hidden matrices reversed and transposed,
+        W_out = W_first^T -- with one shared zero vector for every bias."""
+        raw = pk["coupling"][i]["raw"]
+        h = list(raw["h"])
+        layers = [raw["first"]] + list(raw["hidden"]) + [raw["last"]]
+        # the index set at both ends of every layer: layer j maps ends[j] -> ends[j + 1]
+        ends = ([geo["feat_p"][32 * geo["kb_p0"]: 32 * (geo["kb_p0"] + geo["nk_p"])]] + [arange_padded(w, 256) for w in h]
+                + [geo["feat_t"][32 * geo["kb_t0"]: 32 * (geo["kb_t0"] + geo["nk_t"])]])
+        n = len(layers)
+        mats, vecs = [], []
+        if backward:
+            zeros = torch.zeros(max(256, int(ends[0].numel())), dtype=torch.float32, device=raw["device"])
+        for at, j in enumerate(reversed(range(n)) if backward else range(n)):
+            role = "in" if at == 0 else ("out" if at == n - 1 else "hid")         # (the cache keys name the role in the launch)
+            jkey = (i, j) if role == "hid" else (i,)
+            out_sel, in_sel = (ends[j], ends[j + 1]) if backward else (ends[j + 1], ends[j])
+            mats.append(self._planes_image(pk, (f"pl_c{role}_t" if backward else f"pl_c{role}",) + jkey, layers[j][0], out_sel,
+                                           self._phys(in_sel), fmt, transpose=backward))
+            vecs.append(zeros if backward else self._planes_vec(pk, (f"pl_c{role}b",) + jkey, layers[j][1], out_sel))
+        f = dict(W_in=mats[0], hid=mats[1:-1], W_out=mats[-1], b_in=vecs[0], b_hid=vecs[1:-1], b_out=vecs[-1])
+        if backward:
+            f["zeros"] = zeros
+        return f
+
+    # ---- training on the planes pipeline: the backward launches' weight images (training.py `_backward_body_planes`) ----
+    def planes_dgrad_image(self, pk, m) -> torch.Tensor:
+        """weight planes of an affine layer's data gradient g_in = g_out W as a usf_gemm_planes_bf16x3 operand: rows = the
+        positions of the layer's INPUT layout (segp), K axis = the slots of its OUTPUT layout"""
+        blk = m["blk"]
+        which = "Minv" if m["prim"] == "affine_bwd" else "M"
+        out_phys = self._phys(self.natp_idx if m["out_layout"] == "natp" else self.segp_idx)
+        return self._planes_image(pk, ("pl_aff_t", id(blk), which, m["out_layout"]), self._affine_entry(pk, blk)[which],
+                                  self.segp_idx, out_phys, _ext.PLANES_BF16X3, transpose=True)
+
+    def planes_coupling_bwd(self, pk, m) -> dict:
+        """the backward image set of the coupling whose ``meta`` entry is m (_coupling_planes_images), kept with the layer"""
+        cp = pk["coupling"][m["step"]]
+        if "planes_bwd" not in cp:
+            cp["planes_bwd"] = self._coupling_planes_images(pk, m["step"], m, _ext.PLANES_BF16X3, backward=True)
+        return cp["planes_bwd"]
+
+    def planes_coupling_bwd_op(self, pk, m, g, g_nkb: int, B: int, gates, d_out) -> _ext.Op:
+        """ONE launch for the data-gradient chain of a coupling layer's conditioner on the gradient planes buffer g:
+        g[:, conditioning blocks] += sign * MLP^T(g[:, transformed blocks]); gates / d_out: planes buffers (8 blocks per panel)
+        in the FORWARD's layer order -- the saved activations resp. the gradients at the pre-activations"""
+        cp = pk["coupling"][m["step"]]
+        return coupling_planes_op(g, g_nkb, B, (m["kb_t0"], m["nk_t"], m["kb_p0"], m["nk_p"]),      # the roles of the block ranges swap
+                                  self.planes_coupling_bwd(pk, m), m["sign"], cp["slope"], _ext.ACT_GATE, _ext.PLANES_BF16X3, 0,
+                                  gate=gates[::-1], hidden_out=d_out[::-1])
 
     def _build_plan_planes(self, direction: str, B: int, device, final: str, train: bool = False, has_ctx: bool = False) -> dict:
         """Launch list of the planes pipeline: pack -> (GEMM on planes)* -> GEMM with fp32 output.
@@ -219,239 +218,251 @@ class PlanesPlanMixin:
         buffer z keeps the engine's segment layout [mask==0 | mask==1] padded to whole 32-feature blocks; a coupling
         reads the blocks that hold its conditioning features (zero weights on the others) and rewrites the blocks
         that hold its transformed features (zero rows elsewhere: those values are rewritten unchanged)."""
-        pk = self.pack(device)
-        ws = self._workspace(B, device)
-        prims = self._primitive_ops(direction, merge=not train)     # (the training backward needs every block's own launch)
-        npan = -(-B // 16)
-        nkb = self.LDp // 32
-        segp, natp = self.segp_idx, self.natp_idx
-        seg_phys = self._phys(segp)
-        Hp = _round_up(self.hmax, 32)
-        fmt = self._planes_fmt()
-        chunk = 2048 if fmt == _ext.PLANES_F16X2 else 3072        # bytes per (panel, block): NPL planes of 1 KiB
+        p = _PlanesPlan(self, direction, B, device, final, train, has_ctx)
+        k = p.head()
+        while k < len(p.prims):
+            prim, i = p.prims[k]
+            k += p.affine(k, prim, i) if prim in ("affine_fwd", "affine_bwd") else p.coupling(prim, i)
+        return p.result()
+
+
+def coupling_planes_op(z, z_nkb: int, B: int, ranges, f: dict, sign, slope, act, fmt, flag, gate=(), hidden_out=()) -> _ext.Op:
+    """THE filler of the ``coupling_planes`` descriptor: the planes buffer z (z_nkb blocks per panel, B rows), the block ranges
+    (kb_p0, nk_p, kb_t0, nk_t), an image set f (PlanesPlanMixin._coupling_planes_images), and per hidden layer the optional
+    planes buffers of the gates (USF_ACT_GATE) / the hidden side outputs"""
+    op = _ext.Op()
+    op.kind = _ext.OP_COUPLING_PLANES
+    c = op.u.coupling_planes
+    c.z, c.z_nkb, c.M = z.data_ptr(), z_nkb, B
+    c.kb_p0, c.nk_p, c.kb_t0, c.nk_t = ranges
+    c.n_hidden, c.hidden_padded = len(f["hid"]) + 1, 256
+    c.W_in, c.ldw_in, c.w_in_plane = _image_triple(f["W_in"])
+    c.b_in = f["b_in"].data_ptr()
+    for j, (Wh, bh) in enumerate(zip(f["hid"], f["b_hid"])):
+        c.W_hid[j], c.ldw_hid, c.w_hid_plane = _image_triple(Wh)
+        c.b_hid[j] = bh.data_ptr()
+    c.W_out, c.ldw_out, c.w_out_plane = _image_triple(f["W_out"])
+    c.b_out = f["b_out"].data_ptr()
+    c.sign, c.slope, c.act, c.format, c.range_flag = sign, slope, act, fmt, flag
+    for l, t in enumerate(gate):
+        c.gate[l] = t.data_ptr()
+    for l, t in enumerate(hidden_out):
+        c.hidden_out[l] = t.data_ptr()
+    return op
+
+
+class _PlanesPlan:
+    """A planes plan under construction (PlanesPlanMixin._build_plan_planes): the op list and its bookkeeping, the planes
+    buffer the next layer reads (``z``) and the one an affine layer writes (``other``), and one method per kind of layer."""
+
+    def __init__(self, eng, direction: str, B: int, device, final: str, train: bool, has_ctx: bool):
+        self.eng, self.B, self.device, self.final, self.train, self.has_ctx = eng, B, device, final, train, has_ctx
+        self.pk = eng.pack(device)
+        ws = self.ws = eng._workspace(B, device)
+        self.prims = eng._primitive_ops(direction, merge=not train)     # (the training backward needs every block's own launch)
+        self.nkb = eng.LDp // 32
+        self.seg_phys = eng._phys(eng.segp_idx)
+        self.fmt = eng._planes_fmt()
         if "pflag" not in ws:
             ws["pflag"] = torch.zeros(1, dtype=torch.int32, device=device)
-        flag = ws["pflag"].data_ptr() if fmt == _ext.PLANES_F16X2 else 0
-
-        def planes_buf(name, blocks):
-            if name not in ws or ws[name].numel() < npan * blocks * 3072:
-                ws[name] = torch.empty(npan * blocks * 3072, dtype=torch.uint8, device=device)     # (sized for either format)
-            return ws[name]
-
+        self.flag = ws["pflag"].data_ptr() if self.fmt == _ext.PLANES_F16X2 else 0
         # training: every affine output keeps a planes buffer of its own (the saved activations of the backward pass,
         # already in operand form: (K + 1) x B x LDp x 6 bytes -- cfg2 at 65536 rows: 10.4 GB of the 288 GB), couplings update
         # theirs in place (their conditioning half -- all the backward needs of them -- is untouched)
-        zbufs = [planes_buf("pzA", nkb), planes_buf("pzB", nkb)] if not train else [planes_buf("pz0", nkb), None]
-        znames = ["pzA", "pzB"] if not train else ["pz0", None]
-        n_z = [1]
-        cur = 0
-        ops: List[_ext.Op] = []
-        patch_in, patch_out = [], []
-        meta: List[dict] = []
+        self.z_name, self.other_name = ("pz0", None) if train else ("pzA", "pzB")
+        self.z = self.planes_buf(self.z_name, self.nkb)
+        self.other = None if train else self.planes_buf(self.other_name, self.nkb)
+        self.n_z = 1
+        self.ops: List[_ext.Op] = []
+        self.meta: List[dict] = []
+        self.patch_in, self.patch_out = [], []
+        self.head_scale, self.bias_in_head, self.out_buf = None, False, None
 
-        def gemm_op(**kw) -> _ext.Op:
-            op = _ext.Op()
-            op.kind = _ext.OP_GEMM_PLANES
-            g = op.u.gemm_planes
-            g.M, g.res_sign, g.slope, g.act = B, 1.0, 0.0, _ext.ACT_NONE
-            g.format, g.range_flag = fmt, flag
-            for k_, v_ in kw.items():
-                setattr(g, k_, v_)
-            return op
+    def planes_buf(self, name: str, blocks: int) -> torch.Tensor:
+        ws, n = self.ws, (-(-self.B // 16)) * blocks * 3072            # (sized for either format)
+        if name not in ws or ws[name].numel() < n:
+            ws[name] = torch.empty(n, dtype=torch.uint8, device=self.device)
+        return ws[name]
 
-        # ---- head: the caller's fp32 rows -> planes in segment layout (+ x / s - b of the first layer) -------------
-        n = len(prims)
-        k = 0
+    def gemm_op(self, W: torch.Tensor, **kw) -> _ext.Op:
+        """a usf_gemm_planes op on the weight image W; kw: the descriptor fields that differ from the plain product"""
+        op = _ext.Op()
+        op.kind = _ext.OP_GEMM_PLANES
+        g = op.u.gemm_planes
+        g.M, g.res_sign, g.slope, g.act = self.B, 1.0, 0.0, _ext.ACT_NONE
+        g.format, g.range_flag = self.fmt, self.flag
+        g.W_planes, g.ldw, g.w_plane_stride = _image_triple(W)
+        g.w_rows = W.shape[1]
+        for k_, v_ in kw.items():
+            setattr(g, k_, v_)
+        return op
+
+    def head(self) -> int:
+        """the caller's fp32 rows -> planes in segment layout (+ x / s - b of the first layer); returns how many primitives
+        the pack op took"""
+        e, pk, prims = self.eng, self.pk, self.prims
+        segp = e.segp_idx
         pack = _ext.Op()
         pack.kind = _ext.OP_PACK_PLANES
         d = pack.u.pack_planes
-        d.src, d.ld, d.M, d.nkb = 0, self.D, B, nkb
-        d.src_cols = self.D                    # (every index of the layout is a feature number: rows are read whole, coalesced)
-        d.format, d.range_flag = fmt, flag
-        d.idx = self._idx_dev("segp", device).data_ptr()
-        d.planes = zbufs[cur].data_ptr()
-        first_bias_in_prologue = False
+        d.src, d.ld, d.M, d.nkb = 0, e.D, self.B, self.nkb
+        d.src_cols = e.D                    # (every index of the layout is a feature number: rows are read whole, coalesced)
+        d.format, d.range_flag = self.fmt, self.flag
+        d.idx = e._idx_dev("segp", self.device).data_ptr()
+        d.planes = self.z.data_ptr()
+        k = 0
         if prims[0][0] == "scale_div":
-            s0 = self._step(prims[0][1])
-            d.pre_div = self._planes_vec(pk, ("pl_scale", id(s0.module), "segp"), pk["scale"][id(s0.module)], segp, 1.0).data_ptr()
+            self.head_scale = s0 = e._step(prims[0][1]).module
+            d.pre_div = e._planes_vec(pk, ("pl_scale", id(s0), "segp"), pk["scale"][id(s0)], segp, 1.0).data_ptr()
             if prims[1][0] == "affine_bwd":      # (x / s - b) Minv^T: the bias goes into the head as well
-                blk = self._step(prims[1][1]).module
-                d.pre_sub = self._planes_vec(pk, ("pl_b", id(blk), "segp"), pk["affine"][id(blk)]["b"], segp).data_ptr()
-                first_bias_in_prologue = True
+                blk = e._step(prims[1][1]).module
+                d.pre_sub = e._planes_vec(pk, ("pl_b", id(blk), "segp"), pk["affine"][id(blk)]["b"], segp).data_ptr()
+                self.bias_in_head = True
             k = 1
-        patch_in.append((len(ops), "pack_planes", "src"))
-        ops.append(pack)
-        head_scale = self._step(prims[0][1]).module if prims[0][0] == "scale_div" else None
-        head_bias_folded = first_bias_in_prologue
+        self.patch_in.append((len(self.ops), "pack_planes", "src"))
+        self.ops.append(pack)
+        return k
 
-        while k < n:
-            prim, i = prims[k]
-            s = self._step(i)
-            nxt = prims[k + 1] if k + 1 < n else None
-            if prim in ("affine_fwd", "affine_bwd"):
-                blk = s.module
-                a = self._affine_entry(pk, blk)
-                fuse_post = prim == "affine_fwd" and nxt is not None and nxt[0] == "scale_mul"
-                is_last = (k == n - 1) or (fuse_post and k == n - 2)
-                if train:
-                    is_head = not any(m_["kind"] == "affine" for m_ in meta) and not any(m_["kind"] == "coupling" for m_ in meta)
-                    meta.append(dict(kind="affine", op=len(ops), prim=prim, blk=blk, in_buf=znames[cur], in_layout="segp",
-                                     out_layout="natp" if is_last else "segp", N=self.D if is_last else self.LD, K=self.LD,
-                                     pre_scale=head_scale if is_head else None, post_scale=None,
-                                     pre_sub_folded=bool(is_head and head_bias_folded), is_last=is_last))
-                out_sel = natp if is_last else segp
-                which = "Minv" if prim == "affine_bwd" else "M"
-                W = self._planes_image(pk, ("pl_aff", id(blk), which, is_last), a[which], out_sel, seg_phys, fmt)
-                kw = dict(A=zbufs[cur].data_ptr(), a_nkb=nkb, a_kb0=0, nk=nkb, W_planes=W.data_ptr(), ldw=W.shape[2],
-                          w_plane_stride=W.shape[1] * W.shape[2], w_rows=W.shape[1])
-                lay = "natp" if is_last else "segp"
-                if prim == "affine_bwd":
-                    if first_bias_in_prologue:
-                        first_bias_in_prologue = False        # (x / s - b) @ Minv^T: bias already subtracted by the head
-                    else:
-                        # (y - b) @ Minv^T == y @ Minv^T + c, c = -(Minv b) formed in fp64 at pack time ("bias folding")
-                        if "c" not in a:
-                            a["c"] = torch.empty(a["b"].shape, dtype=torch.float64, device=a["b"].device)
-                            # (launched now, in front of the queued image jobs: it reads the prepared M^-1 and b only, and the job that
-                            # packs c runs with the batch behind the layout loop -- no flush: the images of ALL layers stay one batch)
-                            _ext.matvec_f64(a["Minv"], a["b"].contiguous(), alpha=-1.0, out64=a["c"])
-                        kw["bias"] = self._planes_vec(pk, ("pl_c", id(blk), lay), a["c"], out_sel).data_ptr()
-                else:
-                    kw["bias"] = self._planes_vec(pk, ("pl_b", id(blk), lay), a["b"], out_sel).data_ptr()
-                if is_last:
-                    if fuse_post:
-                        s2 = self._step(nxt[1])
-                        kw["post_mul"] = self._planes_vec(pk, ("pl_scale", id(s2.module), "natp"),
-                                                          pk["scale"][id(s2.module)], natp, 1.0).data_ptr()
-                        k += 1
-                    if final == "user":
-                        kw.update(C_f32=0, ldc=self.D, N=self.D)
-                        patch_out.append((len(ops), "gemm_planes", "C_f32"))
-                        out_buf = ("user_out", "nat", self.D)
-                    elif final.startswith("base"):
-                        # Flow.log_prob: z only feeds the base density -- the epilogue reduces the row's Laplace / Normal terms per
-                        # column block ([B, 8] partial sums; tables refreshed per call by Engine.latent) and stores no rows
-                        stride = _round_up(self.D, 4)
-                        if "btab" not in ws:
-                            ws["btab"] = torch.zeros(3 * stride, dtype=torch.float32, device=device)
-                            ws["bpart"] = torch.zeros(B, 8, dtype=torch.float32, device=device)
-                        kw.update(C_f32=0, ldc=self.D, N=self.D, base_tab=ws["btab"].data_ptr(), base_tab_stride=stride,
-                                  base_part=ws["bpart"].data_ptr(), base=int(final[4:]))
-                        out_buf = ("bpart", "part", 8)
-                    else:
-                        if "nat2" not in ws:
-                            ws["nat2"] = torch.zeros(B, self.LDn, dtype=torch.float32, device=device)
-                        kw.update(C_f32=ws["nat2"].data_ptr(), ldc=self.LDn, N=self.D)
-                        out_buf = ("nat2", "nat", self.LDn)
-                else:
-                    if train:
-                        znames[1 - cur] = f"pz{n_z[0]}"
-                        zbufs[1 - cur] = planes_buf(znames[1 - cur], nkb)
-                        n_z[0] += 1
-                    kw.update(C_planes=zbufs[1 - cur].data_ptr(), c_nkb=nkb, c_kb0=0, c_kbn=nkb)
-                    cur = 1 - cur
-                if train:
-                    meta[-1]["out_buf"] = out_buf[0] if is_last else znames[cur]
-                ops.append(gemm_op(**kw))
-                k += 1
-                continue
-            # ---- additive coupling: its conditioner MLP as a chain of GEMMs, in place on the transformed blocks ----
-            cp = pk["coupling"][i]
-            raw = cp["raw"]
-            sign = 1.0 if prim == "coupling_fwd" else -1.0
-            z = zbufs[cur]
-            lo_p, hi_p = cp["pass_off"], cp["pass_off"] + int((raw["pass_idx"] >= 0).sum())
-            lo_t, hi_t = cp["tr_off"], cp["tr_off"] + cp["tr_n"]
-            kb_p0, kb_p1 = lo_p // 32, -(-hi_p // 32)
-            kb_t0, kb_t1 = lo_t // 32, -(-hi_t // 32)
-            pos = torch.arange(self.LDp)
-            feat_p = torch.where((pos >= lo_p) & (pos < hi_p), segp, torch.full_like(segp, -1))
-            feat_t = torch.where((pos >= lo_t) & (pos < hi_t), segp, torch.full_like(segp, -1))
-            layers = [raw["first"]] + list(raw["hidden"]) + [raw["last"]]
-            h = list(raw["h"])
-            use_ctx = bool(has_ctx and cp["has_ctx"])
-            if self._planes_coupling_fused(h, B, fmt):
-                # ONE launch per layer: usf_coupling_planes (hidden activations stay in registers; widths padded to 256)
-                def pad256(n_valid):
-                    t = torch.full((256,), -1, dtype=torch.long)
-                    t[:n_valid] = torch.arange(n_valid)
-                    return t
-                op = _ext.Op()
-                op.kind = _ext.OP_COUPLING_PLANES
-                c = op.u.coupling_planes
-                c.z, c.z_nkb, c.M = z.data_ptr(), nkb, B
-                c.kb_p0, c.nk_p, c.kb_t0, c.nk_t = kb_p0, kb_p1 - kb_p0, kb_t0, kb_t1 - kb_t0
-                c.n_hidden, c.hidden_padded = len(h), 256
-                Wi = self._planes_image(pk, ("pl_cin", i), layers[0][0], pad256(h[0]), self._phys(feat_p[32 * kb_p0: 32 * kb_p1]), fmt)
-                c.W_in, c.ldw_in, c.w_in_plane = Wi.data_ptr(), Wi.shape[2], Wi.shape[1] * Wi.shape[2]
-                c.b_in = self._planes_vec(pk, ("pl_cinb", i), layers[0][1], pad256(h[0])).data_ptr()
-                for j in range(1, len(h)):
-                    Wh = self._planes_image(pk, ("pl_chid", i, j), layers[j][0], pad256(h[j]), self._phys(pad256(h[j - 1])), fmt)
-                    c.W_hid[j - 1] = Wh.data_ptr()
-                    c.b_hid[j - 1] = self._planes_vec(pk, ("pl_chidb", i, j), layers[j][1], pad256(h[j])).data_ptr()
-                    c.ldw_hid, c.w_hid_plane = Wh.shape[2], Wh.shape[1] * Wh.shape[2]
-                out_sel = feat_t[32 * kb_t0: 32 * kb_t1]
-                Wo = self._planes_image(pk, ("pl_cout", i), layers[-1][0], out_sel, self._phys(pad256(h[-1])), fmt)
-                c.W_out, c.ldw_out, c.w_out_plane = Wo.data_ptr(), Wo.shape[2], Wo.shape[1] * Wo.shape[2]
-                c.b_out = self._planes_vec(pk, ("pl_coutb", i), layers[-1][1], out_sel).data_ptr()
-                c.sign, c.slope, c.act, c.format, c.range_flag = sign, cp["slope"], cp["act"], fmt, flag
-                if use_ctx:
-                    # ConditionalDenseNN's context layer (context_dim 1): the launch becomes usf_coupling_planes_ctx -- a prefix
-                    # op hands the coupling op behind it ws["ctx"] and layers[1]'s weight column / bias as 256-wide vectors
-                    Wc, bc = raw["ctx"]
-                    w_ctx = self._planes_vec(pk, ("pl_cctxw", i), Wc, pad256(h[0]))
-                    b_ctx = self._planes_vec(pk, ("pl_cctxb", i), bc, pad256(h[0]))
-                    ops.append(_ext.coupling_planes_ctx_prefix(ws["ctx"], 1, w_ctx, b_ctx))
-                if train:
-                    # the lane-local splits of the hidden activations also go to planes buffers of the layer's own (8 blocks:
-                    # 2 x B x 256 x 6 bytes per coupling): operands of the conditioner's weight gradients, gates of its backward
-                    hnames = [f"pHs{j}_{i}" for j in range(len(h))]
-                    for j, hn in enumerate(hnames):
-                        c.hidden_out[j] = planes_buf(hn, 8).data_ptr()
-                    meta.append(dict(kind="coupling", op=len(ops), step=i, buf=znames[cur], sign=sign, use_ctx=use_ctx,
-                                     kb_p0=kb_p0, nk_p=kb_p1 - kb_p0, kb_t0=kb_t0, nk_t=kb_t1 - kb_t0, hidden_planes=hnames,
-                                     feat_p=feat_p, feat_t=feat_t))
-                ops.append(op)
-                k += 1
-                continue
-            if train or use_ctx:
-                from .engine import EngineUnsupported
-                raise EngineUnsupported("training / a context on the planes pipeline needs the fused coupling launch")
-            hbufs = [planes_buf("pH1", Hp // 32), planes_buf("pH2", Hp // 32)]
-            src_buf, src_nkb, src_kb0, src_nk = z, nkb, kb_p0, kb_p1 - kb_p0
-            in_sel = self._phys(feat_p[32 * kb_p0: 32 * kb_p1])
-            for j, (W_, b_) in enumerate(layers):
-                last = j == len(layers) - 1
-                if last:
-                    out_sel = feat_t[32 * kb_t0: 32 * kb_t1]
-                else:
-                    hj = _round_up(h[j], 32)
-                    out_sel = torch.full((hj,), -1, dtype=torch.long)
-                    out_sel[: h[j]] = torch.arange(h[j])
-                Wimg = self._planes_image(pk, ("pl_mlp", i, j), W_, out_sel, in_sel, fmt)
-                bvec = self._planes_vec(pk, ("pl_mlpb", i, j), b_, out_sel)
-                kw = dict(A=src_buf.data_ptr(), a_nkb=src_nkb, a_kb0=src_kb0, nk=src_nk, W_planes=Wimg.data_ptr(),
-                          ldw=Wimg.shape[2], w_plane_stride=Wimg.shape[1] * Wimg.shape[2], w_rows=Wimg.shape[1],
-                          bias=bvec.data_ptr())
-                if last:
-                    kw.update(C_planes=z.data_ptr(), c_nkb=nkb, c_kb0=kb_t0, c_kbn=kb_t1 - kb_t0, residual=z.data_ptr(),
-                              res_sign=sign)
-                else:
-                    dst = hbufs[j % 2]
-                    kw.update(C_planes=dst.data_ptr(), c_nkb=Hp // 32, c_kb0=0, c_kbn=hj // 32, act=cp["act"],
-                              slope=cp["slope"])
-                    src_buf, src_nkb, src_kb0, src_nk = dst, Hp // 32, 0, hj // 32
-                    hsel = torch.full((hj,), -1, dtype=torch.long)
-                    hsel[: h[j]] = torch.arange(h[j])
-                    in_sel = self._phys(hsel)
-                ops.append(gemm_op(**kw))
-            k += 1
+    def affine(self, k: int, prim: str, i: int) -> int:
+        """an affine block (with the flow's last ScaleTransform in its epilogue): ONE GEMM, planes -> planes, or -> the fp32
+        result when it is the last layer; returns how many primitives it took"""
+        e, pk, nkb, n = self.eng, self.pk, self.nkb, len(self.prims)
+        nxt = self.prims[k + 1] if k + 1 < n else None
+        blk = e._step(i).module
+        a = e._affine_entry(pk, blk)
+        fuse_post = prim == "affine_fwd" and nxt is not None and nxt[0] == "scale_mul"
+        is_last = (k == n - 1) or (fuse_post and k == n - 2)
+        is_head = len(self.ops) == 1                    # the first layer behind the pack op: the head's prologue belongs to it
+        lay, out_sel = ("natp", e.natp_idx) if is_last else ("segp", e.segp_idx)
+        if self.train:
+            self.meta.append(dict(kind="affine", op=len(self.ops), prim=prim, blk=blk, in_buf=self.z_name, in_layout="segp",
+                                  out_layout=lay, N=e.D if is_last else e.LD, K=e.LD,
+                                  pre_scale=self.head_scale if is_head else None, post_scale=None,
+                                  pre_sub_folded=bool(is_head and self.bias_in_head), is_last=is_last))
+        which = "Minv" if prim == "affine_bwd" else "M"
+        W = e._planes_image(pk, ("pl_aff", id(blk), which, is_last), a[which], out_sel, self.seg_phys, self.fmt)
+        kw = dict(A=self.z.data_ptr(), a_nkb=nkb, a_kb0=0, nk=nkb)
+        if prim == "affine_fwd":
+            kw["bias"] = e._planes_vec(pk, ("pl_b", id(blk), lay), a["b"], out_sel).data_ptr()
+        elif not (is_head and self.bias_in_head):       # (x / s - b) @ Minv^T: bias already subtracted by the head
+            # (y - b) @ Minv^T == y @ Minv^T + c, c = -(Minv b) formed in fp64 at pack time ("bias folding")
+            if "c" not in a:
+                a["c"] = torch.empty(a["b"].shape, dtype=torch.float64, device=a["b"].device)
+                # (launched now, in front of the queued image jobs: it reads the prepared M^-1 and b only, and the job that
+                # packs c runs with the batch behind the layout loop -- no flush: the images of ALL layers stay one batch)
+                _ext.matvec_f64(a["Minv"], a["b"].contiguous(), alpha=-1.0, out64=a["c"])
+            kw["bias"] = e._planes_vec(pk, ("pl_c", id(blk), lay), a["c"], out_sel).data_ptr()
+        if is_last:
+            if fuse_post:
+                s2 = e._step(nxt[1]).module
+                kw["post_mul"] = e._planes_vec(pk, ("pl_scale", id(s2), "natp"), pk["scale"][id(s2)], e.natp_idx, 1.0).data_ptr()
+            self._final_store(kw)
+        else:
+            if self.train:
+                self.other_name = f"pz{self.n_z}"
+                self.other = self.planes_buf(self.other_name, nkb)
+                self.n_z += 1
+            kw.update(C_planes=self.other.data_ptr(), c_nkb=nkb, c_kb0=0, c_kbn=nkb)
+            self.z, self.z_name, self.other, self.other_name = self.other, self.other_name, self.z, self.z_name
+        if self.train:
+            self.meta[-1]["out_buf"] = self.out_buf[0] if is_last else self.z_name
+        self.ops.append(self.gemm_op(W, **kw))
+        return 2 if (is_last and fuse_post) else 1
 
+    def _final_store(self, kw: dict) -> None:
+        """where the last GEMM's fp32 result goes (``final``): sets its descriptor fields in kw and ``out_buf``"""
+        e, ws, B, final = self.eng, self.ws, self.B, self.final
+        if final == "user":
+            kw.update(C_f32=0, ldc=e.D, N=e.D)
+            self.patch_out.append((len(self.ops), "gemm_planes", "C_f32"))
+            self.out_buf = ("user_out", "nat", e.D)
+        elif final.startswith("base"):
+            # Flow.log_prob: z only feeds the base density -- the epilogue reduces the row's Laplace / Normal terms per
+            # column block ([B, 8] partial sums; tables refreshed per call by Engine.latent) and stores no rows
+            stride = _round_up(e.D, 4)
+            if "btab" not in ws:
+                ws["btab"] = torch.zeros(3 * stride, dtype=torch.float32, device=self.device)
+                ws["bpart"] = torch.zeros(B, 8, dtype=torch.float32, device=self.device)
+            kw.update(C_f32=0, ldc=e.D, N=e.D, base_tab=ws["btab"].data_ptr(), base_tab_stride=stride,
+                      base_part=ws["bpart"].data_ptr(), base=int(final[4:]))
+            self.out_buf = ("bpart", "part", 8)
+        else:
+            if "nat2" not in ws:
+                ws["nat2"] = torch.zeros(B, e.LDn, dtype=torch.float32, device=self.device)
+            kw.update(C_f32=ws["nat2"].data_ptr(), ldc=e.LDn, N=e.D)
+            self.out_buf = ("nat2", "nat", e.LDn)
+
+    def coupling(self, prim: str, i: int) -> int:
+        """an additive coupling, in place on the transformed blocks of z: ONE fused launch, or its conditioner as a chain of GEMMs"""
+        e = self.eng
+        cp = self.pk["coupling"][i]
+        geo = e._coupling_geometry(cp)
+        sign = 1.0 if prim == "coupling_fwd" else -1.0
+        use_ctx = bool(self.has_ctx and cp["has_ctx"])
+        if e._planes_coupling_fused(list(cp["raw"]["h"]), self.B, self.fmt):
+            self._coupling_fused(i, cp, geo, sign, use_ctx)
+        elif self.train or use_ctx:
+            raise EngineUnsupported("training / a context on the planes pipeline needs the fused coupling launch")
+        else:
+            self._coupling_chained(i, cp, geo, sign)
+        return 1
+
+    def _coupling_fused(self, i: int, cp: dict, geo: dict, sign: float, use_ctx: bool) -> None:
+        """ONE launch per layer: usf_coupling_planes (hidden activations stay in registers; widths padded to 256)"""
+        e, pk, ws = self.eng, self.pk, self.ws
+        raw = cp["raw"]
+        f = e._coupling_planes_images(pk, i, geo, self.fmt)
+        if use_ctx:
+            # ConditionalDenseNN's context layer (context_dim 1): the launch becomes usf_coupling_planes_ctx -- a prefix
+            # op hands the coupling op behind it ws["ctx"] and layers[1]'s weight column / bias as 256-wide vectors
+            Wc, bc = raw["ctx"]
+            rows0 = arange_padded(raw["h"][0], 256)
+            w_ctx = e._planes_vec(pk, ("pl_cctxw", i), Wc, rows0)
+            b_ctx = e._planes_vec(pk, ("pl_cctxb", i), bc, rows0)
+            self.ops.append(_ext.coupling_planes_ctx_prefix(ws["ctx"], 1, w_ctx, b_ctx))
+        # training: the lane-local splits of the hidden activations also go to planes buffers of the layer's own (8 blocks:
+        # 2 x B x 256 x 6 bytes per coupling): operands of the conditioner's weight gradients, gates of its backward
+        hnames = [f"pHs{j}_{i}" for j in range(len(raw["h"]))] if self.train else []
+        op = coupling_planes_op(self.z, self.nkb, self.B, (geo["kb_p0"], geo["nk_p"], geo["kb_t0"], geo["nk_t"]), f, sign,
+                                cp["slope"], cp["act"], self.fmt, self.flag, hidden_out=[self.planes_buf(hn, 8) for hn in hnames])
+        if self.train:
+            self.meta.append(dict(kind="coupling", op=len(self.ops), step=i, buf=self.z_name, sign=sign, use_ctx=use_ctx,
+                                  hidden_planes=hnames, **geo))
+        self.ops.append(op)
+
+    def _coupling_chained(self, i: int, cp: dict, geo: dict, sign: float) -> None:
+        """the conditioner MLP as a chain of GEMMs through a pair of hidden planes buffers; the last one adds into z"""
+        e, pk, z, nkb = self.eng, self.pk, self.z, self.nkb
+        raw = cp["raw"]
+        h = list(raw["h"])
+        layers = [raw["first"]] + list(raw["hidden"]) + [raw["last"]]
+        hkb = _round_up(e.hmax, 32) // 32
+        hbufs = [self.planes_buf("pH1", hkb), self.planes_buf("pH2", hkb)]
+        src = dict(A=z.data_ptr(), a_nkb=nkb, a_kb0=geo["kb_p0"], nk=geo["nk_p"])
+        in_sel = geo["feat_p"][32 * geo["kb_p0"]: 32 * (geo["kb_p0"] + geo["nk_p"])]
+        for j, (W_, b_) in enumerate(layers):
+            last = j == len(layers) - 1
+            if last:
+                out_sel = geo["feat_t"][32 * geo["kb_t0"]: 32 * (geo["kb_t0"] + geo["nk_t"])]
+                dst = dict(C_planes=z.data_ptr(), c_nkb=nkb, c_kb0=geo["kb_t0"], c_kbn=geo["nk_t"], residual=z.data_ptr(), res_sign=sign)
+            else:
+                hj = _round_up(h[j], 32)
+                out_sel = arange_padded(h[j], hj)
+                buf = hbufs[j % 2]
+                dst = dict(C_planes=buf.data_ptr(), c_nkb=hkb, c_kb0=0, c_kbn=hj // 32, act=cp["act"], slope=cp["slope"])
+            Wimg = e._planes_image(pk, ("pl_mlp", i, j), W_, out_sel, e._phys(in_sel), self.fmt)
+            bvec = e._planes_vec(pk, ("pl_mlpb", i, j), b_, out_sel)
+            self.ops.append(self.gemm_op(Wimg, bias=bvec.data_ptr(), **src, **dst))
+            if not last:
+                src, in_sel = dict(A=buf.data_ptr(), a_nkb=hkb, a_kb0=0, nk=hj // 32), out_sel
+
+    def result(self) -> dict:
+        ops, out_buf = self.ops, self.out_buf
         arr = (_ext.Op * len(ops))(*ops)
         n_part = 0
         if out_buf[1] == "part":
             tn = (_ext.load().usf_gemm_planes_variant(arr[len(ops) - 1].u.gemm_planes) - 5000) // 10
-            n_part = -(-self.D // (32 * tn))
-        return dict(arr=arr, n=len(ops), patch_in=patch_in, patch_out=patch_out, side=[], final_gather=None, n_part=n_part,
-                    out_buf=out_buf, ws=ws, pk=pk, meta=meta, planes=True, planes_fmt=fmt, planes_train=bool(train),
-                    has_ctx=bool(has_ctx))
+            n_part = -(-self.eng.D // (32 * tn))
+        return dict(arr=arr, n=len(ops), patch_in=self.patch_in, patch_out=self.patch_out, side=[], final_gather=None,
+                    n_part=n_part, out_buf=out_buf, ws=self.ws, pk=self.pk, meta=self.meta, planes=True, planes_fmt=self.fmt,
+                    planes_train=bool(self.train), has_ctx=bool(self.has_ctx))

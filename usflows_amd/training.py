@@ -34,7 +34,7 @@ import torch
 from . import _ext
 from . import transforms as T
 from .config import config
-from .engine import FlowEngine, _round_up
+from .engine import FlowEngine, _round_up, conditioner_layers
 from .networks import ConditionalDenseNN, ConvNet, DenseNN
 
 
@@ -485,39 +485,15 @@ class TrainPath:
         if plan.get("planes_train"):
             return self._backward_body_planes(plan, arena)
         eng = self.eng
-        ws, pk = plan["ws"], plan["pk"]
+        ws = plan["ws"]
         dev = ws["zA"].device
         B = ws["zA"].shape[0]
-        D = eng.D
         wid = max(eng.LD, eng.LDn)
         gA, gB = self._buf(ws, "gA", B, wid), self._buf(ws, "gB", B, wid)
-        glp = self._buf(ws, "g_lp", 1, B)[0, :B]
-        _ext.host_op(lambda: (arena["flat"].zero_(), glp.copy_(self._cur["g_lp"])))
-        info = self.flow._base_info(dev)
-        base, loc, scale = self._base_tensors(ws, info)
-        zname, _, ldn = plan["out_buf"]
-        grads = arena["views"]
-        self._touched = arena["touched"]
-        if info[0] == "radial":
-            scale = self._buf(ws, "radius", 1, B)[0, :B]              # the forward left r = ||z - loc||_p here
-        self._base_param_grads(ws, ws[zname], ldn, glp, B, base, loc, scale, grads)
-        _ext.base_logprob_grad(ws[zname], ldn, glp, B, D, base, loc, scale, gA, ldn)
-        if info[0] == "radial":
-            g_loc = self._grad_slot(grads, self.flow.base_distribution.loc)
-            if g_loc is not None:                                     # r depends on z - loc: d/dloc = -sum_m d/dz
-                _ext.colsum(gA, g_loc, M=B, N=D, ldy=ldn, alpha=-1.0)
-        g_cur, g_other, g_ld = gA, gB, ldn
-        aff: Dict[int, dict] = {}            # id(block) -> natural-layout gradients of its usages
-        n_aff = sum(1 for m in plan["meta"] if m["kind"] == "affine")
-        stacks = dict(G=torch.zeros(max(n_aff, 1), D, D, dtype=torch.float32, device=dev),
-                      gs=torch.zeros(max(n_aff, 1), D, dtype=torch.float32, device=dev), next=0)
-        self._lu_slot = self._lu_slots(plan)
-        if self._lu_slot is not None and any(m["kind"] == "affine" and m["prim"] == "affine_fwd" for m in plan["meta"]):
-            # affine_conjugation: a block is also used in its M form (InverseTransform.backward): stacks of their own
-            stacks["GM"] = torch.zeros_like(stacks["G"])
-            stacks["gsM"] = torch.zeros_like(stacks["gs"])
+        glp, base, loc, scale, grads, aff, stacks, first_meta = self._backward_open(plan, arena)
+        self._latent_grad_rows(plan, glp, base, loc, scale, gA, grads)
+        g_cur, g_other, g_ld = gA, gB, plan["out_buf"][2]
         self._wmode = 1 if eng.gemm_mode == "bf16x3" else 0      # weight gradients on the same arithmetic as the GEMMs
-        first_meta = plan["meta"][0] if plan["meta"] else None
         self._prepare_images(plan, first_meta)
         # gradient images -> parameter layout (scatter / un-permute): every layer has image buffers of its own, so all
         # of these copies wait in one batch and go out as one launch per size class behind the last layer
@@ -539,6 +515,46 @@ class TrainPath:
                     self._g_pending = self._defer
         self._dx = (g_cur, g_ld) if self._want_dx else None          # the gradient at the first layer's input (natural order)
         _ext.host_op(lambda: self._affine_param_grads(plan, aff, stacks, glp, grads, arena))
+
+    def _backward_open(self, plan, arena):
+        """the opening both layer loops share: the arena zeroed and g_lp staged (one host op of the tape), the base density's
+        tensors (scale: the radius of a radial base) and its parameter gradients, the stacks the affine layers' natural-layout
+        gradients land in, the batched chain rule's rows.  Returns (glp, base, loc, scale, grads, aff, stacks, first_meta)"""
+        ws = plan["ws"]
+        dev = ws["zA"].device
+        B, D = ws["zA"].shape[0], self.eng.D
+        glp = self._buf(ws, "g_lp", 1, B)[0, :B]
+        _ext.host_op(lambda: (arena["flat"].zero_(), glp.copy_(self._cur["g_lp"])))
+        info = self.flow._base_info(dev)
+        base, loc, scale = self._base_tensors(ws, info)
+        zname, _, ldn = plan["out_buf"]
+        grads = arena["views"]
+        self._touched = arena["touched"]
+        if info[0] == "radial":
+            scale = self._buf(ws, "radius", 1, B)[0, :B]              # the forward left r = ||z - loc||_p here
+        self._base_param_grads(ws, ws[zname], ldn, glp, B, base, loc, scale, grads)
+        aff: Dict[int, dict] = {}            # id(block) -> natural-layout gradients of its usages
+        n_aff = sum(1 for m in plan["meta"] if m["kind"] == "affine")
+        stacks = dict(G=torch.zeros(max(n_aff, 1), D, D, dtype=torch.float32, device=dev),
+                      gs=torch.zeros(max(n_aff, 1), D, dtype=torch.float32, device=dev), next=0)
+        self._lu_slot = self._lu_slots(plan)
+        if self._lu_slot is not None and any(m["kind"] == "affine" and m["prim"] == "affine_fwd" for m in plan["meta"]):
+            # affine_conjugation: a block is also used in its M form (InverseTransform.backward): stacks of their own
+            stacks["GM"] = torch.zeros_like(stacks["G"])
+            stacks["gsM"] = torch.zeros_like(stacks["gs"])
+        return glp, base, loc, scale, grads, aff, stacks, (plan["meta"][0] if plan["meta"] else None)
+
+    def _latent_grad_rows(self, plan, glp, base, loc, scale, gA, grads):
+        """d sum(g_lp log_prob) / d latent as fp32 rows in gA (row stride of the latent buffer) and, for a radial base, d loc
+        from the same rows"""
+        ws = plan["ws"]
+        B, D = ws["zA"].shape[0], self.eng.D
+        zname, _, ldn = plan["out_buf"]
+        _ext.base_logprob_grad(ws[zname], ldn, glp, B, D, base, loc, scale, gA, ldn)
+        if self.flow._base_info(gA.device)[0] == "radial":
+            g_loc = self._grad_slot(grads, self.flow.base_distribution.loc)
+            if g_loc is not None:                                     # r depends on z - loc: d/dloc = -sum_m d/dz
+                _ext.colsum(gA, g_loc, M=B, N=D, ldy=ldn, alpha=-1.0)
 
     def _base_param_grads(self, ws, z, ldz, glp, B, base, loc, scale, grads):
         """a trainable Laplace / Normal base: d/dloc, d/dscale_unconstrained of sum_m g_lp[m] log_prob[m] -- one pass over the
@@ -588,45 +604,24 @@ class TrainPath:
         D = eng.D
         nkb = eng.LDp // 32
         nkb_g = max(eng.LDp, eng.LDnp) // 32
-        wid = max(eng.LD, eng.LDn)
-        gA = self._buf(ws, "gA", B, wid)
-        glp = self._buf(ws, "g_lp", 1, B)[0, :B]
-        _ext.host_op(lambda: (arena["flat"].zero_(), glp.copy_(self._cur["g_lp"])))
-        info = self.flow._base_info(dev)
-        base, loc, scale = self._base_tensors(ws, info)
+        gA = self._buf(ws, "gA", B, max(eng.LD, eng.LDn))
+        glp, base, loc, scale, grads, aff, stacks, first_meta = self._backward_open(plan, arena)
         zname, _, ldn = plan["out_buf"]
-        grads = arena["views"]
-        self._touched = arena["touched"]
-        self._base_param_grads(ws, ws[zname], ldn, glp, B, base, loc, scale, grads)
+        radial = self.flow._base_info(dev)[0] == "radial"
         gp = [self._planes_buf(ws, "pgA", B, nkb_g), self._planes_buf(ws, "pgB", B, nkb_g)]
         key = ("natp_g", nkb_g, str(dev))
         if key not in self._inv:
             t = torch.full((32 * nkb_g,), -1, dtype=torch.int32)
             t[:D] = torch.arange(D, dtype=torch.int32)
             self._inv[key] = t.to(dev)
-        if info[0] != "radial" and (16 * (D + 1) + 96 * nkb_g) * 4 <= 65536:      # (the rows kernel's LDS: 16 rows + the layout tables)
+        if not radial and (16 * (D + 1) + 96 * nkb_g) * 4 <= 65536:      # (the rows kernel's LDS: 16 rows + the layout tables)
             # Laplace / Normal base: the gradient at the latent goes straight into the planes (one pass over z instead of
             # usf_base_logprob_grad_f32's fp32 rows + their repack)
             _ext.pack_planes(ws[zname], gp[0], M=B, nkb=nkb_g, idx=self._inv[key], ld=ldn, src_cols=D, grad=(base, glp, loc, scale))
         else:
-            if info[0] == "radial":
-                scale = self._buf(ws, "radius", 1, B)[0, :B]
-            _ext.base_logprob_grad(ws[zname], ldn, glp, B, D, base, loc, scale, gA, ldn)
-            if info[0] == "radial":
-                g_loc = self._grad_slot(grads, self.flow.base_distribution.loc)
-                if g_loc is not None:
-                    _ext.colsum(gA, g_loc, M=B, N=D, ldy=ldn, alpha=-1.0)
+            self._latent_grad_rows(plan, glp, base, loc, scale, gA, grads)
             _ext.pack_planes(gA, gp[0], M=B, nkb=nkb_g, idx=self._inv[key], ld=ldn, src_cols=D)
         cur = 0
-        aff: Dict[int, dict] = {}
-        n_aff = sum(1 for m in plan["meta"] if m["kind"] == "affine")
-        stacks = dict(G=torch.zeros(max(n_aff, 1), D, D, dtype=torch.float32, device=dev),
-                      gs=torch.zeros(max(n_aff, 1), D, dtype=torch.float32, device=dev), next=0)
-        self._lu_slot = self._lu_slots(plan)
-        if self._lu_slot is not None and any(m["kind"] == "affine" and m["prim"] == "affine_fwd" for m in plan["meta"]):
-            stacks["GM"] = torch.zeros_like(stacks["G"])
-            stacks["gsM"] = torch.zeros_like(stacks["gs"])
-        first_meta = plan["meta"][0] if plan["meta"] else None
         with eng._pk_record(pk), _ext.batch_jobs(dev):      # every weight image of the backward, one batched launch
             for m in plan["meta"]:
                 if m["kind"] == "coupling":
@@ -665,29 +660,14 @@ class TrainPath:
     def _affine_backward_planes(self, plan, m, gp, cur, nkb, nkb_g, aff, stacks, need_dgrad):
         eng = self.eng
         ws, pk = plan["ws"], plan["pk"]
-        dev = ws["zA"].device
         B = ws["zA"].shape[0]
-        D = eng.D
-        blk = m["blk"]
-        which = "Minv" if m["prim"] == "affine_bwd" else "M"
         n_out, n_in = m["N"], m["K"]
         wid = max(eng.LD, eng.LDn)
         Gp = self._buf(ws, f"Gp{m['op']}", wid, wid)
         gs = self._buf(ws, f"gs{m['op']}", 1, wid)
         _ext.wgrad_blocked(gp[cur], nkb_g, 0, ws[m["in_buf"]], nkb, 0, Gp, M=B, N=n_out, K=n_in, ldg=Gp.shape[1], colsum=gs,
                            **self._wq(ws, f"a{m['op']}", B, n_out, n_in))
-        k = self._lu_slot[id(blk)] if self._lu_slot is not None else stacks["next"]
-        stacks["next"] += 1
-        if self._lu_slot is not None and which == "M":
-            G_nat, gs_nat = stacks["GM"][k], stacks["gsM"][k]
-        else:
-            G_nat, gs_nat = stacks["G"][k], stacks["gs"][k]
-        _ext.pack_weight(Gp, self._inv_idx(m["out_layout"], dev), D, self._inv_idx(m["in_layout"], dev), D,
-                         W=G_nat, ldw=D, ld_src=Gp.shape[1])
-        _ext.pack_weight(gs, None, 1, self._inv_idx(m["out_layout"], dev), D, W=gs_nat, ldw=D, ld_src=gs.shape[1])
-        rec = aff.setdefault(id(blk), dict(blk=blk, uses=[]))
-        rec["uses"].append(dict(which=which, G=G_nat, gsum=gs_nat, pre_scale=m["pre_scale"], row=k,
-                                pre_sub_folded=bool(m.get("pre_sub_folded"))))
+        self._affine_grad_to_stack(m, Gp, gs, aff, stacks)
         if not need_dgrad:
             return cur
         Wt = eng.planes_dgrad_image(pk, m)
@@ -723,15 +703,12 @@ class TrainPath:
         hs = [ws[n_] for n_ in m["hidden_planes"]]
         dh = [self._planes_buf(ws, f"pD{j}", B, 8) for j in range(nl)]
         _ext.coupling_planes_op(eng.planes_coupling_bwd_op(pk, m, g, nkb_g, B, hs, dh), dev)
-        lin = list(cond.layers)
-        has_ctx = isinstance(cond, ConditionalDenseNN)
-        first_l, last_l = lin[0], lin[-1]
-        hidden_l = lin[2:-1] if has_ctx else lin[1:-1]
+        first_l, ctx_l, hidden_l, last_l = conditioner_layers(cond)
         wmax = max(eng.LDp, 256)
         gimg = lambda tag: self._buf(ws, f"gW{m['step']}_{tag}", wmax, wmax)      # noqa: E731
         gvec = lambda tag: self._buf(ws, f"gb{m['step']}_{tag}", 1, wmax)          # noqa: E731
         # output layer: Y = the gradient at the transformed blocks (unchanged by the launch above), A = the last hidden activations
-        n_t = int((m["feat_t"] >= 0).nonzero().max().item()) + 1 - 32 * m["kb_t0"]
+        n_t, n_p = m["n_t"], m["n_p"]                         # valid widths of the block ranges (engine_planes: _coupling_geometry)
         gW, gb = gimg("out"), gvec("out")
         _ext.wgrad_blocked(g, nkb_g, m["kb_t0"], hs[nl - 1], 8, 0, gW, M=B, N=n_t, K=256, ldg=gW.shape[1], alpha=sign,
                            colsum=gb, cs_alpha=sign, **self._wq(ws, f"c{m['step']}o", B, n_t, 256))
@@ -747,17 +724,15 @@ class TrainPath:
             self._scatter_weight(grads, l.weight, gW, None, h[j], None, h[j - 1])
             self._scatter_vec(grads, l.bias, gb, None, h[j])
         # input layer: A = the conditioning blocks of the layer's own z buffer (what the forward's conditioner saw)
-        n_p = int((m["feat_p"] >= 0).nonzero().max().item()) + 1 - 32 * m["kb_p0"]
         gW, gb = gimg("in"), gvec("in")
         _ext.wgrad_blocked(dh[0], 8, 0, ws[m["buf"]], nkb, m["kb_p0"], gW, M=B, N=h[0], K=n_p, ldg=gW.shape[1], alpha=sign,
                            colsum=gb, cs_alpha=sign, **self._wq(ws, f"c{m['step']}i", B, h[0], n_p))
         self._scatter_weight(grads, first_l.weight, gW, None, h[0], self._seg_sel(m, "p", dev), eng.D)
         self._scatter_vec(grads, first_l.bias, gb, None, h[0])
-        if has_ctx and m["use_ctx"]:
+        if ctx_l is not None and m["use_ctx"]:
             # the context layer (layers[1], context_dim 1) adds ctx * W_ctx + b_ctx to the first pre-activation: d b_ctx is the
             # column sum d b_in already holds, d W_ctx[h] = sign * sum_rows ctx[row] * d_h0[row, h] -- column 0 of the weight
             # gradient against the context planes.  (A context layer that sees no context gets no gradient, as under autograd.)
-            ctx_l = lin[1]
             self._scatter_vec(grads, ctx_l.bias, gb, None, h[0])
             gWc = gimg("ctx")
             _ext.wgrad_blocked(dh[0], 8, 0, ws["pctx"], 1, 0, gWc, M=B, N=h[0], K=32, ldg=gWc.shape[1], alpha=sign,
@@ -875,18 +850,7 @@ class TrainPath:
         if not from_planes:
             gs = self._buf(ws, f"gs{m['op']}", 1, wid)
             _ext.colsum(g_cur, gs, M=B, N=n_out, ldy=g_ld)
-        D = eng.D
-        k = self._lu_slot[id(blk)] if self._lu_slot is not None else stacks["next"]
-        stacks["next"] += 1
-        if self._lu_slot is not None and which == "M":
-            G_nat, gs_nat = stacks["GM"][k], stacks["gsM"][k]
-        else:
-            G_nat, gs_nat = stacks["G"][k], stacks["gs"][k]
-        _ext.pack_weight(Gp, self._inv_idx(m["out_layout"], dev), D, self._inv_idx(m["in_layout"], dev), D,
-                         W=G_nat, ldw=D, ld_src=Gp.shape[1])
-        _ext.pack_weight(gs, None, 1, self._inv_idx(m["out_layout"], dev), D, W=gs_nat, ldw=D, ld_src=gs.shape[1])
-        rec = aff.setdefault(id(blk), dict(blk=blk, uses=[]))
-        rec["uses"].append(dict(which=which, G=G_nat, gsum=gs_nat, pre_scale=m["pre_scale"], row=k))
+        self._affine_grad_to_stack(m, Gp, gs, aff, stacks)
         if from_planes:
             return g_other, g_cur, n_in
         if need_dgrad:
@@ -898,6 +862,26 @@ class TrainPath:
             self._linear(pk, g_cur, 0, g_ld, Wt, g_other, 0, n_in, B, n_in, n_out)
             return g_other, g_cur, n_in
         return g_cur, g_other, g_ld
+
+    def _affine_grad_to_stack(self, m, Gp, gs, aff, stacks):
+        """the tail of an affine layer's parameter gradients, on either path: the weight-gradient image Gp and the bias sums gs
+        go back to the natural layout, into the block's row of the stacks (two queued un-permute jobs), and the use is recorded
+        for the chain rule (_affine_param_grads)"""
+        D, dev = self.eng.D, Gp.device
+        blk = m["blk"]
+        which = "Minv" if m["prim"] == "affine_bwd" else "M"
+        k = self._lu_slot[id(blk)] if self._lu_slot is not None else stacks["next"]
+        stacks["next"] += 1
+        if self._lu_slot is not None and which == "M":
+            G_nat, gs_nat = stacks["GM"][k], stacks["gsM"][k]
+        else:
+            G_nat, gs_nat = stacks["G"][k], stacks["gs"][k]
+        _ext.pack_weight(Gp, self._inv_idx(m["out_layout"], dev), D, self._inv_idx(m["in_layout"], dev), D,
+                         W=G_nat, ldw=D, ld_src=Gp.shape[1])
+        _ext.pack_weight(gs, None, 1, self._inv_idx(m["out_layout"], dev), D, W=gs_nat, ldw=D, ld_src=gs.shape[1])
+        rec = aff.setdefault(id(blk), dict(blk=blk, uses=[]))
+        rec["uses"].append(dict(which=which, G=G_nat, gsum=gs_nat, pre_scale=m["pre_scale"], row=k,
+                                pre_sub_folded=bool(m.get("pre_sub_folded"))))
 
     # ---- coupling layers ------------------------------------------------------------------------------
     @staticmethod
@@ -1100,10 +1084,7 @@ class TrainPath:
             self._linear(pk, src, src_off, src_ld, W, hbufs[j], 0, hmax, B, W.shape[0], src_K, bias=b, act=act,
                          slope=slope, **kw)
             src, src_off, src_ld, src_K = hbufs[j], 0, hmax, W.shape[0]
-        lin = list(cond.layers)
-        has_ctx = isinstance(cond, ConditionalDenseNN)
-        first_l, last_l = lin[0], lin[-1]
-        hidden_l = lin[2:-1] if has_ctx else lin[1:-1]
+        first_l, ctx_l, hidden_l, last_l = conditioner_layers(cond)
         fused_bwd = self._fused_cbwd(m, B)
         if fused_bwd:
             # ONE launch: g_P += s * MLP^T(g_T) with the (Leaky)ReLU backward from the saved activations; the gradients at the
@@ -1171,13 +1152,11 @@ class TrainPath:
         self._scatter_weight(grads, first_l.weight, gW, None, h[0], self._sel_inv(raw["pass_idx"], dev), eng.D)
         if gbias is None:
             self._colsum_to(grads, first_l.bias, d, B, h[0], hmax, sign)
-        if has_ctx:
-            ctx_l = lin[1]
-            if m["use_ctx"]:
-                gW = gimg("ctx")
-                _ext.wgrad(d, ws["ctx4"], gW, M=B, N=hp[0], K=4, ldy=hmax, lda=4, ldg=gW.shape[1], alpha=sign)
-                self._scatter_weight(grads, ctx_l.weight, gW, None, h[0], None, 1)
-                self._colsum_to(grads, ctx_l.bias, d, B, h[0], hmax, sign)
+        if ctx_l is not None and m["use_ctx"]:
+            gW = gimg("ctx")
+            _ext.wgrad(d, ws["ctx4"], gW, M=B, N=hp[0], K=4, ldy=hmax, lda=4, ldg=gW.shape[1], alpha=sign)
+            self._scatter_weight(grads, ctx_l.weight, gW, None, h[0], None, 1)
+            self._colsum_to(grads, ctx_l.bias, d, B, h[0], hmax, sign)
         # conditioning half of the gradient: g_P += s * d W_in   (in place)
         if fused_bwd:
             return                     # (the fused launch above already updated the conditioning half)
