@@ -16,7 +16,7 @@
 extern "C" {
 #endif
 
-#define USF_INTERNAL_VERSION 3
+#define USF_INTERNAL_VERSION 4
 
 /* USF_INTERNAL_VERSION of the header the library was built from (host only, launches nothing). */
 int usf_internal_version(void);
@@ -130,6 +130,45 @@ int usf_radial_logprob_grad_f32(const float* z, int64_t ldz, const float* r, con
 #define USF_FN_COUPLING_PLANES_CTX 64
 int usf_coupling_planes_ctx(const usf_coupling_planes_desc* d, const float* ctx, int64_t ctx_stride, const float* w_ctx,
                             const float* b_ctx, usf_stream_t stream);
+
+/*
+ * usf_coupling_additive_vctx_f32 (internal version 4): usf_coupling_additive_f32 (usflows_hip.h) whose conditioner is a
+ * ConditionalDenseNN with 1 <= context_dim <= USF_VCTX_MAX (networks.py:681-751: h = layers[0](x) + layers[1](context)).
+ * The first hidden layer's pre-activation becomes
+ *     v + ( b_ctx[h] + sum_{c < ctx_dim} ctx[m * ld_ctx + c] * W_ctx_t[c * ldw_ctx + h] )           (row m, hidden unit h)
+ * -- a rank-ctx_dim term summed in fp32 over c in ascending order and added as ONE value: no matrix instruction, nothing in the
+ * K loops.  It runs in all three kernel families of usf_coupling_additive_f32 (the exact-f32, the bf16x3 and the tiny-layer
+ * kernel), as instantiations of their own: the descriptors without this entry's context run the kernels they always ran.
+ *   ctx       fp32 rows of ld_ctx floats, 16-byte aligned; ld_ctx a multiple of 4 and >= round_up(ctx_dim, 4) (M rows), or
+ *             ld_ctx == 0: ONE row for all rows.  PADDING CONTRACT: only the columns [0, ctx_dim) enter the arithmetic.  A
+ *             kernel may LOAD the padding columns [ctx_dim, round_up(ctx_dim, 4)) of a row (they must be readable memory, also
+ *             with ld_ctx == 0) but never multiplies them in: whatever they hold -- NaN included -- leaves the output unchanged.
+ *   W_ctx_t   the context weights TRANSPOSED, layers[1].weight^T as [ctx_dim, ldw_ctx] fp32 rows: a lane's four consecutive
+ *             hidden units are one 16-byte load per context column.  16-byte aligned, ldw_ctx a multiple of 4 and >= the
+ *             padded hidden width the kernel runs at (usf_coupling_padded_width(widest hidden layer); the tiny-layer kernel
+ *             reads hidden[0] columns only), zeros beyond the real width.
+ *   b_ctx     layers[1].bias, fp32 of that padded width, zeros beyond the real width, 16-byte aligned.
+ * d->context, d->W_ctx and d->b_ctx must be NULL.  USF_ACT_GATE with a context is rejected (the backward chain has no context
+ * term: the context enters no data gradient); hidden_out (the training forward) is served where usf_coupling_additive_f32
+ * serves it.  ctx == NULL: exactly usf_coupling_additive_f32 (same kernels, same bits).  Every argument is validated before
+ * any launch; an error launches nothing.
+ *
+ * usf_coupling_additive_vctx_variant: which kernel the entry point launches for the descriptor with a context of ctx_dim
+ * columns (3 / 2 / 1 / 0 as usf_coupling_variant; nothing is launched, no pointer is dereferenced).  The tiny-layer kernel
+ * keeps the rows' context ([32, ctx_dim]) and W_ctx_t ([ctx_dim, hidden[0]]) in LDS: a layer whose images no longer fit
+ * the 64 KB with them is served by the MFMA kernels (whose alignment rules then apply) -- it selects another kernel, it does
+ * not fail.  ctx_dim == 0: usf_coupling_variant.
+ *
+ * Inside an op list: a USF_OP_CALL op with fn == USF_FN_COUPLING_VCTX and n_args == 6 carries (ctx, ld_ctx, ctx_dim, W_ctx_t,
+ * ldw_ctx, b_ctx) as its words a[0..5] and applies to the USF_OP_COUPLING op that must follow it directly: the pair is ONE
+ * usf_coupling_additive_vctx_f32 launch.  A list that ends behind the prefix op, or whose next op is of another kind, is
+ * rejected.
+ */
+#define USF_VCTX_MAX 32
+#define USF_FN_COUPLING_VCTX 65
+int usf_coupling_additive_vctx_f32(const usf_coupling_desc* d, const float* ctx, int64_t ld_ctx, int32_t ctx_dim,
+                                   const float* W_ctx_t, int64_t ldw_ctx, const float* b_ctx, usf_stream_t stream);
+int usf_coupling_additive_vctx_variant(const usf_coupling_desc* d, int32_t ctx_dim);
 
 /* usf_conv_ctx_wgrad_f32 (ABI 36): the weight gradient of the context channel of usf_conv2d_same_ctx_f32 (usflows_hip.h;
  * reference networks.py:513-680 under autograd),

@@ -4,7 +4,7 @@ loads the library or launches anything; ``_ext.py`` does, and re-exports every n
 import ctypes as C
 
 USF_ABI_VERSION = 36          # include/usflows_hip.h
-USF_INTERNAL_VERSION = 3      # include/usflows_hip_internal.h
+USF_INTERNAL_VERSION = 4      # include/usflows_hip_internal.h
 USF_MAX_HIDDEN = 4
 
 ACT_NONE, ACT_LEAKY_RELU, ACT_GATE = 0, 1, 2
@@ -19,6 +19,8 @@ CALL_FNS = {"usf_scale_f32": 1, "usf_channel_affine_f32": 2, "usf_layernorm_chan
             "usf_base_logprob_f32": 9, "usf_radial_logprob_f32": 10, "usf_gated_tail_f32": 11, "usf_conv2d_same_ctx_f32": 12}
 
 FN_COUPLING_PLANES_CTX = 64   # internal USF_OP_CALL id: the context arguments of the USF_OP_COUPLING_PLANES op behind it
+FN_COUPLING_VCTX = 65         # internal USF_OP_CALL id: the vector context of the USF_OP_COUPLING op behind it
+VCTX_MAX = 32                 # USF_VCTX_MAX: widest context usf_coupling_additive_vctx_f32 takes
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -260,6 +262,8 @@ INTERNAL_SYMBOLS = {
                                               _fp, _fp, _fp, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_void_p]),
     "usf_gated_norm_rows_bwd_f32": (C.c_int, [C.POINTER(GatedNormBwdDesc), C.c_void_p]),
     "usf_coupling_planes_ctx": (C.c_int, [C.POINTER(CouplingPlanesDesc), _fp, C.c_int64, _fp, _fp, C.c_void_p]),
+    "usf_coupling_additive_vctx_f32": (C.c_int, [C.POINTER(CouplingDesc), _fp, C.c_int64, C.c_int32, _fp, C.c_int64, _fp, C.c_void_p]),
+    "usf_coupling_additive_vctx_variant": (C.c_int, [C.POINTER(CouplingDesc), C.c_int32]),
     "usf_conv_ctx_wgrad_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_void_p]),
     "usf_conv2d_same_gate_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [C.c_void_p, _fp, C.c_float, _fp, _fp, C.c_void_p]),
     "usf_conv_wgrad_workspace": (C.c_int64, [C.c_int64] * 6),

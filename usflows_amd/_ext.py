@@ -22,7 +22,7 @@ from ._abi import (  # noqa: E402,F401  -- the declarations, re-exported: caller
     USF_ABI_VERSION, USF_INTERNAL_VERSION, USF_MAX_HIDDEN, ACT_NONE, ACT_LEAKY_RELU, ACT_GATE, BASE_LAPLACE, BASE_NORMAL,
     BASE_LPNORM1, BASE_LPNORM2, BASE_LPNORMINF, BASE_ROWSUM, NORM_LOGNORMAL, NORM_GAMMA, NORM_RAW_PARAMS, RADIAL_MAX_K, OP_LINEAR,
     OP_COUPLING, OP_PACK_PLANES, OP_GEMM_PLANES, OP_COUPLING_PLANES, OP_GATED_NORM, OP_CALL, PLANES_BF16X3, PLANES_F16X2, CALL_FNS,
-    FN_COUPLING_PLANES_CTX,
+    FN_COUPLING_PLANES_CTX, FN_COUPLING_VCTX, VCTX_MAX,
     _fp, LinearDesc, CouplingDesc, PackPlanesDesc, GemmPlanesDesc, CouplingPlanesDesc, MtChunk, GatedNormDesc, GatedNormBwdDesc,
     CallDesc, _OpUnion, Op, LuPrepDesc, PackJob, PsumJob, WgradJob, WReduceJob, WPlanesJob, GradJob, SIZEOF_KINDS, PUBLIC_SYMBOLS,
     INTERNAL_SYMBOLS, SYMBOLS)
@@ -1063,8 +1063,30 @@ def coupling_planes_ctx_prefix(ctx, ctx_stride, w_ctx, b_ctx) -> "Op":
     return op
 
 
+def coupling_vctx_op(op, ctx, ld_ctx, ctx_dim, w_ctx_t, ldw_ctx, b_ctx, device):
+    """usf_coupling_additive_vctx_f32: usf_coupling_additive_f32 with a vector context (ctx None: exactly coupling_op)"""
+    _launch("usf_coupling_additive_vctx_f32", (C.byref(op.u.coupling), ptr(ctx), int(ld_ctx), int(ctx_dim), ptr(w_ctx_t),
+                                               int(ldw_ctx), ptr(b_ctx), current_stream(device)), (op, ctx, w_ctx_t, b_ctx))
+
+
+def coupling_vctx_variant(op, ctx_dim: int) -> int:
+    """which kernel usf_coupling_additive_vctx_f32 launches for the op's descriptor with a context of ctx_dim columns"""
+    return int(load().usf_coupling_additive_vctx_variant(C.byref(op.u.coupling), int(ctx_dim)))
+
+
+def coupling_vctx_prefix(ctx, ld_ctx, ctx_dim, w_ctx_t, ldw_ctx, b_ctx) -> "Op":
+    """the USF_OP_CALL op (USF_FN_COUPLING_VCTX) that hands the USF_OP_COUPLING op behind it its vector context"""
+    op = Op()
+    op.kind = OP_CALL
+    op.u.call.fn, op.u.call.n_args = FN_COUPLING_VCTX, 6
+    for j, w in enumerate((ctx.data_ptr(), int(ld_ctx), int(ctx_dim), w_ctx_t.data_ptr(), int(ldw_ctx), b_ctx.data_ptr())):
+        op.u.call.a[j] = w
+    return op
+
+
 def is_ctx_prefix(op) -> bool:
-    return op.kind == OP_CALL and op.u.call.fn == FN_COUPLING_PLANES_CTX
+    """a USF_OP_CALL op that only carries the context arguments of the op behind it (the pair is one launch)"""
+    return op.kind == OP_CALL and op.u.call.fn in (FN_COUPLING_PLANES_CTX, FN_COUPLING_VCTX)
 
 
 def run_ops(ops_array, n, device=None):
@@ -1255,6 +1277,9 @@ def wgrad(Y, A, G, *, M, N, K, ldy, lda, ldg, y_off=0, a_off=0, g_off=0, alpha=1
     """G[n,k] = alpha * sum_m Y[m,n] A[m,k] + beta * G (element offsets *_off into the fp32 tensors).  Inside a
     ``batch_jobs(defer_grads=True)`` block a small-batch call is queued (same arithmetic: see usf_grad_jobs_f32).
     colsum [N] (only where ``wgrad_bias_ok``): cs_alpha * sum_m Y[m,n] + cs_beta * colsum from the same pass (usf_wgrad_bias_f32)"""
+    if ldg < K or G.numel() - g_off < (N - 1) * ldg + K:
+        # (checked here for every form of the call: a queued usf_grad_jobs_f32 job is not validated by the library)
+        raise ValueError(f"wgrad: gradient image too small (ldg {ldg}, {G.numel() - g_off} floats) for N = {N}, K = {K}")
     lib = load()
     if colsum is not None:
         ws = _workspace(Y.device, lib.usf_wgrad_workspace_floats(M, N, K))

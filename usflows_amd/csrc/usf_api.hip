@@ -60,8 +60,8 @@ void set_error(const char* fmt, ...) {
 
 int linear_dispatch(const usf_linear_desc* d, hipStream_t stream);
 int linear_variant(const usf_linear_desc* d);
-int coupling_dispatch(const usf_coupling_desc* d, hipStream_t stream);
-int coupling_variant(const usf_coupling_desc* d);
+int coupling_dispatch(const usf_coupling_desc* d, hipStream_t stream, const CplVctx* v = nullptr);
+int coupling_variant(const usf_coupling_desc* d, int ctx_dim = 0);
 int coupling_max_width();
 int coupling_padded_width(int h);
 int lu_grad_finish(const double* dL, const double* dU, const double* TL, const double* TU, const double* c, const double* tri,
@@ -254,6 +254,14 @@ int usf_coupling_planes_ctx(const usf_coupling_planes_desc* d, const float* ctx,
 }
 int usf_gemm_planes_variant(const usf_gemm_planes_desc* d) { return usf::gemm_planes_variant(d); }
 int usf_coupling_variant(const usf_coupling_desc* d) { return usf::coupling_variant(d); }
+int usf_coupling_additive_vctx_f32(const usf_coupling_desc* d, const float* ctx, int64_t ld_ctx, int32_t ctx_dim, const float* W_ctx_t,
+                                   int64_t ldw_ctx, const float* b_ctx, usf_stream_t stream) {
+  const usf::CplVctx v = {ctx, ld_ctx, (int)ctx_dim, W_ctx_t, ldw_ctx, b_ctx};
+  return usf::coupling_dispatch(d, (hipStream_t)stream, &v);
+}
+int usf_coupling_additive_vctx_variant(const usf_coupling_desc* d, int32_t ctx_dim) {
+  return usf::coupling_variant(d, (ctx_dim > 0 && ctx_dim <= USF_VCTX_MAX) ? (int)ctx_dim : 0);
+}
 int usf_coupling_max_width(void) { return usf::coupling_max_width(); }
 int usf_coupling_padded_width(int h) { return usf::coupling_padded_width(h); }
 
@@ -645,6 +653,20 @@ int usf_run_ops(const usf_op* ops, int32_t n_ops, usf_stream_t stream) {
           rc = usf::coupling_planes_ctx(&ops[i + 1].u.coupling_planes, reinterpret_cast<const float*>((uintptr_t)c->a[0]), (int64_t)c->a[1],
                                         reinterpret_cast<const float*>((uintptr_t)c->a[2]), reinterpret_cast<const float*>((uintptr_t)c->a[3]),
                                         (hipStream_t)stream);
+          ++i;
+          break;
+        }
+        if (ops[i].u.call.fn == USF_FN_COUPLING_VCTX) {
+          // the vector context of the USF_OP_COUPLING op that follows (usflows_hip_internal.h): one launch for the pair
+          const usf_call_desc* c = &ops[i].u.call;
+          if (c->n_args != 6 || i + 1 >= n_ops || ops[i + 1].kind != USF_OP_COUPLING) {
+            usf::set_error("usf_run_ops: op %d (USF_FN_COUPLING_VCTX) needs 6 arguments and a USF_OP_COUPLING op behind it", i);
+            return -2;
+          }
+          const usf::CplVctx v = {reinterpret_cast<const float*>((uintptr_t)c->a[0]), (int64_t)c->a[1], (int)(int64_t)c->a[2],
+                                  reinterpret_cast<const float*>((uintptr_t)c->a[3]), (int64_t)c->a[4],
+                                  reinterpret_cast<const float*>((uintptr_t)c->a[5])};
+          rc = usf::coupling_dispatch(&ops[i + 1].u.coupling, (hipStream_t)stream, &v);
           ++i;
           break;
         }

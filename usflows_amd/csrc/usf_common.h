@@ -56,6 +56,51 @@ __device__ __forceinline__ float act_apply(float v, int act, float slope) {
 // USF_ACT_GATE: leaky_relu_backward from the saved OUTPUT h (as usf_act_grad_f32: h > 0 ? v : v * slope)
 __device__ __forceinline__ float gate_apply(float v, float h, float slope) { return (h > 0.0f) ? v : v * slope; }
 
+// The vector context of usf_coupling_additive_vctx_f32 (usflows_hip_internal.h), validated by coupling_dispatch; nullptr or
+// ctx == nullptr: no vector context
+struct CplVctx {
+  const float* ctx; int64_t ld_ctx; int ctx_dim;
+  const float* W_ctx_t; int64_t ldw_ctx; const float* b_ctx;
+};
+// X[ht][t] += b_ctx[h] + sum_{c < C} ctx[row, c] * W_ctx_t[c, h]  for h = 16 ht + 4 lg + t: the accumulator layout of the fused
+// coupling kernels (a lane's four consecutive hidden units = one 16-byte load per context column).  The sum runs over c in
+// ascending order in fp32 and is added to the pre-activation as ONE term (networks.py:741-743: layers[0](x) + layers[1](context)).
+// crow: the row's context columns, 16-byte aligned; whole groups of four are loaded, so the padding columns [C, round_up(C, 4))
+// are read but never enter the arithmetic.  Four hidden tiles at a time: 16 running sums, the weight loads of a group of four
+// columns in flight together.
+template <int T>
+__device__ __forceinline__ void vctx_add(f32x4 (&X)[T], const float* crow, int C, const float* Wt, int64_t ldw, const float* bc,
+                                         int lg) {
+  constexpr int G = T < 4 ? T : 4;
+#pragma unroll
+  for (int h0 = 0; h0 < T; h0 += G) {
+    f32x4 s[G];
+#pragma unroll
+    for (int i = 0; i < G; ++i) s[i] = *reinterpret_cast<const f32x4*>(bc + (h0 + i) * 16 + 4 * lg);
+    const float* w = Wt + h0 * 16 + 4 * lg;
+    int c = 0;
+#pragma unroll 1
+    for (; c + 4 <= C; c += 4) {
+      const f32x4 cv = *reinterpret_cast<const f32x4*>(crow + c);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int i = 0; i < G; ++i) s[i] += cv[e] * *reinterpret_cast<const f32x4*>(w + (int64_t)(c + e) * ldw + 16 * i);
+    }
+    if (c < C) {
+      const f32x4 cv = *reinterpret_cast<const f32x4*>(crow + c);
+#pragma unroll
+      for (int e = 0; e < 3; ++e)
+        if (c + e < C) {
+#pragma unroll
+          for (int i = 0; i < G; ++i) s[i] += cv[e] * *reinterpret_cast<const f32x4*>(w + (int64_t)(c + e) * ldw + 16 * i);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < G; ++i) X[h0 + i] += s[i];
+  }
+}
+
 // The context channel of a conditional conditioner's first convolution (usf_conv2d_same_ctx_f32): a constant plane ctx[b]
 // under zero padding contributes ctx[b] * S[co, p] with S = the sum of the channel's taps that land inside the image at p.
 // ctx_tapmask: bit t (t = dy * ks + dx) set when tap t of output pixel (py, px) reads inside the H x W image.

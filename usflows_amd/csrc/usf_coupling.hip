@@ -46,8 +46,21 @@ struct CplArgs {
 //    software-pipelined two tiles ahead of the MFMAs that consume them;
 //  * no clamps / selects on the weight loads: a thread's NST loads of a stage sit at constant
 //    strides from one per-thread pointer.
+//
+// USF_VCTX (usf_coupling_vctx.hip includes this file with it defined): the same kernel text compiled a second time as
+// coupling_vctx_kernel -- the vector-context form of usf_coupling_additive_vctx_f32, whose layer-0 context step is vctx_add
+// (usf_common.h) -- in a translation unit of its own, so that this one compiles to what it was before that form existed.
+#ifdef USF_VCTX
+// W_ctx = the transposed context weights [ctx_dim, ldw_ctx], ctx = rows of ld_ctx floats (0: one row for all)
+struct CplArgsV : CplArgs { int64_t ld_ctx, ldw_ctx; int ctx_dim; };
+#define CPL_KERNEL coupling_vctx_kernel
+#define CPL_KARGS CplArgsV
+#else
+#define CPL_KERNEL coupling_kernel
+#define CPL_KARGS CplArgs
+#endif
 template <int NH, int T>
-__global__ __launch_bounds__(256, 2) void coupling_kernel(const CplArgs p) {
+__global__ __launch_bounds__(256, 2) void CPL_KERNEL(const CPL_KARGS p) {
   constexpr int HP = 16 * T;               // padded hidden width
   constexpr int NST = T / 2;               // float4 staged per thread per stage (HP*32/4/256)
   constexpr int BUF = HP * CPL_BK;         // floats per stage buffer
@@ -231,7 +244,12 @@ __global__ __launch_bounds__(256, 2) void coupling_kernel(const CplArgs p) {
     }
   };
   CSTAMP(c1);
+#ifdef USF_VCTX
+  vctx_add<T>(X1, p.ctx + (int64_t)rowc * p.ld_ctx, p.ctx_dim, p.W_ctx, p.ldw_ctx, p.b_ctx, lg);
+  ctx_act(X1, false);
+#else
   ctx_act(X1, p.ctx != nullptr);
+#endif
   CSTAMP(c2);
 
   // ================= phase 2: Xout[h2][row] += W_h[h2][h1] * Xin[h1][row] ====================
@@ -336,6 +354,28 @@ __global__ __launch_bounds__(256, 2) void coupling_kernel(const CplArgs p) {
 #endif
 }
 
+#define USF_CPL_T(NHV) do { if (hmax <= 64) USF_CPL(NHV, 4); else if (hmax <= 128) USF_CPL(NHV, 8); else USF_CPL(NHV, 16); } while (0)
+
+#ifdef USF_VCTX
+// the vector-context launch: a = the arguments coupling_dispatch built and checked, v = its checked context
+int coupling_vctx_launch(const CplArgs& a, const CplVctx* v, int n_hidden, int hmax, dim3 grid, hipStream_t stream) {
+  CplArgsV av;
+  static_cast<CplArgs&>(av) = a;
+  av.ctx = v->ctx; av.W_ctx = v->W_ctx_t; av.b_ctx = v->b_ctx;
+  av.ld_ctx = v->ld_ctx; av.ldw_ctx = v->ldw_ctx; av.ctx_dim = v->ctx_dim;
+  const dim3 block(256);
+#define USF_CPL(NHV, TV) hipLaunchKernelGGL((coupling_vctx_kernel<NHV, TV>), grid, block, 0, stream, av)
+  switch (n_hidden) {
+    case 1: USF_CPL_T(1); break;
+    case 2: USF_CPL_T(2); break;
+    default: USF_CPL_T(3); break;
+  }
+#undef USF_CPL
+  return check_launch("usf_coupling_additive_vctx_f32");
+}
+#else
+int coupling_vctx_launch(const CplArgs& a, const CplVctx* v, int n_hidden, int hmax, dim3 grid, hipStream_t stream);
+
 #ifdef USF_STAMP
 unsigned long long* g_cdbg = nullptr;
 #endif
@@ -347,18 +387,42 @@ int coupling_padded_width(int h) { return (h < 1 || h > CPL_HMAX) ? -1 : padded_
 int coupling_max_width() { return CPL_HMAX; }
 
 bool coupling_bf16x3_eligible(const usf_coupling_desc* d);
-int coupling_bf16x3_dispatch(const usf_coupling_desc* d, hipStream_t stream);
-bool coupling_tiny_eligible(const usf_coupling_desc* d);       // usf_coupling_tiny.hip
-int coupling_tiny_dispatch(const usf_coupling_desc* d, hipStream_t stream);
+int coupling_bf16x3_dispatch(const usf_coupling_desc* d, hipStream_t stream, const CplVctx* v);
+bool coupling_tiny_eligible(const usf_coupling_desc* d, int ctx_dim);       // usf_coupling_tiny.hip (ctx_dim 0: no vector context)
+int coupling_tiny_dispatch(const usf_coupling_desc* d, hipStream_t stream, const CplVctx* v);
 
-int coupling_variant(const usf_coupling_desc* d) {
+// ctx_dim > 0: the descriptor with a vector context of that width (usf_coupling_additive_vctx_variant)
+int coupling_variant(const usf_coupling_desc* d, int ctx_dim) {
   if (!d) return 0;
-  if (d->M >= 0 && d->n_pass > 0 && d->n_trans > 0 && d->n_hidden >= 1 && d->n_hidden <= 3 && coupling_tiny_eligible(d)) return 3;
+  if (d->M >= 0 && d->n_pass > 0 && d->n_trans > 0 && d->n_hidden >= 1 && d->n_hidden <= 3 && coupling_tiny_eligible(d, ctx_dim)) return 3;
   return coupling_bf16x3_eligible(d) ? 2 : 1;
 }
 
-int coupling_dispatch(const usf_coupling_desc* d, hipStream_t stream) {
+// the vector context of usf_coupling_additive_vctx_f32, checked before anything is launched
+static int vctx_check(const usf_coupling_desc* d, const CplVctx* v) {
+  if (d->context || d->W_ctx || d->b_ctx) {
+    set_error("usf_coupling_additive_vctx_f32: the descriptor's own context / W_ctx / b_ctx must be NULL");
+    return -2;
+  }
+  if (d->act == USF_ACT_GATE) { set_error("usf_coupling_additive_vctx_f32: USF_ACT_GATE takes no context (the context enters no data gradient)"); return -2; }
+  if (v->ctx_dim < 1 || v->ctx_dim > USF_VCTX_MAX) {
+    set_error("usf_coupling_additive_vctx_f32: ctx_dim %d outside 1..%d", v->ctx_dim, USF_VCTX_MAX);
+    return -2;
+  }
+  if (!v->W_ctx_t || !v->b_ctx) { set_error("usf_coupling_additive_vctx_f32: context needs W_ctx_t and b_ctx"); return -1; }
+  const int64_t c4 = (v->ctx_dim + 3) / 4 * 4;
+  if (!aligned16(v->ctx) || !aligned16(v->W_ctx_t) || !aligned16(v->b_ctx) || (v->ld_ctx & 3) || (v->ldw_ctx & 3) ||
+      (v->ld_ctx != 0 && v->ld_ctx < c4) || v->ldw_ctx < 4) {
+    set_error("usf_coupling_additive_vctx_f32: ctx / W_ctx_t / b_ctx must be 16-byte aligned, ld_ctx 0 or a multiple of 4 >= "
+              "round_up(ctx_dim, 4), ldw_ctx a multiple of 4");
+    return -2;
+  }
+  return 0;
+}
+
+int coupling_dispatch(const usf_coupling_desc* d, hipStream_t stream, const CplVctx* v) {
   if (!d) { set_error("usf_coupling_additive_f32: null descriptor"); return -1; }
+  if (v && !v->ctx) v = nullptr;                                  // ctx == NULL: exactly usf_coupling_additive_f32
   if (d->M < 0 || d->M > 0x7fffffff || d->n_pass <= 0 || d->n_trans <= 0 || d->n_hidden < 1 || d->n_hidden > 3) {
     set_error("usf_coupling_additive_f32: bad sizes (M=%lld n_pass=%lld n_trans=%lld n_hidden=%d; fused kernel "
               "supports 1..3 hidden layers)", (long long)d->M, (long long)d->n_pass, (long long)d->n_trans, d->n_hidden);
@@ -368,15 +432,33 @@ int coupling_dispatch(const usf_coupling_desc* d, hipStream_t stream) {
   if (!d->z || !d->out || !d->W_in || !d->b_in || !d->W_out || !d->b_out) { set_error("usf_coupling_additive_f32: null pointer"); return -1; }
   if (d->out != d->z || d->ldo != d->ldz) { set_error("usf_coupling_additive_f32: this version works in place (out == z)"); return -2; }
   if (d->act != USF_ACT_NONE && d->act != USF_ACT_LEAKY_RELU && d->act != USF_ACT_GATE) { set_error("usf_coupling_additive_f32: bad act"); return -2; }
+  if (v) {
+    const int rc = vctx_check(d, v);
+    if (rc != 0) return rc;
+    for (int i = 0; i < d->n_hidden; ++i)
+      if (d->hidden[i] < 1 || d->hidden[i] > CPL_HMAX) { set_error("usf_coupling_additive_vctx_f32: hidden width %d must be in [1, %d]", d->hidden[i], CPL_HMAX); return -2; }
+  }
   // tiny layers at launch-bound batches (M <= 256: disjoint from the bf16x3 kernel's M >= 1024): scalar accesses, no alignment rules
-  if (coupling_tiny_eligible(d)) return coupling_tiny_dispatch(d, stream);
+  if (coupling_tiny_eligible(d, v ? v->ctx_dim : 0)) {
+    if (v && v->ldw_ctx < d->hidden[0]) { set_error("usf_coupling_additive_vctx_f32: ldw_ctx %lld below the first hidden width", (long long)v->ldw_ctx); return -2; }
+    return coupling_tiny_dispatch(d, stream, v);
+  }
   if ((d->n_pass & 3) || (d->off_pass & 3) || (d->off_trans & 3) || (d->ldz & 3) || d->off_trans + ((d->n_trans + 3) / 4) * 4 > d->ldz || (d->ldw_in & 3) || (d->ldw_out & 3) || !aligned16(d->z) ||
       !aligned16(d->W_in) || !aligned16(d->W_out) || !aligned16(d->b_in)) {
     set_error("usf_coupling_additive_f32: n_pass/off_pass/ldz/ldw must be multiples of 4 and pointers 16-byte aligned");
     return -2;
   }
   if (d->act != USF_ACT_NONE && d->act != USF_ACT_LEAKY_RELU && d->act != USF_ACT_GATE) { set_error("usf_coupling_additive_f32: bad act"); return -2; }
-  if (coupling_bf16x3_eligible(d)) return coupling_bf16x3_dispatch(d, stream);
+  if (v) {
+    // both MFMA kernels read W_ctx_t / b_ctx over the padded hidden width (zeros beyond the real one)
+    int hm = 0;
+    for (int i = 0; i < d->n_hidden; ++i) hm = d->hidden[i] > hm ? d->hidden[i] : hm;
+    if (v->ldw_ctx < padded_width(hm)) {
+      set_error("usf_coupling_additive_vctx_f32: padding contract violated (ldw_ctx %lld < %d)", (long long)v->ldw_ctx, padded_width(hm));
+      return -2;
+    }
+  }
+  if (coupling_bf16x3_eligible(d)) return coupling_bf16x3_dispatch(d, stream, v);
   if (d->hidden_out[0] || d->act == USF_ACT_GATE) { set_error("usf_coupling_additive_f32: hidden_out / USF_ACT_GATE are served by the bf16x3 kernel (split planes, hidden width in (128, 256], M >= 1024) and by the tiny-layer kernel (M <= 256, segments <= 64, hidden <= 64) only"); return -2; }
   CplArgs a;
   a.z = d->z; a.out = d->out; a.ldz = d->ldz;
@@ -417,16 +499,17 @@ int coupling_dispatch(const usf_coupling_desc* d, hipStream_t stream) {
   a.dbg = g_cdbg;
 #endif
   const dim3 grid((unsigned)((d->M + CPL_ROWS - 1) / CPL_ROWS)), block(256);
+  if (v) return coupling_vctx_launch(a, v, d->n_hidden, hmax, grid, stream);
 #define USF_CPL(NHV, TV) hipLaunchKernelGGL((coupling_kernel<NHV, TV>), grid, block, 0, stream, a)
-#define USF_CPL_T(NHV) do { if (hmax <= 64) USF_CPL(NHV, 4); else if (hmax <= 128) USF_CPL(NHV, 8); else USF_CPL(NHV, 16); } while (0)
   switch (d->n_hidden) {
     case 1: USF_CPL_T(1); break;
     case 2: USF_CPL_T(2); break;
     default: USF_CPL_T(3); break;
   }
-#undef USF_CPL_T
 #undef USF_CPL
   return check_launch("usf_coupling_additive_f32");
 }
+#endif  // USF_VCTX
+#undef USF_CPL_T
 
 }  // namespace usf

@@ -61,8 +61,20 @@ __device__ __forceinline__ void c3_split3(const f32x4 x0, const f32x4 x1, bf16x8
     ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(W1, A1, ACC, 0, 0, 0);        \
   } while (0)
 
+// USF_VCTX (usf_coupling_vctx.hip includes this file with it defined): the same kernel text compiled a second time as
+// coupling_bf16x3_vctx_kernel -- the vector-context form of usf_coupling_additive_vctx_f32, whose layer-0 context step is
+// vctx_add (usf_common.h) -- in a translation unit of its own, so that this one compiles to what it was before that form existed.
+#ifdef USF_VCTX
+// W_ctx = the transposed context weights [ctx_dim, ldw_ctx], ctx = rows of ld_ctx floats (0: one row for all)
+struct Cpl3ArgsV : Cpl3Args { int64_t ld_ctx, ldw_ctx; int ctx_dim; };
+#define C3_KERNEL coupling_bf16x3_vctx_kernel
+#define C3_KARGS Cpl3ArgsV
+#else
+#define C3_KERNEL coupling_bf16x3_kernel
+#define C3_KARGS Cpl3Args
+#endif
 template <int NH, int T>
-__global__ __launch_bounds__(C3_NT, 2) void coupling_bf16x3_kernel(const Cpl3Args p) {
+__global__ __launch_bounds__(C3_NT, 2) void C3_KERNEL(const C3_KARGS p) {
   constexpr int HP = 16 * T;               // padded hidden width
   constexpr int KS = T / 2;                // 32-k steps over a hidden layer
   constexpr int SLOTS = 3 * 4 * HP;        // 16-B slots per stage (k-slab: 3 planes x 4 chunks x HP rows;
@@ -285,7 +297,12 @@ __global__ __launch_bounds__(C3_NT, 2) void coupling_bf16x3_kernel(const Cpl3Arg
       }
     }
   };
+#ifdef USF_VCTX
+  vctx_add<T>(X1, p.ctx + (int64_t)rowc * p.ld_ctx, p.ctx_dim, p.W_ctx, p.ldw_ctx, p.b_ctx, lg);
+  ctx_act(X1, false, 0);
+#else
   ctx_act(X1, p.ctx != nullptr, 0);
+#endif
   // training: the hidden activations go to HBM for the backward pass (lane (j, g) holds units 16 ht + 4 g .. + 3 of row j)
   auto save_hidden = [&](const f32x4 (&X)[T], float* H) {
     if (H == nullptr || wrow0 + lj >= p.M) return;
@@ -414,6 +431,24 @@ __global__ __launch_bounds__(C3_NT, 2) void coupling_bf16x3_kernel(const Cpl3Arg
 #endif
 }
 
+#ifdef USF_VCTX
+// the vector-context launch: a = the arguments coupling_bf16x3_dispatch built and checked, v = the context coupling_dispatch checked
+int coupling_bf16x3_vctx_launch(const Cpl3Args& a, const CplVctx* v, int n_hidden, dim3 grid, hipStream_t stream) {
+  Cpl3ArgsV av;
+  static_cast<Cpl3Args&>(av) = a;
+  av.ctx = v->ctx; av.W_ctx = v->W_ctx_t; av.b_ctx = v->b_ctx;
+  av.ld_ctx = v->ld_ctx; av.ldw_ctx = v->ldw_ctx; av.ctx_dim = v->ctx_dim;
+  const dim3 block(C3_NT);
+  switch (n_hidden) {
+    case 1: hipLaunchKernelGGL((coupling_bf16x3_vctx_kernel<1, 16>), grid, block, 0, stream, av); break;
+    case 2: hipLaunchKernelGGL((coupling_bf16x3_vctx_kernel<2, 16>), grid, block, 0, stream, av); break;
+    default: hipLaunchKernelGGL((coupling_bf16x3_vctx_kernel<3, 16>), grid, block, 0, stream, av); break;
+  }
+  return check_launch("usf_coupling_additive_vctx_f32(bf16x3)");
+}
+#else
+int coupling_bf16x3_vctx_launch(const Cpl3Args& a, const CplVctx* v, int n_hidden, dim3 grid, hipStream_t stream);
+
 #ifdef USF_STAMP
 unsigned long long* g_c3dbg = nullptr;
 #endif
@@ -427,7 +462,7 @@ bool coupling_bf16x3_eligible(const usf_coupling_desc* d) {
   return hmax > 128 && hmax <= C3_HMAX && d->M >= 1024;     // instantiated for the 256-wide tile set only
 }
 
-int coupling_bf16x3_dispatch(const usf_coupling_desc* d, hipStream_t stream) {
+int coupling_bf16x3_dispatch(const usf_coupling_desc* d, hipStream_t stream, const CplVctx* v) {
   Cpl3Args a;
   a.z = d->z; a.out = d->out; a.ldz = d->ldz;
   a.M = (int)d->M; a.off_pass = (int)d->off_pass; a.n_pass = (int)d->n_pass; a.off_trans = (int)d->off_trans;
@@ -483,6 +518,7 @@ int coupling_bf16x3_dispatch(const usf_coupling_desc* d, hipStream_t stream) {
     return -2;
   }
   const dim3 grid((unsigned)((d->M + C3_ROWS - 1) / C3_ROWS)), block(C3_NT);
+  if (v) return coupling_bf16x3_vctx_launch(a, v, d->n_hidden, grid, stream);   // (v: validated by coupling_dispatch, usf_coupling.hip)
   switch (d->n_hidden) {
     case 1: hipLaunchKernelGGL((coupling_bf16x3_kernel<1, 16>), grid, block, 0, stream, a); break;
     case 2: hipLaunchKernelGGL((coupling_bf16x3_kernel<2, 16>), grid, block, 0, stream, a); break;
@@ -490,5 +526,6 @@ int coupling_bf16x3_dispatch(const usf_coupling_desc* d, hipStream_t stream) {
   }
   return check_launch("usf_coupling_additive_f32(bf16x3)");
 }
+#endif  // USF_VCTX
 
 }  // namespace usf

@@ -105,8 +105,24 @@ __device__ __forceinline__ void tiny_store4(const TinySeg& s, float* lds, const 
 // NW: 16-byte groups per thread of the largest weight image, NS: elements per thread of the largest row segment (inputs, residual,
 // gates) -- the staging code is straight-line and runs once per launch, cold: the small instantiation (<= 32 x 32 layers, the
 // live flat configuration) is a third of the large one's code
+// USF_VCTX (usf_coupling_vctx.hip includes this file with it defined): the same kernel text compiled a second time as
+// coupling_tiny_vctx_kernel -- the vector-context form of usf_coupling_additive_vctx_f32: the ctx segment holds the rows' cdim
+// context columns ([32, cdim], up to 1024 elements), the wctx segment the transposed context weights [cdim, hidden[0]] (up to
+// 2048) -- in a translation unit of its own, so that this one compiles to what it was before that form existed.
+#ifdef USF_VCTX
+struct TinyArgsV : TinyArgs { int cdim; };
+#define TINY_KERNEL coupling_tiny_vctx_kernel
+#define TINY_KARGS TinyArgsV
+#define TINY_NVC 4
+#define TINY_NVW 8
+#else
+#define TINY_KERNEL coupling_tiny_kernel
+#define TINY_KARGS TinyArgs
+#define TINY_NVC 1
+#define TINY_NVW 1
+#endif
 template <int NW, int NS>
-__global__ __launch_bounds__(256) void coupling_tiny_kernel(const TinyArgs p) {
+__global__ __launch_bounds__(256) void TINY_KERNEL(const TINY_KARGS p) {
   extern __shared__ __attribute__((aligned(16))) float tl[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lj = lane & 15, lg = lane >> 4;
@@ -114,7 +130,7 @@ __global__ __launch_bounds__(256) void coupling_tiny_kernel(const TinyArgs p) {
   const bool gated = p.act == USF_ACT_GATE;
   // ---- everything the layer reads, ONE batch of loads: the arithmetic of a layer is far too short to hide a second round trip ----
   f32x4 vw[4][NW];
-  float vx[NS], vz[NS], vb[4][1], vg[3][NS], vc[1], vwc[1], vbc[1];
+  float vx[NS], vz[NS], vb[4][1], vg[3][NS], vc[TINY_NVC], vwc[TINY_NVW], vbc[1];
 #pragma unroll
   for (int l = 0; l < 4; ++l)
     if (l <= p.nh) { tiny_load4<NW>(p.w[l], vw[l]); tiny_load<1>(p.b[l], row0, p.M, vb[l]); }
@@ -125,7 +141,7 @@ __global__ __launch_bounds__(256) void coupling_tiny_kernel(const TinyArgs p) {
     for (int l = 0; l < 3; ++l)
       if (l < p.nh) tiny_load<NS>(p.g[l], row0, p.M, vg[l]);
   }
-  if (p.has_ctx) { tiny_load<1>(p.ctx, row0, p.M, vc); tiny_load<1>(p.wctx, row0, p.M, vwc); tiny_load<1>(p.bctx, row0, p.M, vbc); }
+  if (p.has_ctx) { tiny_load<TINY_NVC>(p.ctx, row0, p.M, vc); tiny_load<TINY_NVW>(p.wctx, row0, p.M, vwc); tiny_load<1>(p.bctx, row0, p.M, vbc); }
   // zero the padded images while the loads fly (weight rows beyond the layer's width, inputs beyond K, activations beyond the widths)
   for (int e = tid; e < (p.zoff >> 2); e += 256) reinterpret_cast<f32x4*>(tl)[e] = (f32x4){0.f, 0.f, 0.f, 0.f};
   __syncthreads();
@@ -139,7 +155,7 @@ __global__ __launch_bounds__(256) void coupling_tiny_kernel(const TinyArgs p) {
     for (int l = 0; l < 3; ++l)
       if (l < p.nh) tiny_store<NS>(p.g[l], tl, vg[l]);
   }
-  if (p.has_ctx) { tiny_store<1>(p.ctx, tl, vc); tiny_store<1>(p.wctx, tl, vwc); tiny_store<1>(p.bctx, tl, vbc); }
+  if (p.has_ctx) { tiny_store<TINY_NVC>(p.ctx, tl, vc); tiny_store<TINY_NVW>(p.wctx, tl, vwc); tiny_store<1>(p.bctx, tl, vbc); }
   __syncthreads();
   const float* hin = tl + p.xoff;
   int ldin = p.xld;
@@ -171,7 +187,17 @@ __global__ __launch_bounds__(256) void coupling_tiny_kernel(const TinyArgs p) {
           if (gated) {
             v = v * (tl[p.goff[l] + r * H + u] > 0.f ? 1.f : p.slope);
           } else {
+#ifdef USF_VCTX
+            if (l == 0) {                                           // b_ctx[u] + sum_c ctx[r, c] W_ctx_t[c, u], c ascending
+              float sc = tl[p.bcoff + u];
+              const float* cr = tl + p.coff + r * p.cdim;
+              const float* wc = tl + p.wcoff + u;
+              for (int c = 0; c < p.cdim; ++c) sc += cr[c] * wc[c * H];
+              v = v + sc;
+            }
+#else
             if (l == 0 && p.has_ctx) v = v + (tl[p.coff + r] * tl[p.wcoff + u] + tl[p.bcoff + u]);          // networks.py:741-743
+#endif
             v = act_apply(v, p.act, p.slope);
           }
           hout[r * TINY_HS + u] = v;
@@ -187,6 +213,20 @@ __global__ __launch_bounds__(256) void coupling_tiny_kernel(const TinyArgs p) {
     ldin = TINY_HS;
   }
 }
+
+#ifdef USF_VCTX
+// the vector-context launch: a = the arguments coupling_tiny_dispatch built (ctx / wctx segments for cdim columns)
+int coupling_tiny_vctx_launch(const TinyArgs& a, int cdim, bool small, dim3 grid, size_t lds_bytes, hipStream_t stream) {
+  TinyArgsV av;
+  static_cast<TinyArgs&>(av) = a;
+  av.cdim = cdim;
+  const dim3 block(256);
+  if (small) hipLaunchKernelGGL((coupling_tiny_vctx_kernel<1, 4>), grid, block, lds_bytes, stream, av);
+  else hipLaunchKernelGGL((coupling_tiny_vctx_kernel<TINY_NV4, 8>), grid, block, lds_bytes, stream, av);
+  return check_launch("usf_coupling_additive_vctx_f32(tiny)");
+}
+#else
+int coupling_tiny_vctx_launch(const TinyArgs& a, int cdim, bool small, dim3 grid, size_t lds_bytes, hipStream_t stream);
 
 static inline int r4(int64_t v) { return (int)((v + 3) / 4 * 4); }
 
@@ -204,7 +244,9 @@ static int64_t tiny_lds_floats(const usf_coupling_desc* d) {
 }
 
 // the descriptor has passed coupling_dispatch's basic checks (usf_coupling.hip)
-bool coupling_tiny_eligible(const usf_coupling_desc* d) {
+// ctx_dim > 0: with a vector context of that width -- its segments ([32, ctx_dim] rows, [ctx_dim, hidden[0]] weights) take the
+// place of the scalar form's (32 values, 64 weights) in the LDS budget: a layer that no longer fits goes to the MFMA kernels
+bool coupling_tiny_eligible(const usf_coupling_desc* d, int ctx_dim) {
   if (!tuning("coupling_tiny", 1) || d->M > TINY_MAX_M || d->n_pass > TINY_MAXW || d->n_trans > TINY_MAXW) return false;
   for (int i = 0; i < d->n_hidden; ++i)
     if (d->hidden[i] < 1 || d->hidden[i] > TINY_MAXW) return false;
@@ -217,10 +259,11 @@ bool coupling_tiny_eligible(const usf_coupling_desc* d) {
     if (!W || !aligned16(W) || (ldw & 3) || ldw < r4(k)) return false;
     k = i == d->n_hidden ? d->n_trans : d->hidden[i];
   }
-  return tiny_lds_floats(d) * 4 <= 64 * 1024;
+  const int64_t extra = ctx_dim > 0 ? (int64_t)TINY_ROWS * (ctx_dim - 1) + (int64_t)ctx_dim * d->hidden[0] - TINY_MAXW : 0;
+  return (tiny_lds_floats(d) + extra) * 4 <= 64 * 1024;
 }
 
-int coupling_tiny_dispatch(const usf_coupling_desc* d, hipStream_t stream) {
+int coupling_tiny_dispatch(const usf_coupling_desc* d, hipStream_t stream, const CplVctx* v) {
   if (d->off_pass < 0 || d->off_trans < 0 || d->off_pass + d->n_pass > d->ldz || d->off_trans + d->n_trans > d->ldz) {
     set_error("usf_coupling_additive_f32: column segments outside the rows (ldz %lld)", (long long)d->ldz);
     return -2;
@@ -279,18 +322,28 @@ int coupling_tiny_dispatch(const usf_coupling_desc* d, hipStream_t stream) {
   if ((want_h && a.ld_hout < hmax) || (gated && d->ld_gate < hmax)) { set_error("usf_coupling_additive_f32: ld_hidden_out / ld_gate below the hidden width"); return -2; }
   a.has_ctx = (!gated && d->context != nullptr) ? 1 : 0;
   if (a.has_ctx && (!d->W_ctx || !d->b_ctx)) { set_error("usf_coupling_additive_f32: context needs W_ctx and b_ctx"); return -1; }
-  a.coff = off; a.ctx = seg(a.has_ctx ? d->context : nullptr, 1, TINY_ROWS, 1, off, 1, 1); off += TINY_ROWS;
-  a.wcoff = off; a.wctx = seg(a.has_ctx ? d->W_ctx : nullptr, 0, 1, d->hidden[0], off, d->hidden[0], 0); off += TINY_MAXW;
-  a.bcoff = off; a.bctx = seg(a.has_ctx ? d->b_ctx : nullptr, 0, 1, d->hidden[0], off, d->hidden[0], 0); off += TINY_MAXW;
+  if (v) {                          // validated by coupling_dispatch (usf_coupling.hip): not gated, the descriptor's own context NULL
+    const int cd = v->ctx_dim;
+    a.has_ctx = 1;
+    a.coff = off; a.ctx = seg(v->ctx, v->ld_ctx, TINY_ROWS, cd, off, cd, 1); off += TINY_ROWS * cd;
+    a.wcoff = off; a.wctx = seg(v->W_ctx_t, v->ldw_ctx, cd, d->hidden[0], off, d->hidden[0], 0); off += cd * d->hidden[0];
+    a.bcoff = off; a.bctx = seg(v->b_ctx, 0, 1, d->hidden[0], off, d->hidden[0], 0); off += TINY_MAXW;
+  } else {
+    a.coff = off; a.ctx = seg(a.has_ctx ? d->context : nullptr, 1, TINY_ROWS, 1, off, 1, 1); off += TINY_ROWS;
+    a.wcoff = off; a.wctx = seg(a.has_ctx ? d->W_ctx : nullptr, 0, 1, d->hidden[0], off, d->hidden[0], 0); off += TINY_MAXW;
+    a.bcoff = off; a.bctx = seg(a.has_ctx ? d->b_ctx : nullptr, 0, 1, d->hidden[0], off, d->hidden[0], 0); off += TINY_MAXW;
+  }
   a.sign = d->sign; a.slope = d->slope; a.act = d->act;
   if ((int64_t)off * 4 > 64 * 1024) { set_error("usf_coupling_additive_f32: tiny-layer layout exceeds 64 KB of LDS"); return -3; }
   const dim3 grid((unsigned)((d->M + TINY_ROWS - 1) / TINY_ROWS)), block(256);
   bool small = a.x0.n <= 1024 && a.zres.n <= 1024;
   for (int l = 0; l <= a.nh; ++l) small = small && a.w[l].n <= 256;
   for (int l = 0; l < a.nh; ++l) small = small && a.g[l].n <= 1024;
+  if (v) return coupling_tiny_vctx_launch(a, v->ctx_dim, small, grid, (size_t)off * sizeof(float), stream);
   if (small) hipLaunchKernelGGL((coupling_tiny_kernel<1, 4>), grid, block, (size_t)off * sizeof(float), stream, a);
   else hipLaunchKernelGGL((coupling_tiny_kernel<TINY_NV4, 8>), grid, block, (size_t)off * sizeof(float), stream, a);
   return check_launch("usf_coupling_additive_f32(tiny)");
 }
+#endif  // USF_VCTX
 
 }  // namespace usf

@@ -46,9 +46,10 @@ def _activation_of(f) -> Optional[Tuple[int, float]]:
 
 def conditioner_supported(cond: nn.Module) -> bool:
     if getattr(cond, "consumes_context", False):
-        return False                     # (CondConvNet: the flat plan has no context column)
+        return False                     # (CondConvNet: the flat plan's context columns feed ConditionalDenseNN's layers[1] only)
     if isinstance(cond, ConditionalDenseNN):
-        return cond.context_dim == 1 and _activation_of(cond.f) is not None
+        # the context columns of the workspace: one (the fused kernels' scalar form) up to VCTX_MAX (their vector form)
+        return 1 <= cond.context_dim <= _ext.VCTX_MAX and _activation_of(cond.f) is not None
     if isinstance(cond, DenseNN):
         return cond.count_params == 1 and _activation_of(cond.f) is not None
     if isinstance(cond, ConvNet):        # vector path: plain chain of Linears, or GatedMLP / LayerNormVector blocks
@@ -58,7 +59,7 @@ def conditioner_supported(cond: nn.Module) -> bool:
 
 def conditioner_layers(cond: nn.Module):
     """(first, context layer | None, hidden layers, last) of a DenseNN's / ConditionalDenseNN's ``layers``: the context
-    layer (context_dim 1) sits behind the first"""
+    layer ([h0, context_dim]) sits behind the first"""
     lin = list(cond.layers)
     if isinstance(cond, ConditionalDenseNN):
         return lin[0], lin[1], lin[2:-1], lin[-1]
@@ -102,7 +103,15 @@ def _analyze(layers: Sequence[nn.Module]) -> List[_Step]:
             raise EngineUnsupported(f"layer {type(l).__name__} has no fused device form")
     if not steps:
         raise EngineUnsupported("empty layer list")
+    if len(context_dims(steps)) > 1:
+        raise EngineUnsupported("couplings of one flow disagree on context_dim (one context workspace per plan)")
     return steps
+
+
+def context_dims(steps) -> set:
+    """the context widths of a step list's ConditionalDenseNN conditioners"""
+    return {int(s.module.conditioner.context_dim) for s in steps
+            if s.kind == "coupling" and isinstance(s.module.conditioner, ConditionalDenseNN)}
 
 
 # ---------------------------------------------------------------------------------------------
@@ -378,6 +387,7 @@ class FlowEngine(PlanesPlanMixin):
         self.segp_idx[: self.LD] = seg
         self.natp_idx = torch.full((self.LDnp,), -1, dtype=torch.long)
         self.natp_idx[:D] = torch.arange(D)
+        self.ctx_dim = max(context_dims(self.steps), default=1)      # context columns of the workspace (_analyze: one width per flow)
         self.hmax = 4
         self._general_cond = False       # a conditioner with gate / layer-norm blocks: chain of ops, no fused kernel
         for s in self.steps:
@@ -622,8 +632,9 @@ class FlowEngine(PlanesPlanMixin):
         if cp["has_ctx"]:
             Wc, bc = raw["ctx"]
             rows = self._iarange(h[0], hp[0], dev)
-            # [h0, 4]: context rides in column 0 of a 4-wide K
-            u["W_ctx4"], _ = self._packed(Wc, rows, hp[0], self._iarange(1, 4, dev), 4)
+            # [h0, Cp]: the context rides in columns [0, C) of a K padded to a multiple of 4 (C = 1: column 0 of a 4-wide K)
+            Cp = _round_up(self.ctx_dim, 4)
+            u["W_ctx4"], _ = self._packed(Wc, rows, hp[0], self._iarange(self.ctx_dim, Cp, dev), Cp)
             u["b_ctx"] = self._packed_vec(bc, rows, hp[0])
         cp["unfused"] = u
         return u
@@ -758,8 +769,12 @@ class FlowEngine(PlanesPlanMixin):
                 self._plans.clear()
             z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=device)
             ws = dict(zA=z(B, self.LD), zB=z(B, self.LD), nat=z(B, self.LDn), H1=z(B, self.hmax),
-                      H2=z(B, self.hmax), P=z(B, self.hmax), ctx4=z(B, 4), ctx=z(B),
+                      H2=z(B, self.hmax), P=z(B, self.hmax), ctx4=z(B, _round_up(self.ctx_dim, 4)),
                       sum=torch.zeros(2, dtype=torch.float64, device=device))
+            if self.ctx_dim == 1:
+                ws["ctx"] = z(B)
+            # (ctx4 [B, Cp]: the context rows, 16-byte aligned, columns [C, Cp) zero -- the operand of the unfused plan's context
+            # GEMM and, for C > 1, of the fused kernels' vector form; ctx [B]: the scalar form's column, C == 1 only)
             self._ws[key] = ws
         return ws
 
@@ -1052,7 +1067,9 @@ class FlowEngine(PlanesPlanMixin):
             if not cp.get("general") and self.use_fused_coupling and self._fused_ok(cp) and \
                     (B >= self.fused_min_rows or self.tiny_coupling(cp, B)):
                 op = self._coupling_op(cp, zptr, B, sign, ws if use_ctx else None)
-                if B < self.fused_min_rows and not self._tiny_served(pk, cp, op, ws, i, B, train, device):
+                vctx = use_ctx and self.ctx_dim > 1
+                if B < self.fused_min_rows and not self._tiny_served(pk, cp, op, ws, i, B, train, device,
+                                                                     self.ctx_dim if vctx else 0):
                     op = None
             if cp.get("general"):
                 self._general_coupling_ops(ops, lin_op, pk, cp, ws, zptr, B, sign, device)
@@ -1067,6 +1084,12 @@ class FlowEngine(PlanesPlanMixin):
                         op.u.coupling.hidden_out[j] = hb.data_ptr()
                     op.u.coupling.ld_hidden_out = self.hmax
                     meta[-1]["hidden_saved_fused"] = True
+                if vctx:
+                    # a vector context: the launch becomes usf_coupling_additive_vctx_f32 -- a prefix op carries its arguments
+                    f = cp["fused"]
+                    ops.append(_ext.coupling_vctx_prefix(ws["ctx4"], ws["ctx4"].shape[1], self.ctx_dim, f["W_ctx_t"],
+                                                         f["W_ctx_t"].shape[1], f["b_ctx"]))
+                    meta[-1]["op"] = len(ops)
                 ops.append(op)
             else:
                 hbufs = ["H1", "H2"]
@@ -1089,11 +1112,12 @@ class FlowEngine(PlanesPlanMixin):
                         hb = ws[hbufs[j % 2]]
                     kw = {}
                     if j == 0 and use_ctx:
-                        # P = ctx * Wc + bc as a K=4 GEMM (context in column 0 of a zero-padded [B,4] operand);
+                        # P = ctx . Wc^T + bc as a K = Cp GEMM (the context in columns [0, C) of a zero-padded [B, Cp] operand);
                         # added to (acc + b_in) before the activation, as networks.py:741-745 does
-                        ops.append(lin_op(A=ws["ctx4"].data_ptr(), lda=4, W=un["W_ctx4"].data_ptr(), ldw=4,
+                        Cp = ws["ctx4"].shape[1]
+                        ops.append(lin_op(A=ws["ctx4"].data_ptr(), lda=Cp, W=un["W_ctx4"].data_ptr(), ldw=Cp,
                                           bias=un["b_ctx"].data_ptr(), C=ws["P"].data_ptr(), ldc=self.hmax,
-                                          M=B, N=cp["hidden"][0], K=4, res_sign=1.0, slope=0.0, act=_ext.ACT_NONE))
+                                          M=B, N=cp["hidden"][0], K=Cp, res_sign=1.0, slope=0.0, act=_ext.ACT_NONE))
                         kw = dict(addend=ws["P"].data_ptr(), ldadd=self.hmax)
                     kw.update(self._split_kw(pk, W, src_K))
                     ops.append(lin_op(A=src_ptr, lda=src_ld, W=W.data_ptr(), ldw=W.shape[1], bias=b.data_ptr(),
@@ -1151,12 +1175,13 @@ class FlowEngine(PlanesPlanMixin):
                 ws[hname] = torch.zeros(B, self.hmax, dtype=torch.float32, device=device)
         return [ws[f"Hs{j}_{i}"] for j in range(n)]
 
-    def _tiny_served(self, pk, cp, op, ws, i, B, train, device) -> bool:
+    def _tiny_served(self, pk, cp, op, ws, i, B, train, device, ctx_dim: int = 0) -> bool:
         """the library's own answer for a layer tiny_coupling() admits: the tiny-layer kernel serves the forward descriptor and,
         for a training plan whose backward chain runs fused (training.py: _fused_cbwd), the backward one (usf_coupling_variant,
         host-only).  Otherwise the layer takes the unfused ops: the f32 kernel rejects hidden_out / GATE"""
         lib = _ext.load()
-        if lib.usf_coupling_variant(C.byref(op.u.coupling)) != 3:
+        # (a vector context's LDS segments count against the kernel's budget: usf_coupling_additive_vctx_variant knows)
+        if (_ext.coupling_vctx_variant(op, ctx_dim) if ctx_dim else lib.usf_coupling_variant(C.byref(op.u.coupling))) != 3:
             return False
         if train and config.fused_cbwd:
             hb = self._hidden_bufs(ws, i, len(cp["hidden"]), B, device)
@@ -1293,7 +1318,13 @@ class FlowEngine(PlanesPlanMixin):
             f["zeros"] = zeros
         elif cp["has_ctx"]:
             Wc, bc = raw["ctx"]
-            f["W_ctx"] = self._packed_vec(Wc, ends[1], Hp)        # layers[1].weight is [h0, 1]: one column
+            if self.ctx_dim == 1:
+                f["W_ctx"] = self._packed_vec(Wc, ends[1], Hp)        # layers[1].weight is [h0, 1]: one column
+            else:
+                # layers[1].weight [h0, C] TRANSPOSED to [C, Hp] rows (usf_coupling_additive_vctx_f32: a lane's four hidden
+                # units are one 16-byte load per context column), zeros beyond h0
+                f["W_ctx_t"], _ = self._packed(Wc, self._iarange(self.ctx_dim, self.ctx_dim, dev), self.ctx_dim, ends[1], Hp,
+                                               transpose=True)
             f["b_ctx"] = self._packed_vec(bc, ends[1], Hp)
         return f
 
@@ -1338,7 +1369,7 @@ class FlowEngine(PlanesPlanMixin):
         f = self._fused_pack(cp)
         op = self._fused_op(cp, f, zptr, self.LD, B, sign, cp["act"],
                             split=self.gemm_mode in ("bf16x3", "f16x2") and "split" in f)
-        if ws_ctx is not None:
+        if ws_ctx is not None and self.ctx_dim == 1:           # (a vector context travels in a prefix op: _build_plan_body)
             d = op.u.coupling
             d.context = ws_ctx["ctx"].data_ptr()
             d.W_ctx, d.b_ctx = f["W_ctx"].data_ptr(), f["b_ctx"].data_ptr()
@@ -1350,7 +1381,7 @@ class FlowEngine(PlanesPlanMixin):
         key = (direction, B, str(device), has_ctx, final, self.use_fused_coupling, self.gemm_mode, self.fused_min_rows,
                config.tiny_coupling, config.get_lib("coupling_tiny", 1), train, self.use_planes, self.planes_min_rows, self._planes_fmt(), self.planes_min_rows_bf16x3,
                (not train) and self._merge_on(direction), train and self.use_train_planes, train and self.train_planes_min_rows,
-               has_ctx and (self.train_ctx_planes_min_rows if train else self.ctx_planes_min_rows))
+               has_ctx and (self.train_ctx_planes_min_rows if train else self.ctx_planes_min_rows), has_ctx and self.ctx_dim)
         plan = self._plans.get(key)
         if plan is None:
             plan = self._build_plan(direction, B, device, has_ctx, final, train)
@@ -1433,11 +1464,19 @@ class FlowEngine(PlanesPlanMixin):
         if out is not None:
             out.copy_(os_)
 
-    @staticmethod
-    def _fill_context(plan, context, B: int):
+    def _fill_context(self, plan, context, B: int):
         """the context columns of the workspace: one value per row ([B] / [B, 1]), or ONE value spread over the rows (the plans'
-        launches read them with stride 1; stride 0 of usf_coupling_planes_ctx is for direct callers of the entry point)"""
+        launches read them with stride 1; stride 0 of usf_coupling_planes_ctx is for direct callers of the entry point).
+        context_dim C > 1: rows of C values ([B, C]), or ONE row ([1, C] / [C]) spread over the rows, of any floating dtype, into
+        columns [0, C) of ctx4 [B, Cp]; the padding columns keep their zeros."""
         ws = plan["ws"]
+        Cd = self.ctx_dim
+        if Cd > 1:
+            if tuple(context.shape) not in ((B, Cd), (1, Cd), (Cd,)):        # the shapes the reference's layers[1] broadcasts
+                raise ValueError(f"context of shape {tuple(context.shape)}: a context_dim {Cd} flow takes [{B}, {Cd}], [1, {Cd}] "
+                                 f"or [{Cd}] for {B} rows")
+            ws["ctx4"][:, :Cd].copy_(context.reshape(-1, Cd).expand(B, Cd))       # (copy_ converts any floating dtype)
+            return
         c = context.reshape(-1).to(torch.float32)
         if c.numel() == 1 and B > 1:
             c = c.expand(B)
@@ -1467,7 +1506,10 @@ class FlowEngine(PlanesPlanMixin):
                 while j < end:
                     op = arr[j]
                     n_run = 2 if _ext.is_ctx_prefix(op) else 1       # (a context prefix and its coupling op are ONE launch)
-                    if n_run == 2:
+                    if n_run == 2 and arr[j + 1].kind == _ext.OP_COUPLING:
+                        c_ = arr[j + 1].u.coupling
+                        tag = ("coupling_vctx", c_.M, c_.n_trans, c_.n_pass)
+                    elif n_run == 2:
                         c_ = arr[j + 1].u.coupling_planes
                         tag = ("coupling_planes_ctx", c_.M, 32 * c_.nk_t, 32 * c_.nk_p)
                     elif op.kind == _ext.OP_LINEAR:

@@ -34,6 +34,8 @@ class PlanesPlanMixin:
         return _ext.PLANES_F16X2 if (self.gemm_mode == "f16x2" and not self._f16_overflow) else _ext.PLANES_BF16X3
 
     def _planes_ok(self, direction: str, B: int, has_ctx: bool, train: bool) -> bool:
+        if has_ctx and self.ctx_dim > 1:
+            return False       # a vector context never takes the planes plans (usf_coupling_planes_ctx is rank-1), also in training
         if self.use_planes is None:
             use = self.gemm_mode == "f16x2" or B >= self.planes_min_rows_bf16x3 or self._has_wide_conditioner()
             if has_ctx:        # (off until measured: engine.py, ctx_planes_min_rows)

@@ -190,14 +190,19 @@ class Flow(LayerLoopMixin, FitMixin, torch.nn.Module):
         return info
 
     # ---- the hot path ----------------------------------------------------------------------
-    @staticmethod
-    def _engine_context_ok(context, n: int, device) -> bool:
-        """contexts the device engine takes (context_dim 1): None, or a tensor [n], [n, 1] or of one element, on the device,
-        without grad"""
+    def _engine_context_ok(self, context, n: int, device) -> bool:
+        """contexts the device engine takes: None, or a tensor on the device, without grad, of a shape the reference's
+        ConditionalDenseNN itself accepts for its context_dim C (networks.py:739-743: layers[1](context) broadcast against the
+        [n, h0] pre-activation) -- C == 1: [n], [n, 1] or one element; C > 1: [n, C], [1, C] or [C].  (A 1-D [n] context with
+        C > 1 is an error in the reference: it is not served here, the composite path raises as the reference does.)"""
         if context is None:
             return True
         if not (torch.is_tensor(context) and context.device == device and not context.requires_grad):
             return False
+        eng = self.engine()
+        C = eng.ctx_dim if eng is not None else 1
+        if C > 1:
+            return tuple(context.shape) in ((n, C), (1, C), (C,))
         return context.numel() == 1 or tuple(context.shape) in ((n,), (n, 1))
 
     def _forward(self, x: torch.Tensor, context: Optional[torch.Tensor] = None):

@@ -854,7 +854,8 @@ class CondConvNet(ConvNet):
     feature, the context appended as that channel (expanded to ``(B, 1, *spatial)``; a context that does not expand becomes
     a zero channel).  Same constructor signature, module tree and state-dict keys.  Spatial 2-D inputs take the device
     form of ``CondConvNet2D``; the vector path (``in_dims = [D]``) is the torch formulation only -- the flat engine does not
-    serve it (``engine.conditioner_supported`` is False)."""
+    serve it (``engine.conditioner_supported`` is False: the flat plan's context columns, one to 32 of them, feed a
+    ``ConditionalDenseNN``'s ``layers[1]``, not a conditioner's input feature)."""
     consumes_context = True
 
     def __init__(self, in_dims, c_hidden: List[int], c_out: int = -1, nonlinearity=nn.ReLU(), kernel_size: int = 3,

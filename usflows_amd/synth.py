@@ -116,7 +116,7 @@ def synth_state_dict(spec: ModelSpec, seed: int = 0, alpha: float = 0.1) -> Dict
             hs = list(spec.hidden_dims)
             if spec.conditioner == "ConditionalDenseNN":
                 linear(c + "layers.0.", hs[0], D)
-                linear(c + "layers.1.", hs[0], 1)
+                linear(c + "layers.1.", hs[0], int(spec.extra.get("context_dim", 1)))     # (default 1: the draws of every existing spec)
                 idx = 2
                 for i in range(1, len(hs)):
                     linear(c + f"layers.{idx}.", hs[i], hs[i - 1])
@@ -191,7 +191,7 @@ def build_usflow(spec: ModelSpec, sd: Optional[Dict[str, torch.Tensor]] = None, 
     from .networks import ConditionalDenseNN, DenseNN
     act = torch.nn.LeakyReLU(spec.negative_slope) if spec.negative_slope != 0 else torch.nn.ReLU()
     if spec.conditioner == "ConditionalDenseNN":
-        cls, args = ConditionalDenseNN, dict(input_dim=spec.dim, context_dim=1, hidden_dims=list(spec.hidden_dims),
+        cls, args = ConditionalDenseNN, dict(input_dim=spec.dim, context_dim=int(spec.extra.get("context_dim", 1)), hidden_dims=list(spec.hidden_dims),
                                              out_dim=spec.dim, nonlinearity=act)
     elif spec.conditioner == "ConvNet":
         from .networks import ConvNet

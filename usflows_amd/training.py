@@ -221,7 +221,7 @@ class TrainPath:
                 lin = [l for l in cond.layers]
                 has_ctx = isinstance(cond, ConditionalDenseNN)
                 h = [int(v) for v in cond.hidden_dims]
-                want = [(h[0], D)] + ([(h[0], 1)] if has_ctx else []) + \
+                want = [(h[0], D)] + ([(h[0], self.eng.ctx_dim)] if has_ctx else []) + \
                        [(h[i + 1], h[i]) for i in range(len(h) - 1)] + [(D, h[-1])]
                 got = [tuple(l.weight.shape) for l in lin]
                 if got != want:
@@ -730,7 +730,7 @@ class TrainPath:
         self._scatter_weight(grads, first_l.weight, gW, None, h[0], self._seg_sel(m, "p", dev), eng.D)
         self._scatter_vec(grads, first_l.bias, gb, None, h[0])
         if ctx_l is not None and m["use_ctx"]:
-            # the context layer (layers[1], context_dim 1) adds ctx * W_ctx + b_ctx to the first pre-activation: d b_ctx is the
+            # the context layer (layers[1], context_dim 1 on this path) adds ctx * W_ctx + b_ctx to the first pre-activation: d b_ctx is the
             # column sum d b_in already holds, d W_ctx[h] = sign * sum_rows ctx[row] * d_h0[row, h] -- column 0 of the weight
             # gradient against the context planes.  (A context layer that sees no context gets no gradient, as under autograd.)
             self._scatter_vec(grads, ctx_l.bias, gb, None, h[0])
@@ -1079,7 +1079,8 @@ class TrainPath:
         for j, (W, b) in enumerate(un["layers"] if recompute else []):
             kw = {}
             if j == 0 and m["use_ctx"]:
-                self._linear(pk, ws["ctx4"], 0, 4, un["W_ctx4"], ws["P"], 0, hmax, B, hp[0], 4, bias=un["b_ctx"])
+                Cp = ws["ctx4"].shape[1]          # the context GEMM at K = Cp (context_dim padded to 4), as the forward plan's
+                self._linear(pk, ws["ctx4"], 0, Cp, un["W_ctx4"], ws["P"], 0, hmax, B, hp[0], Cp, bias=un["b_ctx"])
                 kw = dict(addend=ws["P"], ldadd=hmax)
             self._linear(pk, src, src_off, src_ld, W, hbufs[j], 0, hmax, B, W.shape[0], src_K, bias=b, act=act,
                          slope=slope, **kw)
@@ -1153,9 +1154,12 @@ class TrainPath:
         if gbias is None:
             self._colsum_to(grads, first_l.bias, d, B, h[0], hmax, sign)
         if ctx_l is not None and m["use_ctx"]:
-            gW = gimg("ctx")
-            _ext.wgrad(d, ws["ctx4"], gW, M=B, N=hp[0], K=4, ldy=hmax, lda=4, ldg=gW.shape[1], alpha=sign)
-            self._scatter_weight(grads, ctx_l.weight, gW, None, h[0], None, 1)
+            # d W_ctx [h0, C] = sign * d^T ctx over the padded context rows [B, Cp] (the padding columns hold zeros)
+            # (an image of its own shape: Cp may be wider than every hidden layer and the rows, e.g. hidden [16] with C = 32)
+            Cp = ws["ctx4"].shape[1]
+            gW = self._buf(ws, f"gW{m['step']}_ctx", max(hmax, LD), max(hmax, LD, Cp))
+            _ext.wgrad(d, ws["ctx4"], gW, M=B, N=hp[0], K=Cp, ldy=hmax, lda=Cp, ldg=gW.shape[1], alpha=sign)
+            self._scatter_weight(grads, ctx_l.weight, gW, None, h[0], None, eng.ctx_dim)
             self._colsum_to(grads, ctx_l.bias, d, B, h[0], hmax, sign)
         # conditioning half of the gradient: g_P += s * d W_in   (in place)
         if fused_bwd:
