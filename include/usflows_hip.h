@@ -66,7 +66,11 @@ typedef void* usf_stream_t; /* hipStream_t */
  *   one nn.Linear (+LeakyReLU) of the conditioner MLP    networks.py:739-751
  *   the masked residual of MaskedCoupling                transforms.py:285-290, 301-306
  *     (mask-aware: A/W/C are the pass-through / transformed column segments)
- * Requirements: K % 4 == 0, lda/ldw/ldc/ldr % 4 == 0, all base pointers 16-byte aligned.
+ * Requirements: K % 4 == 0, lda / ldw % 4 == 0, A / W / pre_div / pre_sub 16-byte aligned, every stride at least its extent.
+ * ldc / ldr / ldadd and the alignment of C / residual / addend / bias are free: rows that are 16-byte aligned with
+ * ldc % 4 == 0 are stored as vectors, others element by element (the engine's last layer writes the caller's [M, D] tensor
+ * with ldc = D).  The bf16x3 path (W_split) additionally wants those strides % 4 == 0 and 16-byte aligned operands; a
+ * descriptor that misses that is served by the other kernels.
  */
 typedef struct usf_linear_desc {
   const float* A;        int64_t lda;   /* [M,K] activations */

@@ -27,9 +27,11 @@ int usf_internal_version(void);
  * usf_linear_desc::A_planes_out, ldp_out, planes_out_stride:
  *   Optional side output (ABI 32): the three row-major bf16 planes of the INPUT A (A == p1 + p2 + p3 exactly, the
  *   split the bf16x3 kernel makes of its operand anyway), plane p at A_planes_out + p * planes_out_stride elements,
- *   each [ceil32(M), ldp_out] bf16 with ldp_out >= ceil32(K), ldp_out % 8 == 0; rows [M, ceil32(M)) are NOT written
- *   (the caller's buffer holds zeros there: usf_wgrad_planes_f32 sums over them), columns [K, ceil32(K)) receive finite
- *   padding.  This is the operand layout of usf_wgrad_planes_f32: the
+ *   each [ceil32(M), ldp_out] bf16 with ldp_out >= ceil32(K), ldp_out % 8 == 0; rows [M, ceil32(M)) are NOT written by the
+ *   bf16x3 kernels (the caller's buffer holds zeros there: usf_wgrad_planes_f32 sums over them), columns [K, ceil32(K)) receive
+ *   finite padding.  Where another kernel serves the product (small M, no W_split), the planes come from a usf_split_planes_f32
+ *   pass, which writes the whole [ceil32(M), ldp_out] image: zeros in rows [M, ceil32(M)) and in columns [K, ldp_out).  Either
+ *   way a buffer that held zeros in the padding rows still does.  This is the operand layout of usf_wgrad_planes_f32: the
  *   data-gradient / forward GEMM of a layer hands the weight gradient of the same layer its operand already split
  *   (flows.py:196-203: loss.backward() through every F.linear of the flow).  Not with pre_div / pre_sub.
  *

@@ -5,7 +5,8 @@ would receive -- with torch-CPU arithmetic, by mapping raw pointers back onto th
 tensors.  This lets the `-m "not gpu"` suite check the engine's layout permutation, mask-aware
 weight slicing, fusion and pointer arithmetic against the golden vectors without a GPU.
 It implements the *documented semantics* of ``usf_linear_f32`` / ``usf_coupling_additive_f32``
-(the public header include/usflows_hip.h), not the kernels."""
+(the public header include/usflows_hip.h), not the kernels.  tests/test_emulator_conformance_gpu.py holds it to the
+kernels on the device, op by op: what is written, what is left alone, what is refused."""
 import ctypes as C
 
 import torch
@@ -36,8 +37,45 @@ class PtrMap:
         return self.view(ptr, 1, n, n)[0]
 
 
+def _check_linear(N, K, lda, ldw, ldc, ldr, ldadd, act):
+    """usf_linear_f32's own argument checks (include/usflows_hip.h): K, lda, ldw multiples of 4, every stride at least its
+    extent (ldr / ldadd: None without the operand), USF_ACT_GATE with an addend and no residual, never residual and addend"""
+    if K % 4 != 0 or lda % 4 != 0 or ldw % 4 != 0 or lda < K or ldw < K or ldc < N or (ldr is not None and ldr < N) \
+            or (ldadd is not None and ldadd < N):
+        raise ValueError(f"usf_linear_f32: K / lda / ldw must be multiples of 4 and strides >= extents (K={K} lda={lda} ldw={ldw} ldc={ldc})")
+    if act == _ext.ACT_GATE and (ldadd is None or ldr is not None):
+        raise ValueError("usf_linear_f32: USF_ACT_GATE reads the gate from `addend` (required) and takes no residual")
+    if ldr is not None and ldadd is not None:
+        raise ValueError("usf_linear_f32: residual and addend are mutually exclusive")
+
+
+def _check_gated_norm(Cn, Cp, ld_skip, has_vg, ld_vg, gate_off, has_gamma, has_beta, has_out, ld_out, has_act, ld_act):
+    """usf_gated_norm_rows_f32's requirements: an output, 1 <= C <= c_pad <= 4096, rows inside their strides, gamma and beta together"""
+    if not (has_out or has_act):
+        raise ValueError("usf_gated_norm_rows_f32: neither out nor out_act")
+    if not (1 <= Cn <= Cp <= 4096):
+        raise ValueError(f"usf_gated_norm_rows_f32: needs 1 <= C ({Cn}) <= c_pad ({Cp}) <= 4096")
+    if ld_skip < Cn or (has_vg and ld_vg < gate_off + Cn) or (has_out and ld_out < Cp) or (has_act and ld_act < Cp):
+        raise ValueError("usf_gated_norm_rows_f32: a row stride is shorter than the row")
+    if has_gamma != has_beta:
+        raise ValueError("usf_gated_norm_rows_f32: gamma and beta come together")
+
+
+def _check_gemm_planes(a_nkb, a_kb0, nk, has_planes_out, has_f32_out, has_base_part, c_nkb, c_kb0, c_kbn):
+    """usf_gemm_planes_bf16x3's requirements: the K range inside A's blocks, an output, the output range inside C's blocks"""
+    if nk < 1 or a_kb0 < 0 or a_kb0 + nk > a_nkb:
+        raise ValueError(f"usf_gemm_planes_bf16x3: K range [{a_kb0}, {a_kb0 + nk}) outside the buffer's {a_nkb} blocks")
+    if not (has_planes_out or has_f32_out or has_base_part):
+        raise ValueError("usf_gemm_planes_bf16x3: no output")
+    if has_planes_out and (has_f32_out or has_base_part):
+        raise ValueError("usf_gemm_planes_bf16x3: give C_planes or C_f32 / base_part, not both")
+    if has_planes_out and (c_kbn < 1 or c_kb0 < 0 or c_kb0 + c_kbn > c_nkb):
+        raise ValueError(f"usf_gemm_planes_bf16x3: output range [{c_kb0}, {c_kb0 + c_kbn}) outside the buffer's {c_nkb} blocks")
+
+
 def emulate_linear(d, pm: PtrMap, dtype=torch.float32):
     M, N, K = d.M, d.N, d.K
+    _check_linear(N, K, d.lda, d.ldw, d.ldc, d.ldr if d.residual else None, d.ldadd if d.addend else None, d.act)
     A = pm.view(d.A, M, K, d.lda).to(dtype)
     W = pm.view(d.W, N, K, d.ldw).to(dtype)
     if d.pre_div:
@@ -47,7 +85,9 @@ def emulate_linear(d, pm: PtrMap, dtype=torch.float32):
     v = A @ W.t()
     if d.bias:
         v = v + pm.vec(d.bias, N).to(dtype)
-    if d.addend:
+    if d.act == _ext.ACT_GATE:          # leaky_relu_backward: the saved activation arrives in `addend`
+        v = torch.where(pm.view(d.addend, M, N, d.ldadd) > 0, v, v * d.slope)
+    elif d.addend:
         v = v + pm.view(d.addend, M, N, d.ldadd).to(dtype)
     if d.act == _ext.ACT_LEAKY_RELU:
         v = torch.where(v > 0, v, v * d.slope)
@@ -61,6 +101,8 @@ def emulate_linear(d, pm: PtrMap, dtype=torch.float32):
 def emulate_gated_norm(d, pm: PtrMap, dtype=torch.float32):
     """usf_gated_norm_rows_f32 as include/usflows_hip.h documents it"""
     M, Cn, Cp = d.M, d.C, d.c_pad
+    _check_gated_norm(Cn, Cp, d.ld_skip, bool(d.vg), d.ld_vg, d.gate_off, bool(d.gamma), bool(d.beta), bool(d.out), d.ld_out,
+                      bool(d.out_act), d.ld_act)
     r = pm.view(d.skip, M, Cn, d.ld_skip).to(dtype)
     if d.vg:
         r = r + pm.view(d.vg, M, Cn, d.ld_vg).to(dtype) * torch.sigmoid(pm.view(d.vg + 4 * d.gate_off, M, Cn, d.ld_vg).to(dtype))
@@ -163,13 +205,14 @@ def emulate_pack_planes(d, pm: PtrMap, dtype=torch.float32):
     npan = -(-M // 16)
     idx = pm.view(d.idx, 1, 32 * nkb, 32 * nkb, dtype=torch.int32)[0].long()
     src = pm.view(d.src, M, int(idx.max()) + 1, d.ld)
-    X = torch.zeros(M, 32 * nkb)
+    X = torch.zeros(M, 32 * nkb, dtype=dtype)
     ok = idx >= 0
-    X[:, ok] = src[:, idx[ok]]
+    X[:, ok] = src[:, idx[ok]].to(dtype)
     if d.pre_div:
-        X[:, ok] = X[:, ok] / pm.vec(d.pre_div, 32 * nkb)[ok]
+        X[:, ok] = X[:, ok] / pm.vec(d.pre_div, 32 * nkb)[ok].to(dtype)
     if d.pre_sub:
-        X[:, ok] = X[:, ok] - pm.vec(d.pre_sub, 32 * nkb)[ok]
+        X[:, ok] = X[:, ok] - pm.vec(d.pre_sub, 32 * nkb)[ok].to(dtype)
+    X = X.to(torch.float32)
     if d.format == 1 and d.range_flag and not bool((X.abs() < 65000.0).all()):
         pm.view(d.range_flag, 1, 1, 1, dtype=torch.int32)[0, 0] = 1
     planes_encode(planes_view(pm, d.planes, npan, nkb, d.format), X, 0)
@@ -180,6 +223,7 @@ def emulate_gemm_planes(d, pm: PtrMap, dtype=torch.float32):
     npan = -(-M // 16)
     fmt = d.format
     npl = 2 if fmt == 1 else 3
+    _check_gemm_planes(d.a_nkb, d.a_kb0, d.nk, bool(d.C_planes), bool(d.C_f32), bool(d.base_part), d.c_nkb, d.c_kb0, d.c_kbn)
     A = planes_decode(planes_view(pm, d.A, npan, d.a_nkb, fmt), M)[:, 32 * d.a_kb0: 32 * (d.a_kb0 + d.nk)]
     Wp = pm.view(d.W_planes, npl, d.w_rows * d.ldw, d.w_plane_stride).view(npl, d.w_rows, d.ldw)
     W = Wp[0].float() + Wp[1].float()
@@ -292,28 +336,48 @@ def _planes_weight(W_planes, K):
 
 
 def _emu_gemm_planes_call(A, W_planes, *, M, a_nkb, nk, a_kb0=0, bias=None, post_mul=None, residual=None, C_planes=None, c_nkb=0,
-                          c_kb0=0, c_kbn=0, C_f32=None, ldc=0, N=0, res_sign=1.0, act=0, slope=0.0, fmt=0, range_flag=None):
+                          c_kb0=0, c_kbn=0, C_f32=None, ldc=0, N=0, res_sign=1.0, act=0, slope=0.0, fmt=0, range_flag=None, dtype=torch.float64):
+    _check_gemm_planes(a_nkb, a_kb0, nk, C_planes is not None, C_f32 is not None, False, c_nkb, c_kb0, c_kbn)
     assert fmt == 0 and residual is None and C_f32 is None and post_mul is None
-    Am = planes_decode(_tensor_planes_view(A, M, a_nkb), M)[:, 32 * a_kb0: 32 * (a_kb0 + nk)].double()
-    v = Am @ _planes_weight(W_planes, 32 * nk).double().t()
+    Am = planes_decode(_tensor_planes_view(A, M, a_nkb), M)[:, 32 * a_kb0: 32 * (a_kb0 + nk)].to(dtype)
+    v = Am @ _planes_weight(W_planes, 32 * nk).to(dtype).t()
     if bias is not None:
-        v = v + bias.double()
+        v = v + bias.to(dtype)
     if act == _ext.ACT_LEAKY_RELU:
         v = torch.where(v > 0, v, v * slope)
     planes_encode(_tensor_planes_view(C_planes, M, c_nkb), v[:, : 32 * c_kbn].float(), c_kb0)
 
 
 def _emu_wgrad_blocked(Yp, y_nkb, y_kb0, Ap, a_nkb, a_kb0, G, *, M, N, K, ldg, g_off=0, alpha=1.0, beta=0.0, colsum=None,
-                       cs_alpha=1.0, cs_beta=0.0, queue=None, ws=None):
-    Y = planes_decode(_tensor_planes_view(Yp, M, y_nkb), M)[:, 32 * y_kb0: 32 * y_kb0 + N].double()
-    A = planes_decode(_tensor_planes_view(Ap, M, a_nkb), M)[:, 32 * a_kb0: 32 * a_kb0 + K].double()
-    g = _view(G, g_off, N, K, ldg)
-    r = alpha * (Y.t() @ A)
-    g.copy_((r + beta * g.double() if beta != 0.0 else r).float())
-    if colsum is not None:
-        c = cs_alpha * Y.sum(0)
-        cv = colsum.view(-1)[:N]
-        cv.copy_((c + cs_beta * cv.double() if cs_beta != 0.0 else c).float())
+                       cs_alpha=1.0, cs_beta=0.0, queue=None, ws=None, dtype=torch.float64):
+    if colsum is not None and K < 64:
+        raise RuntimeError("usf_wgrad_blocked_f32: colsum_out needs K >= 64")
+    Y = planes_decode(_tensor_planes_view(Yp, M, y_nkb), M)[:, 32 * y_kb0: 32 * y_kb0 + N].to(dtype)
+    A = planes_decode(_tensor_planes_view(Ap, M, a_nkb), M)[:, 32 * a_kb0: 32 * a_kb0 + K].to(dtype)
+    r = alpha * (Y.t() @ A)                  # the multiply kernel: reads the operands NOW, also where the reduction is queued
+    c = cs_alpha * Y.sum(0)
+
+    def reduce():                            # the reduction: reads (beta, cs_beta) and writes G / colsum
+        g = _view(G, g_off, N, K, ldg)
+        g.copy_((r + beta * g.to(dtype) if beta != 0.0 else r).float())
+        if colsum is not None:
+            cv = colsum.view(-1)[:N]
+            cv.copy_((c + cs_beta * cv.to(dtype) if cs_beta != 0.0 else c).float())
+    if queue is not None:
+        # usf_wgrad_blocked_plan_f32: G / colsum stay unwritten until the queue is flushed (_emu_wgrad_reduce_flush); the partial
+        # sums live in the call's own workspace until then (its contents are the kernel's business and are not emulated)
+        if ws is None:
+            raise ValueError("wgrad_blocked: a queued reduction needs a workspace of its own (ws=)")
+        queue.append(reduce)
+        return
+    reduce()
+
+
+def _emu_wgrad_reduce_flush(queue, device):
+    """_ext.wgrad_reduce_flush of the emulation: the queued reductions in the order they were queued, then an empty queue"""
+    for job in queue:
+        job()
+    del queue[:]
 
 
 _LAST_RUN = {}
@@ -359,9 +423,42 @@ def _gather(src, dst, idx):
     dst.copy_(out)
 
 
-def run_plan(eng, plan, x, out, context=None, dtype=torch.float32):
-    """CPU stand-in for FlowEngine._execute."""
-    _LAST_RUN.update(eng=eng, plan=plan)
+# ---- the interpreter: one branch per op kind, nothing falls through ---------------------------------------------------
+# USF_OP_CALL function id -> handler(call descriptor, the op behind it | None, pm, dtype).  The two context prefix ops are
+# registered by tests/emulator_ctx.py / tests/emulator_vctx.py; a function nobody registered is an error, not a coupling.
+CALL_HANDLERS = {}
+
+
+def emulate_launch(arr, pos, n, pm: PtrMap, dtype=torch.float32) -> int:
+    """interpret the launch that starts at arr[pos] of an op list of n ops; returns how many ops it took (a context prefix op
+    and the op behind it are ONE launch, as in usf_run_ops).  An op kind without a branch of its own raises."""
+    op = arr[pos]
+    kind = op.kind
+    if kind == _ext.OP_LINEAR:
+        emulate_linear(op.u.linear, pm, dtype)
+    elif kind == _ext.OP_COUPLING:
+        emulate_coupling(op.u.coupling, pm, dtype)
+    elif kind == _ext.OP_PACK_PLANES:
+        emulate_pack_planes(op.u.pack_planes, pm, dtype)
+    elif kind == _ext.OP_GEMM_PLANES:
+        emulate_gemm_planes(op.u.gemm_planes, pm, dtype)
+    elif kind == _ext.OP_COUPLING_PLANES:
+        emulate_coupling_planes(op.u.coupling_planes, pm, dtype)
+    elif kind == _ext.OP_GATED_NORM:
+        emulate_gated_norm(op.u.gated_norm, pm, dtype)
+    elif kind == _ext.OP_CALL:
+        handler = CALL_HANDLERS.get(int(op.u.call.fn))
+        if handler is None:
+            raise NotImplementedError(f"USF_OP_CALL function {int(op.u.call.fn)} has no emulation")
+        handler(op.u.call, arr[pos + 1] if pos + 1 < n else None, pm, dtype)
+        return 2
+    else:
+        raise NotImplementedError(f"op kind {int(kind)} has no emulation")
+    return 1
+
+
+def plan_ptr_map(eng, plan, x, out) -> PtrMap:
+    """every tensor an op of the plan can point into: workspace, index vectors, packed weights, the caller's in / out"""
     ws, pk = plan["ws"], plan["pk"]
     pm = PtrMap()
     for t in ws.values():
@@ -380,58 +477,71 @@ def run_plan(eng, plan, x, out, context=None, dtype=torch.float32):
                 pm.add(t)
         if "fused" in cp:
             f = cp["fused"]
-            for t in (f["W_in"], f["b_in"], f["W_out"], f["b_out"], f.get("W_ctx"), f.get("b_ctx")):
+            for t in (f["W_in"], f["b_in"], f["W_out"], f["b_out"], f.get("W_ctx"), f.get("W_ctx_t"), f.get("b_ctx")):
                 pm.add(t)
             for W, b in f["hid"]:
                 pm.add(W), pm.add(b)
     pm.add(x)
     pm.add(out)
-    B = x.shape[0]
-    if context is not None:
-        ws["ctx4"][:, 0].copy_(context.reshape(B))
-        ws["ctx"].copy_(context.reshape(B))
+    return pm
+
+
+def patch_user_pointers(plan, x, out):
     arr = plan["arr"]
     for idx, member, field in plan["patch_in"]:
         setattr(getattr(arr[idx].u, member), field, x.data_ptr())
     for idx, member, field in plan["patch_out"]:
         setattr(getattr(arr[idx].u, member), field, out.data_ptr())
+
+
+def emulate_side(eng, plan, g, x, dtype=torch.float32):
+    """one entry of plan["side"]: a stand-alone scale layer (usf_scale_f32, in place) or a layout gather (usf_gather_cols_f32)"""
+    ws = plan["ws"]
+    if g[0] == "scale":
+        _, _, buf, ld, sc, divide, ncols = g
+        v = ws[buf][:, :ncols].to(dtype)
+        ws[buf][:, :ncols] = (v / sc.to(dtype) if divide else v * sc.to(dtype)).to(torch.float32)
+    elif g[0] == "gather":
+        _, _, src, dst_name, dst_layout = g
+        src_t = x if src[0] == "user_in" else ws[src[0]]
+        _gather(src_t, ws[dst_name], eng._gather_index(src[1], dst_layout, x.device))
+    else:
+        raise NotImplementedError(f"side step {g[0]!r} has no emulation")
+
+
+def emulate_final_gather(eng, plan, x, out):
+    src, dst_name = plan["final_gather"]
+    ws = plan["ws"]
+    if dst_name == "user_out":
+        _gather(ws[src[0]], out, eng._gather_index(src[1], "user", x.device))
+    else:
+        _gather(ws[src[0]], ws[dst_name], eng._gather_index(src[1], "nat", x.device))
+
+
+def run_plan(eng, plan, x, out, context=None, dtype=torch.float32):
+    """CPU stand-in for FlowEngine._execute."""
+    _LAST_RUN.update(eng=eng, plan=plan)
+    ws = plan["ws"]
+    pm = plan_ptr_map(eng, plan, x, out)
+    B = x.shape[0]
+    if context is not None:
+        ws["ctx4"][:, 0].copy_(context.reshape(B))
+        ws["ctx"].copy_(context.reshape(B))
+    arr = plan["arr"]
+    patch_user_pointers(plan, x, out)
     pos = 0
 
     def run_until(end):
         nonlocal pos
         while pos < end:
-            op = arr[pos]
-            if op.kind == _ext.OP_LINEAR:
-                emulate_linear(op.u.linear, pm, dtype)
-            elif op.kind == _ext.OP_PACK_PLANES:
-                emulate_pack_planes(op.u.pack_planes, pm, dtype)
-            elif op.kind == _ext.OP_GEMM_PLANES:
-                emulate_gemm_planes(op.u.gemm_planes, pm, dtype)
-            elif op.kind == _ext.OP_COUPLING_PLANES:
-                emulate_coupling_planes(op.u.coupling_planes, pm, dtype)
-            elif op.kind == _ext.OP_GATED_NORM:
-                emulate_gated_norm(op.u.gated_norm, pm, dtype)
-            else:
-                emulate_coupling(op.u.coupling, pm, dtype)
-            pos += 1
+            pos += emulate_launch(arr, pos, plan["n"], pm, dtype)
 
     for g in plan["side"]:
         run_until(g[1])
-        if g[0] == "scale":
-            _, _, buf, ld, sc, divide, ncols = g
-            ws[buf][:, :ncols] = ws[buf][:, :ncols] / sc if divide else ws[buf][:, :ncols] * sc
-        else:
-            _, _, src, dst_name, dst_layout = g
-            src_t = x if src[0] == "user_in" else ws[src[0]]
-            _gather(src_t, ws[dst_name], eng._gather_index(src[1], dst_layout, x.device))
+        emulate_side(eng, plan, g, x, dtype)
     run_until(plan["n"])
-    fg = plan["final_gather"]
-    if fg is not None:
-        src, dst_name = fg
-        if dst_name == "user_out":
-            _gather(ws[src[0]], out, eng._gather_index(src[1], "user", x.device))
-        else:
-            _gather(ws[src[0]], ws[dst_name], eng._gather_index(src[1], "nat", x.device))
+    if plan["final_gather"] is not None:
+        emulate_final_gather(eng, plan, x, out)
 
 
 # ---- parameter-prep entry points (usf_prep.hip), documented semantics of include/usflows_hip.h ----------
@@ -533,9 +643,35 @@ def _view(t, off, rows, cols, ld):
     return torch.as_strided(t.reshape(-1), (rows, cols), (ld, 1), t.storage_offset() + off)   # as_strided offsets are absolute
 
 
+def _linear_bf16x3_eligible(M, N, K, ldc, c_off, residual, ldr, r_off, addend, ldadd, W_split):
+    """linear_bf16x3_eligible of the library (usflows_hip.h: the split-precision kernel's rule), on what the wrapper's arguments show
+    of it: the weight planes, K % 8 == 0, N % 4 == 0, more than 64 columns, 16-byte aligned rows of C / residual / addend -- and more
+    than 768 rows: up to there the small-batch kernel serves every product (usf_linear_variant 1000)"""
+    return (W_split is not None and K % 8 == 0 and N % 4 == 0 and M > 768 and N > 64 and ldc % 4 == 0 and c_off % 4 == 0
+            and (residual is None or (ldr % 4 == 0 and r_off % 4 == 0)) and (addend is None or ldadd % 4 == 0)
+            and W_split.shape[2] % 8 == 0 and W_split.shape[2] >= -(-K // 32) * 32)
+
+
 def _emu_linear(A, W, C_out, *, M, N, K, lda, ldw, ldc, bias=None, pre_div=None, pre_sub=None, residual=None, ldr=0,
                 post_mul=None, res_sign=1.0, act=_ext.ACT_NONE, slope=0.0, a_off=0, c_off=0, r_off=0, addend=None,
-                ldadd=0, W_split=None, dtype=torch.float64):
+                ldadd=0, W_split=None, planes_out=None, dtype=torch.float64):
+    _check_linear(N, K, lda, ldw, ldc, ldr if residual is not None else None, ldadd if addend is not None else None, act)
+    if planes_out is not None:
+        # usf_linear_desc::A_planes_out (include/usflows_hip_internal.h): the bf16 planes of the INPUT in rows [0, M) x columns [0, K)
+        if pre_div is not None or pre_sub is not None:
+            raise ValueError("usf_linear_f32: A_planes_out does not go with pre_div / pre_sub")
+        planes = _bf16_planes(_view(A, a_off, M, K, lda).contiguous())
+        if _linear_bf16x3_eligible(M, N, K, ldc, c_off, residual, ldr, r_off, addend, ldadd, W_split):
+            # the bf16x3 kernel stores the planes it splits anyway: rows >= M and columns >= ceil32(K) are NOT written; columns
+            # [K, ceil32(K)) receive "finite padding" -- which values the header leaves open: zeros here
+            for q, pl in enumerate(planes):
+                planes_out[q, :M, : -(-K // 32) * 32] = 0
+                planes_out[q, :M, :K] = pl
+        else:
+            # every other kernel: a usf_split_planes_f32 pass writes the whole [ceil32(M), ldp_out] image, zeros in the padding
+            for q, pl in enumerate(planes):
+                planes_out[q, : -(-M // 32) * 32] = 0
+                planes_out[q, :M, :K] = pl
     a = _view(A, a_off, M, K, lda).to(dtype)
     if pre_div is not None:
         a = a / pre_div[:K].to(dtype)
@@ -557,32 +693,48 @@ def _emu_linear(A, W, C_out, *, M, N, K, lda, ldw, ldc, bias=None, pre_div=None,
     _view(C_out, c_off, M, N, ldc).copy_(v.to(torch.float32))
 
 
-def _emu_wgrad(Y, A, G, *, M, N, K, ldy, lda, ldg, y_off=0, a_off=0, g_off=0, alpha=1.0, beta=0.0, mode=0, defer=True):
+def _emu_wgrad(Y, A, G, *, M, N, K, ldy, lda, ldg, y_off=0, a_off=0, g_off=0, alpha=1.0, beta=0.0, mode=0, defer=True, colsum=None,
+               cs_alpha=1.0, cs_beta=0.0, dtype=torch.float64):
+    if ldg < K or G.numel() - g_off < (N - 1) * ldg + K:           # (the binding's own check, for every form of the call)
+        raise ValueError(f"wgrad: gradient image too small (ldg {ldg}, {G.numel() - g_off} floats) for N = {N}, K = {K}")
+    if colsum is not None:
+        # usf_wgrad_bias_f32: never queued; served only where a bf16x3 instantiation carries the column sums
+        if not _ext.wgrad_bias_ok(M, N, K, ldy, lda, mode):
+            raise RuntimeError("usf_wgrad_bias_f32: usf_wgrad_bias_ok says no kernel carries the column sums for this call")
+        _emu_wgrad(Y, A, G, M=M, N=N, K=K, ldy=ldy, lda=lda, ldg=ldg, y_off=y_off, a_off=a_off, g_off=g_off, alpha=alpha, beta=beta,
+                   mode=mode, defer=False, dtype=dtype)
+        c = cs_alpha * _view(Y, y_off, M, N, ldy).to(dtype).sum(0)
+        cv = colsum.view(-1)[:N]
+        cv.copy_((c + cs_beta * cv.to(dtype) if cs_beta != 0.0 else c).float())
+        return
     bj = _ext._defer_grad_job(M) if defer else None
     if bj is not None:         # as the real call: queued, reads its operands at the flush (usf_grad_jobs_f32)
         bj.grad_jobs.append(lambda: _emu_wgrad(Y, A, G, M=M, N=N, K=K, ldy=ldy, lda=lda, ldg=ldg, y_off=y_off, a_off=a_off,
-                                               g_off=g_off, alpha=alpha, beta=beta, mode=mode, defer=False))
+                                               g_off=g_off, alpha=alpha, beta=beta, mode=mode, defer=False, dtype=dtype))
         return
-    y = _view(Y, y_off, M, N, ldy).double()
-    a = _view(A, a_off, M, K, lda).double()
+    y = _view(Y, y_off, M, N, ldy).to(dtype)
+    a = _view(A, a_off, M, K, lda).to(dtype)
     g = _view(G, g_off, N, K, ldg)
-    g.copy_((alpha * (y.t() @ a) + (beta * g.double() if beta != 0.0 else 0.0)).float())
+    g.copy_((alpha * (y.t() @ a) + (beta * g.to(dtype) if beta != 0.0 else 0.0)).float())
 
 
-def _emu_colsum(Y, out, *, M, N, ldy, y_off=0, alpha=1.0, beta=0.0, defer=True):
+def _emu_colsum(Y, out, *, M, N, ldy, y_off=0, alpha=1.0, beta=0.0, defer=True, dtype=torch.float64):
     bj = _ext._defer_grad_job(M) if defer else None
     if bj is not None:
-        bj.grad_jobs.append(lambda: _emu_colsum(Y, out, M=M, N=N, ldy=ldy, y_off=y_off, alpha=alpha, beta=beta, defer=False))
+        bj.grad_jobs.append(lambda: _emu_colsum(Y, out, M=M, N=N, ldy=ldy, y_off=y_off, alpha=alpha, beta=beta, defer=False, dtype=dtype))
         return
     o = out.reshape(-1)[:N]
-    o.copy_((alpha * _view(Y, y_off, M, N, ldy).double().sum(0) + (beta * o.double() if beta != 0.0 else 0.0)).float())
+    o.copy_((alpha * _view(Y, y_off, M, N, ldy).to(dtype).sum(0) + (beta * o.to(dtype) if beta != 0.0 else 0.0)).float())
 
 
 def _emu_gated_norm_rows(skip, *, M, C_cols, c_pad=None, ld_skip=None, vg=None, ld_vg=0, gate_off=0, gamma=None, beta=None, eps=1e-5,
                          out=None, ld_out=0, out_act=None, ld_act=0, act=_ext.ACT_NONE, slope=0.0, dtype=torch.float64):
     """usf_gated_norm_rows_f32 (include/usflows_hip.h) on raw buffers"""
     Cn, Cp = C_cols, c_pad if c_pad is not None else C_cols
-    r = _view(skip, 0, M, Cn, ld_skip if ld_skip is not None else Cn).to(dtype)
+    ld_skip = ld_skip if ld_skip is not None else Cn
+    _check_gated_norm(Cn, Cp, ld_skip, vg is not None, ld_vg, gate_off, gamma is not None, beta is not None, out is not None, ld_out,
+                      out_act is not None, ld_act)
+    r = _view(skip, 0, M, Cn, ld_skip).to(dtype)
     if vg is not None:
         r = r + _view(vg, 0, M, Cn, ld_vg).to(dtype) * torch.sigmoid(_view(vg, gate_off, M, Cn, ld_vg).to(dtype))
     if gamma is not None:
@@ -641,10 +793,11 @@ def _emu_act_grad(d, h, *, M, H, ldd, ldh, act, slope):
     dv.copy_(torch.where(hv > 0, dv, dv * slope))
 
 
-def _emu_base_logprob(z, ldz, M, D, base, loc, scale, logdet_const, out, sum_out=None, logdet_dev=None):
+def _emu_base_logprob(z, ldz, M, D, base, loc, scale, logdet_const, out, sum_out=None, logdet_dev=None, dtype=torch.float64):
     if logdet_dev is not None:
         logdet_const = float(logdet_const) + float(logdet_dev.float())
-    zz = _view(z, 0, M, D, ldz).double()
+    zz = _view(z, 0, M, D, ldz).to(dtype)
+    out = out.view(-1)[:M]                           # logp [M]: what lies behind it in the caller's tensor is not the kernel's
     if base == _ext.BASE_ROWSUM:
         out.copy_((zz.sum(-1) + logdet_const).float())
         if sum_out is not None:
@@ -653,10 +806,16 @@ def _emu_base_logprob(z, ldz, M, D, base, loc, scale, logdet_const, out, sum_out
         return
     if base in (_ext.BASE_LPNORM1, _ext.BASE_LPNORM2, _ext.BASE_LPNORMINF):
         p = {_ext.BASE_LPNORM1: 1.0, _ext.BASE_LPNORM2: 2.0}.get(base, float("inf"))
-        out.copy_((zz - loc.double()).norm(p=p, dim=1).float())
+        out.copy_((zz - loc.to(dtype)).norm(p=p, dim=1).float())
+        if sum_out is not None:
+            sum_out[0] += out.double().sum()
+            sum_out[1] += M
         return
-    dist = (torch.distributions.Laplace if base == _ext.BASE_LAPLACE else torch.distributions.Normal)(loc.double(), scale.double())
+    dist = (torch.distributions.Laplace if base == _ext.BASE_LAPLACE else torch.distributions.Normal)(loc.to(dtype), scale.to(dtype))
     out.copy_((dist.log_prob(zz).sum(-1) + logdet_const).float())
+    if sum_out is not None:          # (every base id: sum_out[0] += sum_m logp[m], sum_out[1] += M -- include/usflows_hip.h)
+        sum_out[0] += out.double().sum()
+        sum_out[1] += M
 
 
 def _emu_base_tables(base, loc, scale, D, tab, stride):
@@ -667,28 +826,31 @@ def _emu_base_tables(base, loc, scale, D, tab, stride):
     t[2, :D] = -(2.0 * scale).log() if base == _ext.BASE_LAPLACE else -scale.log() - 0.91893853320467274178
 
 
-def _emu_base_logprob_grad(z, ldz, g_lp, M, D, base, loc, scale, g, ldg):
-    t = _view(z, 0, M, D, ldz).double() - loc.double()
+def _emu_base_logprob_grad(z, ldz, g_lp, M, D, base, loc, scale, g, ldg, dtype=torch.float64):
+    t = _view(z, 0, M, D, ldz).to(dtype) - loc.to(dtype)
     if base == _ext.BASE_LAPLACE:
-        v = -torch.sign(t) / scale.double()
+        v = -torch.sign(t) / scale.to(dtype)
     elif base == _ext.BASE_NORMAL:
-        v = -t / (scale.double() ** 2)
+        v = -t / (scale.to(dtype) ** 2)
     elif base == _ext.BASE_LPNORM1:
         v = torch.sign(t)
     elif base == _ext.BASE_LPNORM2:
-        v = t / t.norm(dim=1, keepdim=True)
+        # (for the LPNORM* ids `scale` carries the radius vector [M], the forward kernel's output: include/usflows_hip_internal.h)
+        r = scale.to(dtype)[:M, None]
+        v = torch.where(r > 0, t / r, torch.zeros_like(t))
     else:
-        v = torch.sign(t) * (t.abs() == t.abs().max(dim=1, keepdim=True).values)
+        t32 = _view(z, 0, M, D, ldz) - loc                           # the kernel compares fp32 |t| with the stored radius
+        v = torch.sign(t) * (t32.abs() == scale[:M, None])
     gv = _view(g, 0, M, ldg, ldg)
     gv.zero_()
-    gv[:, :D] = (v * g_lp.double()[:, None]).float()
+    gv[:, :D] = (v * g_lp.to(dtype)[:, None]).float()
 
 
-def _emu_base_param_grad(z, ldz, g_lp, M, D, base, loc, scale, out):
-    zz = _view(z, 0, M, D, ldz).double()
-    t = zz - loc.double()
-    b = scale.double()
-    w = g_lp.double()[:M, None]
+def _emu_base_param_grad(z, ldz, g_lp, M, D, base, loc, scale, out, dtype=torch.float64):
+    zz = _view(z, 0, M, D, ldz).to(dtype)
+    t = zz - loc.to(dtype)
+    b = scale.to(dtype)
+    w = g_lp.to(dtype)[:M, None]
     if base == _ext.BASE_LAPLACE:
         dl, ds = torch.sign(t) / b, t.abs() / (b * b) - 1.0 / b
     else:
@@ -713,8 +875,8 @@ def _emu_lu_grad_finish(dL, dU, TL, TU, c, tri, n, D, out_L, out_U):
     u = u + torch.diag_embed(c[:n, None].double() / tri[1:2 * n:2].double().diagonal(dim1=1, dim2=2))
     if TU is not None:
         u = u + TU[:n].double().triu()
-    out_L.view(n, D, D).copy_(l.tril(-1).float())
-    out_U.view(n, D, D).copy_(u.float())
+    out_L.view(-1)[: n * D * D].view(n, D, D).copy_(l.tril(-1).float())
+    out_U.view(-1)[: n * D * D].view(n, D, D).copy_(u.float())
 
 
 def install_training_emulation(monkeypatch):
@@ -737,6 +899,7 @@ def install_training_emulation(monkeypatch):
     monkeypatch.setattr(_ext, "pack_planes", _emu_pack_planes_call)
     monkeypatch.setattr(_ext, "gemm_planes", _emu_gemm_planes_call)
     monkeypatch.setattr(_ext, "wgrad_blocked", _emu_wgrad_blocked)
+    monkeypatch.setattr(_ext, "wgrad_reduce_flush", _emu_wgrad_reduce_flush)
     monkeypatch.setattr(_ext, "coupling_planes_op", _emu_coupling_planes_op)
     monkeypatch.setattr(_ext, "coupling_op", _emu_coupling_op)
     monkeypatch.setattr(_ext, "lu_grad_finish", _emu_lu_grad_finish)

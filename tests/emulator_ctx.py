@@ -3,8 +3,6 @@
 b_in + b_ctx + ctx[row * ctx_stride] * w_ctx -- and the launch list's prefix op (USF_OP_CALL / USF_FN_COUPLING_PLANES_CTX: the
 four context arguments of the USF_OP_COUPLING_PLANES op behind it).  ``install`` puts both over tests/emulator.py's interpreter and
 over the binding's direct call."""
-import ctypes as C
-
 import torch
 
 import emulator
@@ -56,40 +54,30 @@ def emulate_coupling_planes_ctx(d, pm: PtrMap, dtype=torch.float32, ctx=None):
 
 
 class _Pending:
-    """the context arguments a prefix op left for the coupling op behind it"""
-    ctx = None
-    seen = 0            # context launches interpreted (the tests assert the context form really ran)
+    """how many context launches were interpreted (the tests assert the context form really ran)"""
+    seen = 0
 
 
-def _op_of(member) -> "_ext.Op":
-    """the usf_op a union member (op.u.<member>) lives in"""
-    return _ext.Op.from_address(C.addressof(member) - _ext.Op.u.offset)
+def register(monkeypatch):
+    """the prefix op's branch of tests/emulator.py's interpreter (emulator.CALL_HANDLERS): USF_FN_COUPLING_PLANES_CTX takes four
+    arguments and applies to a USF_OP_COUPLING_PLANES op behind it -- anything else is refused, as usf_run_ops refuses it"""
+    _Pending.seen = 0
+
+    def prefix(call, nxt, pm, dtype=torch.float32):
+        if call.n_args != 4:
+            raise ValueError("USF_FN_COUPLING_PLANES_CTX takes 4 arguments")
+        if nxt is None or nxt.kind != _ext.OP_COUPLING_PLANES:
+            raise ValueError("USF_FN_COUPLING_PLANES_CTX must be followed by a USF_OP_COUPLING_PLANES op")
+        _Pending.seen += 1
+        emulate_coupling_planes_ctx(nxt.u.coupling_planes, pm, dtype, tuple(int(call.a[j]) for j in range(4)))
+
+    monkeypatch.setitem(emulator.CALL_HANDLERS, _ext.FN_COUPLING_PLANES_CTX, prefix)
+    return _Pending
 
 
 def install(monkeypatch):
-    """tests/emulator.py's run_plan hands every op kind it does not know to ``emulate_coupling``: the prefix op is caught there;
-    ``emulate_coupling_planes`` becomes the context form (which is the plain one when no prefix op came before)"""
-    real_coupling, real_planes = emulator.emulate_coupling, emulator.emulate_coupling_planes
-    _Pending.ctx, _Pending.seen = None, 0
-
-    def coupling_or_prefix(d, pm, dtype=torch.float32):
-        op = _op_of(d)
-        if _ext.is_ctx_prefix(op):
-            a = op.u.call.a
-            assert op.u.call.n_args == 4 and _Pending.ctx is None
-            _Pending.ctx = (int(a[0]), int(a[1]), int(a[2]), int(a[3]))
-            return
-        real_coupling(d, pm, dtype)
-
-    def planes(d, pm, dtype=torch.float32):
-        ctx, _Pending.ctx = _Pending.ctx, None
-        if ctx is None:
-            return real_planes(d, pm, dtype)
-        _Pending.seen += 1
-        emulate_coupling_planes_ctx(d, pm, dtype, ctx)
-
-    monkeypatch.setattr(emulator, "emulate_coupling", coupling_or_prefix)
-    monkeypatch.setattr(emulator, "emulate_coupling_planes", planes)
+    """``register`` + the binding's direct call (_ext.coupling_planes_ctx_op) on the CPU"""
+    register(monkeypatch)
 
     def ctx_op(op, ctx, ctx_stride, w_ctx, b_ctx, device):        # the binding's direct call (_ext.coupling_planes_ctx_op)
         if ctx is None:

@@ -3,8 +3,6 @@ include/usflows_hip_internal.h): ``emulate_coupling`` restated with ConditionalD
 pre-activation becomes v + (b_ctx + sum_c ctx[row, c] W_ctx_t[c, :]) over the C real columns only -- and the launch list's prefix
 op (USF_OP_CALL / USF_FN_COUPLING_VCTX: the six context arguments of the USF_OP_COUPLING op behind it).  ``install`` puts both
 over tests/emulator.py's interpreter, and fills the workspace's context rows the way the engine does (``_fill_context``)."""
-import ctypes as C
-
 import torch
 
 import emulator
@@ -47,41 +45,32 @@ def emulate_coupling_vctx(d, pm: PtrMap, dtype, ctx):
 
 
 class _Pending:
-    """the context arguments a prefix op left for the coupling op behind it"""
-    ctx = None
-    seen = 0            # vector-context launches interpreted (the tests assert the vector form really ran)
+    """how many vector-context launches were interpreted (the tests assert the vector form really ran)"""
+    seen = 0
 
 
-def _op_of(member) -> "_ext.Op":
-    """the usf_op a union member (op.u.<member>) lives in"""
-    return _ext.Op.from_address(C.addressof(member) - _ext.Op.u.offset)
+def register(monkeypatch):
+    """the prefix op's branch of tests/emulator.py's interpreter (emulator.CALL_HANDLERS): USF_FN_COUPLING_VCTX takes six
+    arguments and applies to a USF_OP_COUPLING op behind it -- anything else is refused, as usf_run_ops refuses it"""
+    _Pending.seen = 0
+
+    def prefix(call, nxt, pm, dtype=torch.float32):
+        if call.n_args != 6:
+            raise ValueError("USF_FN_COUPLING_VCTX takes 6 arguments")
+        if nxt is None or nxt.kind != _ext.OP_COUPLING:
+            raise ValueError("USF_FN_COUPLING_VCTX must be followed by a USF_OP_COUPLING op")
+        _Pending.seen += 1
+        emulate_coupling_vctx(nxt.u.coupling, pm, dtype, tuple(int(call.a[j]) for j in range(6)))
+
+    monkeypatch.setitem(emulator.CALL_HANDLERS, _ext.FN_COUPLING_VCTX, prefix)
+    return _Pending
 
 
 def install(monkeypatch):
-    """tests/emulator.py's run_plan hands every op kind it does not know to ``emulate_coupling``: the prefix op is caught there and
-    the coupling op behind it becomes the vector-context form.  The engine's ``_execute`` / ``_execute_plain`` fill the context
-    rows with the engine's own ``_fill_context`` and run the list through run_plan."""
+    """``register`` + the engine's ``_execute`` / ``_execute_plain``: they fill the context rows with the engine's own
+    ``_fill_context`` and run the list through run_plan."""
     from usflows_amd.engine import FlowEngine
-    real_coupling = emulator.emulate_coupling
-    _Pending.ctx, _Pending.seen = None, 0
-
-    def coupling_or_prefix(d, pm, dtype=torch.float32):
-        op = _op_of(d)
-        if op.kind == _ext.OP_CALL:
-            a = op.u.call.a
-            assert op.u.call.fn == _ext.FN_COUPLING_VCTX and op.u.call.n_args == 6 and _Pending.ctx is None
-            _Pending.ctx = tuple(int(a[j]) for j in range(6))
-            return
-        ctx, _Pending.ctx = _Pending.ctx, None
-        if ctx is None:
-            return real_coupling(d, pm, dtype)
-        assert op.kind == _ext.OP_COUPLING
-        for cp in emulator._LAST_RUN["plan"]["pk"]["coupling"].values():     # (run_plan's pointer map predates the transposed image)
-            pm.add(cp.get("fused", {}).get("W_ctx_t"))
-        _Pending.seen += 1
-        emulate_coupling_vctx(d, pm, dtype, ctx)
-
-    monkeypatch.setattr(emulator, "emulate_coupling", coupling_or_prefix)
+    register(monkeypatch)
 
     def execute(self, plan, x, out, context, dtype=torch.float64):
         if context is not None:
