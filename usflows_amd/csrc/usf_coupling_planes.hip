@@ -77,6 +77,7 @@ struct CplPArgs {
   const char* Wout; int64_t ld_out, pl_out; const float* b_out;
   float sign, slope; int act;
   int32_t* range_flag;
+  int descend;                           // knob coupling_descend: blocks take the panels from the last one down
   unsigned long long* dbg;               // tuning builds (-DUSF_STAMP) only
   // training (ABI 33; bf16x3 only): planes buffers of 8 blocks per panel (hidden width 256).  hout[l]: receives hidden
   // layer l's activations (MODE 1) resp. the gradients at its pre-activations (MODE 2); gate[l]: MODE 2, the saved
@@ -123,7 +124,10 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
   const int lane = tid & 63;
   const int wave = tid >> 6;
   const int lj = lane & 15, lg = lane >> 4;
-  const int panel = blockIdx.x * 8 + wave;                       // this wave's 16 rows
+  // this wave's 16 rows.  Descending (the default): the GEMM in front of the layer finishes with the highest rows and the one
+  // behind it starts with the lowest, so the layer reads what was written last and leaves behind what is read next
+  // (profiles/dead_tiles_and_pack.md; blocks are independent: the results are the same bit for bit)
+  const int panel = (p.descend ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x) * 8 + wave;
   const int panc = min(panel, p.npanels - 1);
   const bool live = panel < p.npanels;
   // the rows this lane writes back into z: a context launch leaves the last panel's rows beyond M as they are
@@ -471,6 +475,7 @@ int coupling_planes_ctx(const usf_coupling_planes_desc* d, const float* ctx, int
   a.ld_hid = d->ldw_hid; a.pl_hid = d->w_hid_plane;
   a.Wout = reinterpret_cast<const char*>(d->W_out); a.ld_out = d->ldw_out; a.pl_out = d->w_out_plane; a.b_out = d->b_out;
   a.sign = d->sign; a.slope = d->slope; a.act = d->act; a.range_flag = d->range_flag;
+  a.descend = (int)tuning("coupling_descend", 1);           // A/B aid: 0 = ascending
   a.ctx = ctx; a.ctx_stride = (int)ctx_stride; a.w_ctx = w_ctx; a.b_ctx = b_ctx;
   a.dbg = nullptr;
 #ifdef USF_STAMP

@@ -23,12 +23,15 @@
 // accumulation, smallest terms first.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "usf_common.h"
 
 namespace usf {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #define USF_F16_GUARD 65000.0f
 #define USF_PL_LOAD_A(ptr) (*(ptr))
 #define USF_PL_STORE_C(v, ptr) (*(ptr) = (v))
@@ -118,8 +121,11 @@ __global__ __launch_bounds__(256) void pack_planes_kernel(const float* __restric
 // the 8 (profiles/r04_hbm_traffic.json); here the HBM sees 16-byte loads along rows and 1-KiB plane stores only.
 // GRAD: the staged value is g = row_weight[m] * d/dz base_c(z) (base_grad_kernel's Laplace / Normal formulas) instead of the
 // source value -- the training backward's head in one pass instead of usf_base_logprob_grad_f32 + usf_pack_planes_f32.
-template <int NPL, bool GRAD>
-__global__ __launch_bounds__(256) void pack_planes_rows_kernel(const float* __restrict__ src, int64_t ld, int M, int nkb, int src_cols,
+// NT: threads per block.  The LDS tile (59.8 KB at 784 columns) lets two blocks share a CU whatever their size, and a block
+// loads, waits at its barrier and only then gathers and stores: with 256 threads that is 8 waves a CU and too few bytes in
+// flight (2.6 TB/s of 8); 512 threads double both (knob pack_wide, 0 = 256 threads).
+template <int NPL, bool GRAD, int NT>
+__global__ __launch_bounds__(NT) void pack_planes_rows_kernel(const float* __restrict__ src, int64_t ld, int M, int nkb, int src_cols,
                                                                const int32_t* __restrict__ idx, const float* __restrict__ pre_div,
                                                                const float* __restrict__ pre_sub, char* __restrict__ dst,
                                                                int32_t* __restrict__ range_flag, const float* __restrict__ row_weight,
@@ -136,7 +142,7 @@ __global__ __launch_bounds__(256) void pack_planes_rows_kernel(const float* __re
   const int p = blockIdx.x;
   // the layout tables once per block, coalesced (a chunk's 8 x 3 dependent global loads per lane were what the first version
   // of this kernel waited for: 203 us, the same as the per-element gather)
-  for (int e = tid; e < L; e += 256) {
+  for (int e = tid; e < L; e += NT) {
     t_idx[e] = idx[e];
     t_div[e] = pre_div ? pre_div[e] : 1.0f;
     t_sub[e] = pre_sub ? pre_sub[e] : 0.0f;
@@ -150,7 +156,7 @@ __global__ __launch_bounds__(256) void pack_planes_rows_kernel(const float* __re
   };
   if (vec) {
     const int c4n = src_cols >> 2;
-    for (int e = tid; e < 16 * c4n; e += 256) {
+    for (int e = tid; e < 16 * c4n; e += NT) {
       const int r = e / c4n, c = 4 * (e - r * c4n);
       const int row = 16 * p + r;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
@@ -162,13 +168,13 @@ __global__ __launch_bounds__(256) void pack_planes_rows_kernel(const float* __re
 #pragma unroll
       for (int q = 0; q < 4; ++q) tile[r * S + c + q] = (row < M) ? xform(v[q], c + q, w) : 0.f;
     }
-    for (int e = tid; e < 16 * (src_cols & 3); e += 256) {      // (a column remainder: scalar)
+    for (int e = tid; e < 16 * (src_cols & 3); e += NT) {      // (a column remainder: scalar)
       const int r = e / (src_cols & 3), c = (src_cols & ~3) + e % (src_cols & 3);
       const int row = 16 * p + r;
       tile[r * S + c] = (row < M) ? xform(src[(int64_t)row * ld + c], c, GRAD ? row_weight[row] : 0.f) : 0.f;
     }
   } else {
-    for (int e = tid; e < 16 * src_cols; e += 256) {
+    for (int e = tid; e < 16 * src_cols; e += NT) {
       const int r = e / src_cols, c = e - r * src_cols;
       const int row = 16 * p + r;
       tile[r * S + c] = (row < M) ? xform(src[(int64_t)row * ld + c], c, GRAD ? row_weight[row] : 0.f) : 0.f;
@@ -179,7 +185,7 @@ __global__ __launch_bounds__(256) void pack_planes_rows_kernel(const float* __re
   const bool row_live = 16 * p + lj < M;
   const bool has_div = pre_div != nullptr, has_sub = pre_sub != nullptr;
   bool bad = false;
-  for (int kb = wave; kb < nkb; kb += 4) {
+  for (int kb = wave; kb < nkb; kb += NT / 64) {
     float x[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
@@ -229,12 +235,15 @@ int pack_planes(const usf_pack_planes_desc* d, hipStream_t stream) {
   if (d->src_cols > 0 && d->src_cols <= d->ld && lds <= 65536 && (rows_env || d->grad_base != 0)) {
     const int vec = (aligned16(d->src) && (d->ld & 3) == 0) ? 1 : 0;
     char* out = reinterpret_cast<char*>(d->planes);
-#define USF_PPR(NPL_, GRAD_) hipLaunchKernelGGL((pack_planes_rows_kernel<NPL_, GRAD_>), dim3((unsigned)npanels), dim3(256), lds, stream, d->src, \
-                             d->ld, (int)d->M, (int)d->nkb, (int)d->src_cols, d->idx, d->pre_div, d->pre_sub, out, d->range_flag,      \
+    const int wide = (int)tuning("pack_wide", 1);           // A/B aid: 0 = 256-thread blocks
+#define USF_PPR(NPL_, GRAD_, NT_) hipLaunchKernelGGL((pack_planes_rows_kernel<NPL_, GRAD_, NT_>), dim3((unsigned)npanels), dim3(NT_), lds, stream, \
+                             d->src, d->ld, (int)d->M, (int)d->nkb, (int)d->src_cols, d->idx, d->pre_div, d->pre_sub, out, d->range_flag,  \
                              d->row_weight, d->loc, d->scale, (int)d->grad_base, vec)
-    if (d->grad_base != 0) USF_PPR(3, true);
-    else if (d->format == USF_PLANES_F16X2) USF_PPR(2, false);
-    else USF_PPR(3, false);
+#define USF_PPW(NPL_, GRAD_) do { if (wide) USF_PPR(NPL_, GRAD_, 512); else USF_PPR(NPL_, GRAD_, 256); } while (0)
+    if (d->grad_base != 0) USF_PPW(3, true);
+    else if (d->format == USF_PLANES_F16X2) USF_PPW(2, false);
+    else USF_PPW(3, false);
+#undef USF_PPW
 #undef USF_PPR
     return check_launch("usf_pack_planes_f32");
   }
@@ -262,6 +271,7 @@ struct PlArgs {
   int N, nbm, nbn, nvb;
   float res_sign, slope; int act;
   int32_t* range_flag;
+  int skip_dead;                        // knob planes_skip_dead: the last column block looks for an all-zero last feature tile
   // base density in the fp32-output epilogue (b_part == nullptr: off): tables loc | 1 / scale | constant, stride b_stride
   const float* b_tab; float* b_part; int b_stride; int b_base;
   unsigned long long* clk;              // usf_set_clock_buffer: [shader cycles, 100 MHz ticks] summed over the blocks' lifetimes
@@ -288,12 +298,9 @@ __global__ __launch_bounds__(512, 2) void gemm_planes_kernel(const PlArgs p) {
   static_assert(NWV * NT - NSLOT <= NSLOT, "surplus threads wrap once");
   __shared__ __attribute__((aligned(16))) float wring[NB * STG];
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int lj = lane & 15, lg = lane >> 4;
+  const int tid0 = threadIdx.x;
 #ifdef USF_STAMP
-  if (p.span && tid == 0) atomicMin(p.span, __builtin_amdgcn_s_memrealtime());
+  if (p.span && tid0 == 0) atomicMin(p.span, __builtin_amdgcn_s_memrealtime());
 #endif
   unsigned long long clk_c0 = 0, clk_r0 = 0;    // (scalar registers; block-uniform branch)
 #ifndef USF_NO_CLOCK                             // (A/B builds: the kernel without the two counter reads)
@@ -304,6 +311,14 @@ __global__ __launch_bounds__(512, 2) void gemm_planes_kernel(const PlArgs p) {
   // b, b + grid, b + 2 grid, ... -- the order in which the hardware would have dispatched a grid of that size.
   // XCD-aware map of a virtual block: the column blocks of one 256-row panel group run back to back on one XCD.
   for (int bid = blockIdx.x; bid < p.nvb; bid += gridDim.x) {
+  // (the thread index is re-read per tile behind a compiler barrier: everything a tile derives from it -- staging and
+  // fragment addresses of both K loop forms below -- is then the tile's own and not a set of values hoisted out of this
+  // loop and kept alive, for both forms at once, across the K loops)
+  int tid = tid0;
+  asm volatile("" : "+v"(tid));
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int lj = lane & 15, lg = lane >> 4;
   const int xcd = bid & 7;
   const int seq = bid >> 3;
   const int pg = (seq / p.nbn) * 8 + xcd;       // group of 16 panels (256 rows)
@@ -315,6 +330,35 @@ __global__ __launch_bounds__(512, 2) void gemm_planes_kernel(const PlArgs p) {
   pw[0] = pg * 16 + wave * 2;
   pw[1] = pw[0] + 1;
 
+  // Dead last feature tile.  A layer whose width is no multiple of 32 TN ends in weight rows that are zero by the planes
+  // contract (784 features in 160-column blocks: rows 784..799), and the last of the FT feature tiles of the last column
+  // block then multiplies zeros.  The block looks before it starts the tile: the 16 rows, all planes, the whole K range
+  // (16-byte loads, coalesced along the rows, four in flight per thread), OR-ed over the block.  Exact for whatever image
+  // the caller hands in and stateless -- weights are refilled in place after an optimiser step, so nothing is remembered
+  // per pointer.  Only the all-zero bit pattern counts (a -0 weight runs the full path).
+  bool dead = false;                            // (block-uniform)
+  if (p.skip_dead && bn == p.nbn - 1 && n0 + BN <= p.wrows) {
+    const int spr = 4 * p.nk;                   // 16-byte slots per row and plane
+    const int nscan = NPL * 16 * spr;
+    const char* const wz = p.Wp + 2 * ((int64_t)(n0 + BN - 16) * p.ldwp);
+    unsigned nz = 0;
+    for (int e0 = tid; e0 < nscan; e0 += 4 * NT) {
+      u32x4 v[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int e = min(e0 + i * NT, nscan - 1);          // (a slot past the end: the last one again)
+        const int pl = e / (16 * spr), rem = e - pl * (16 * spr);
+        const int r = rem / spr, c = rem - r * spr;
+        v[i] = *reinterpret_cast<const u32x4*>(wz + 2 * (pl * p.plane_stride + (int64_t)r * p.ldwp + 8 * c));
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) nz |= v[i][0] | v[i][1] | v[i][2] | v[i][3];
+    }
+    dead = __builtin_amdgcn_readfirstlane(__syncthreads_or(nz != 0)) == 0;
+  }
+  // The tile, once per DEAD value (a compile-time flag of mm_pair / slab, chosen by ONE block-uniform branch per tile, at
+  // the bottom): the two forms share no register assignment and meet again behind the tile's last store.
+  auto tile = [&](auto dead_c) {
   // ---- activations: one 16-byte load per lane, plane and batch tile, straight into the MFMA B operand ----
   unsigned aoff[2];
 #pragma unroll
@@ -387,6 +431,10 @@ __global__ __launch_bounds__(512, 2) void gemm_planes_kernel(const PlArgs p) {
       f[1][q] = *reinterpret_cast<const vec8*>(wl + 4 * (q * 4 * CS + (2 * pr + 1) * 16));
     }
   };
+  auto read_half = [&](const float* wl, int pr, vec8 (&f)[2][NPL]) {      // the pair's first feature tile only
+#pragma unroll
+    for (int q = 0; q < NPL; ++q) f[0][q] = *reinterpret_cast<const vec8*>(wl + 4 * (q * 4 * CS + (2 * pr) * 16));
+  };
   read_pair(wl0, 0, fr);
 
   // One slab = TN tile pairs, NPR products per feature tile and batch tile (NPL = 3: six, smallest terms first;
@@ -404,9 +452,21 @@ __global__ __launch_bounds__(512, 2) void gemm_planes_kernel(const PlArgs p) {
 #define USF_MM(FT_, W, P)                                        \
   acc[FT_][0] = PT::mfma(W, cur[0][P], acc[FT_][0]);             \
   acc[FT_][1] = PT::mfma(W, cur[1][P], acc[FT_][1])
-  auto mm_pair = [&](int pr, const vec8 (&f)[2][NPL], const vec8 (&cur)[2][NPL]) {
+  // DEAD: the last feature tile's weight rows are zero -- its products and its fragment reads are left out and its accumulators keep their
+  // starting value, the bias, as the zero products would leave it.  (Rows with non-finite activations are not part of the
+  // contract: the full path would turn such a row's dead slots into NaN where this one leaves the bias; both sit under
+  // zero weights downstream.)  The live tiles keep their order and their pins.
+  static_assert(NP - 1 > MID + 1, "the last pair runs behind the barrier and carries no global loads");
+  auto mm_pair = [&](auto dead_c, int pr, const vec8 (&f)[2][NPL], const vec8 (&cur)[2][NPL]) {
     const int ft = 2 * pr;
-    if (NPL == 3) {
+    if (decltype(dead_c)::value && pr == NP - 1) {
+      if constexpr (NPL == 3) {
+        USF_MM(ft, f[0][2], 0); USF_MM(ft, f[0][1], 1); USF_MM(ft, f[0][0], NPL - 1); USF_MM(ft, f[0][1], 0);
+        USF_MM(ft, f[0][0], 1); USF_MM(ft, f[0][0], 0);
+      } else {
+        USF_MM(ft, f[0][1], 0); USF_MM(ft, f[0][0], 1); USF_MM(ft, f[0][0], 0);
+      }
+    } else if constexpr (NPL == 3) {
       USF_MM(ft, f[0][2], 0); USF_MM(ft + 1, f[1][2], 0); USF_MM(ft, f[0][1], 1); USF_MM(ft + 1, f[1][1], 1);
       USF_MM(ft, f[0][0], NPL - 1); USF_MM(ft + 1, f[1][0], NPL - 1); USF_MM(ft, f[0][1], 0); USF_MM(ft + 1, f[1][1], 0);
       USF_MM(ft, f[0][0], 1); USF_MM(ft + 1, f[1][0], 1); USF_MM(ft, f[0][0], 0); USF_MM(ft + 1, f[1][0], 0);
@@ -425,18 +485,23 @@ __global__ __launch_bounds__(512, 2) void gemm_planes_kernel(const PlArgs p) {
 #endif
   // fA holds the slab's first pair on entry; the two fragment sets alternate as "current" / "being read"; the first
   // pair of the NEXT slab lands in fA when NP is even, in fB when NP is odd (the caller swaps them then)
-  auto slab = [&](int s, int ring_s, const vec8 (&cur)[2][NPL], vec8 (&nxt)[2][NPL], vec8 (&fA)[2][NPL], vec8 (&fB)[2][NPL]) {
+  auto slab = [&](auto dead_c, int s, int ring_s, const vec8 (&cur)[2][NPL], vec8 (&nxt)[2][NPL], vec8 (&fA)[2][NPL], vec8 (&fB)[2][NPL]) {
+    constexpr bool DEAD = decltype(dead_c)::value;
     LSTAMP(l0);
     const int ring_n = (ring_s == 2) ? 0 : ring_s + 1;
     const float* wl = wl0 + ring_s * STG;
     const float* wln = wl0 + ring_n * STG;
+    // the fragments of pair pr + 1 are read under pair pr: half of them when that pair's second tile is dead
+    auto read_next = [&](int pr, vec8 (&f)[2][NPL]) {
+      if (DEAD && pr + 1 == NP - 1) read_half(wl, pr + 1, f); else read_pair(wl, pr + 1, f);
+    };
     float* wb = wring + ring_n * STG;
     issue_a(ks(min(s + 1, nslab - 1)), nxt);
     // ---- pairs in front of the barrier; the last of them carries the stores that stage slab s + 1 ----
 #pragma unroll
     for (int pr = 0; pr <= MID; ++pr) {
-      if (pr & 1) { if (pr + 1 < NP) read_pair(wl, pr + 1, fA); mm_pair(pr, fB, cur); }
-      else        { if (pr + 1 < NP) read_pair(wl, pr + 1, fB); mm_pair(pr, fA, cur); }
+      if (pr & 1) { if (pr + 1 < NP) read_next(pr, fA); mm_pair(dead_c, pr, fB, cur); }
+      else        { if (pr + 1 < NP) read_next(pr, fB); mm_pair(dead_c, pr, fA, cur); }
       if (pr == MID) store_w(wb, wst);
       // pins (masks: 0x008 MFMA, 0x020 VMEM read, 0x100 DS read, 0x200 DS write): the fragment reads first, then the
       // pair's MFMAs with this pair's share of the global loads / the staging stores dealt in
@@ -467,12 +532,15 @@ __global__ __launch_bounds__(512, 2) void gemm_planes_kernel(const PlArgs p) {
     issue_w(ks(min(s + 2, nslab - 1)) * 32, wst);
 #pragma unroll
     for (int pr = MID + 1; pr < NP; ++pr) {
-      if (pr & 1) { if (pr + 1 < NP) read_pair(wl, pr + 1, fA); else read_pair(wln, 0, fA); mm_pair(pr, fB, cur); }
-      else        { if (pr + 1 < NP) read_pair(wl, pr + 1, fB); else read_pair(wln, 0, fB); mm_pair(pr, fA, cur); }
-      __builtin_amdgcn_sched_group_barrier(0x100, 2 * NPL, 0);
+      if (pr & 1) { if (pr + 1 < NP) read_next(pr, fA); else read_pair(wln, 0, fA); mm_pair(dead_c, pr, fB, cur); }
+      else        { if (pr + 1 < NP) read_next(pr, fB); else read_pair(wln, 0, fB); mm_pair(dead_c, pr, fA, cur); }
+      if (DEAD && pr + 1 == NP - 1) __builtin_amdgcn_sched_group_barrier(0x100, NPL, 0);
+      else __builtin_amdgcn_sched_group_barrier(0x100, 2 * NPL, 0);
       if (pr == MID + 1) {
         __builtin_amdgcn_sched_group_barrier(0x008, 2 * NPR, 0);
         __builtin_amdgcn_sched_group_barrier(0x020, NWV, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 2 * NPR, 0);
+      } else if (DEAD && pr == NP - 1) {
         __builtin_amdgcn_sched_group_barrier(0x008, 2 * NPR, 0);
       } else {
         __builtin_amdgcn_sched_group_barrier(0x008, 4 * NPR, 0);
@@ -483,15 +551,14 @@ __global__ __launch_bounds__(512, 2) void gemm_planes_kernel(const PlArgs p) {
     LACC(0, l0, l1); LACC(1, l1, l2); LACC(2, l2, l3); LACC(3, l3, l4);
   };
   PSTAMP(t1);
-  int s = 0, ring = 0;
-  for (; s + 2 <= nslab; s += 2) {
-    slab(s, ring, pa, pb, fr, f2);
-    ring = (ring == 2) ? 0 : ring + 1;
-    if (NP & 1) slab(s + 1, ring, pb, pa, f2, fr); else slab(s + 1, ring, pb, pa, fr, f2);
-    ring = (ring == 2) ? 0 : ring + 1;
-  }
-  if (s < nslab) slab(s, ring, pa, pb, fr, f2);
-#undef USF_MM
+    int s = 0, ring = 0;
+    for (; s + 2 <= nslab; s += 2) {
+      slab(dead_c, s, ring, pa, pb, fr, f2);
+      ring = (ring == 2) ? 0 : ring + 1;
+      if (NP & 1) slab(dead_c, s + 1, ring, pb, pa, f2, fr); else slab(dead_c, s + 1, ring, pb, pa, fr, f2);
+      ring = (ring == 2) ? 0 : ring + 1;
+    }
+    if (s < nslab) slab(dead_c, s, ring, pa, pb, fr, f2);
   PSTAMP(t2);
 
   // ---- epilogue ----
@@ -607,12 +674,15 @@ __global__ __launch_bounds__(512, 2) void gemm_planes_kernel(const PlArgs p) {
 #endif
   }
 #endif
+  };  // tile
+  if (dead) tile(std::true_type()); else tile(std::false_type());
+#undef USF_MM
   }  // virtual blocks
 #ifdef USF_STAMP
-  if (p.span && tid == 0) atomicMax(p.span + 1, __builtin_amdgcn_s_memrealtime());
+  if (p.span && tid0 == 0) atomicMax(p.span + 1, __builtin_amdgcn_s_memrealtime());
 #endif
 #ifndef USF_NO_CLOCK
-  if (p.clk && tid == 0) {
+  if (p.clk && tid0 == 0) {
     atomicAdd(p.clk, __builtin_amdgcn_s_memtime() - clk_c0);
     atomicAdd(p.clk + 1, __builtin_amdgcn_s_memrealtime() - clk_r0);
   }
@@ -691,6 +761,7 @@ int gemm_planes(const usf_gemm_planes_desc* d, hipStream_t stream) {
   a.c_nkb = (int)d->c_nkb; a.c_kb0 = (int)d->c_kb0; a.c_kbn = (int)d->c_kbn; a.N = (int)d->N;
   a.res_sign = d->res_sign; a.slope = d->slope; a.act = d->act; a.nbm = a.nbn = a.nvb = 0;
   a.range_flag = d->range_flag;
+  a.skip_dead = (int)tuning("planes_skip_dead", 1);         // A/B aid: 0 = every tile runs the full K loop
   a.b_tab = d->base_tab; a.b_part = d->base_part; a.b_stride = (int)d->base_tab_stride; a.b_base = d->base;
   a.dbg = nullptr; a.span = nullptr;
   a.clk = clock_buffer();
