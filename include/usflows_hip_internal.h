@@ -1,7 +1,7 @@
 /*
  * usflows_hip_internal.h -- the rest of libusflows_hip.so's C exports: the plumbing of the Python engine (usflows_amd) that
  * happens to cross the C boundary.  Every backward, weight-gradient and job-queue entry point of the training path, the
- * SophiaG optimizer, which kernel variant a descriptor selects, and the measurement / tuning aids.
+ * SophiaG and Adam optimizers and the gradient clip, which kernel variant a descriptor selects, and the measurement / tuning aids.
  *
  * NO STABILITY PROMISE: anything here may change in any release.  Such a change bumps USF_INTERNAL_VERSION, never
  * USF_ABI_VERSION, which covers usflows_hip.h alone.  A binding that mirrors this file checks usf_internal_version() next
@@ -70,7 +70,8 @@ int usf_internal_version(void);
  *   Flow.fit (flows.py:196-203) at batches of thousands of rows.
  *
  * usf_sizeof_desc(kind) also reports sizeof(usf_mt_chunk|usf_grad_job|usf_psum_job) for kind 8|11|12 and
- * sizeof(usf_gated_norm_bwd_desc|usf_wgrad_job|usf_wreduce_job|usf_wplanes_job) for kind 13|14|15|16.
+ * sizeof(usf_gated_norm_bwd_desc|usf_wgrad_job|usf_wreduce_job|usf_wplanes_job) for kind 13|14|15|16 and
+ * sizeof(usf_adam_chunk|usf_grad_chunk) for kind 17|18.
  */
 
 /*
@@ -451,6 +452,45 @@ typedef struct usf_mt_chunk {
 int usf_sophiag_step_f32(const usf_mt_chunk* chunks, int64_t n_chunks, float decay, float beta1, float one_minus_beta1,
                          float rho_bs, float neg_lr, int32_t maximize, usf_stream_t stream);
 int usf_sophiag_hessian_f32(const usf_mt_chunk* chunks, int64_t n_chunks, float beta2, float one_minus_beta2,
+                            usf_stream_t stream);
+
+/*
+ * Adam / AdamW (torch/optim/adam.py, _single_tensor_adam, the non-capturable branch) over all fp32 tensors of a parameter
+ * group in one launch, in torch's operation order:
+ *   g' = maximize ? -g : g;   L2 decay: g' = fma(wd, p, g');   decoupled decay (AdamW): p *= 1 - lr * wd
+ *   m = lerp(m, g', 1 - beta1);   v = v * beta2 + (1 - beta2) * g' * g';   amsgrad: vmax = max(vmax, v)
+ *   denom = sqrt(v | vmax) / sqrt(1 - beta2^t) + eps;   p += (-lr / (1 - beta1^t)) * (m / denom)
+ * `chunks` is a DEVICE array, one 256-thread block per chunk (the host cuts tensors into pieces of 16 384 elements); vmax
+ * is read with USF_ADAM_AMSGRAD only.  The step count t lives on the DEVICE: steps[n_slots] (int64), one counter per group
+ * of tensors that have taken the same number of steps; a chunk names its counter in `slot`.  The call first adds 1 to
+ * every counter in a small launch of its own, then runs the update, whose blocks only read them -- so a captured call
+ * (hipGraph) advances t on every replay.  beta^t is computed in fp64 on the device, everything else in fp32.  No
+ * atomics, no host read-back.  28 bytes of HBM traffic per parameter and step (36 with amsgrad).
+ */
+typedef struct usf_adam_chunk {
+  float* p; const float* g; float* m; float* v; float* vmax;
+  int32_t n; int32_t slot;
+} usf_adam_chunk;
+#define USF_ADAM_MAXIMIZE 1
+#define USF_ADAM_AMSGRAD 2
+#define USF_ADAM_DECOUPLED 4
+int usf_adam_step_f32(const usf_adam_chunk* chunks, int64_t n_chunks, int64_t* steps, int64_t n_slots, double lr, double beta1,
+                      double beta2, double eps, double weight_decay, int32_t flags, usf_stream_t stream);
+
+/*
+ * torch.nn.utils.clip_grad_norm_(params, max_norm) with the 2-norm and error_if_nonfinite=False, over a DEVICE table of
+ * gradient chunks, without atomics or a host synchronisation:
+ *   usf_grad_sqnorm_partials_f32: partials[b] = the sum of squares of chunk b in fp64 (one block per chunk, fixed order)
+ *   usf_grad_clip_scale_f32:      every block adds all n_chunks partials in one fixed order, forms
+ *                                 coef = min(max_norm / (sqrt(total) + 1e-6), 1) (fp64, rounded to fp32 once) and scales
+ *                                 its chunk of g in place.  A non-finite norm propagates as in torch.
+ */
+typedef struct usf_grad_chunk {
+  float* g;
+  int32_t n; int32_t reserved;
+} usf_grad_chunk;
+int usf_grad_sqnorm_partials_f32(const usf_grad_chunk* chunks, int64_t n_chunks, double* partials, usf_stream_t stream);
+int usf_grad_clip_scale_f32(const usf_grad_chunk* chunks, int64_t n_chunks, const double* partials, double max_norm,
                             usf_stream_t stream);
 
 /* (Leaky)ReLU backward from the saved layer OUTPUT h: d[m,j] *= (h[m,j] > 0 ? 1 : slope), slope >= 0

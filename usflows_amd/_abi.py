@@ -98,6 +98,16 @@ class MtChunk(C.Structure):
     _fields_ = [("p", _fp), ("g", _fp), ("m", _fp), ("h", _fp), ("n", C.c_int32), ("reserved", C.c_int32)]
 
 
+class AdamChunk(C.Structure):
+    """usf_adam_chunk: one block's share of one parameter tensor (usf_adam_step_f32); slot: its device step counter"""
+    _fields_ = [("p", _fp), ("g", _fp), ("m", _fp), ("v", _fp), ("vmax", _fp), ("n", C.c_int32), ("slot", C.c_int32)]
+
+
+class GradChunk(C.Structure):
+    """usf_grad_chunk: one block's share of one gradient tensor (usf_grad_sqnorm_partials_f32 / usf_grad_clip_scale_f32)"""
+    _fields_ = [("g", _fp), ("n", C.c_int32), ("reserved", C.c_int32)]
+
+
 class GatedNormDesc(C.Structure):
     """usf_gated_norm_desc: row pass of the vector ConvNet conditioner (gate, layer norm, activation)"""
     _fields_ = [("skip", _fp), ("ld_skip", C.c_int64), ("vg", _fp), ("ld_vg", C.c_int64), ("gate_off", C.c_int64),
@@ -184,7 +194,7 @@ class GradJob(C.Structure):
 # usf_sizeof_desc kind -> the struct whose size it reports: every Structure above (load() compares each one with C)
 SIZEOF_KINDS = {OP_LINEAR: LinearDesc, OP_COUPLING: CouplingDesc, 0: Op, 3: LuPrepDesc, 4: PackJob, OP_PACK_PLANES: PackPlanesDesc,
                 OP_GEMM_PLANES: GemmPlanesDesc, OP_COUPLING_PLANES: CouplingPlanesDesc, 8: MtChunk, OP_GATED_NORM: GatedNormDesc,
-                OP_CALL: CallDesc, 11: GradJob, 12: PsumJob, 13: GatedNormBwdDesc, 14: WgradJob, 15: WReduceJob, 16: WPlanesJob}
+                OP_CALL: CallDesc, 11: GradJob, 12: PsumJob, 13: GatedNormBwdDesc, 14: WgradJob, 15: WReduceJob, 16: WPlanesJob, 17: AdamChunk, 18: GradChunk}
 
 
 # every symbol include/usflows_hip.h declares (the stable public ABI): (restype, argtypes)
@@ -309,6 +319,10 @@ INTERNAL_SYMBOLS = {
     "usf_sophiag_step_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32,
                                        C.c_void_p]),
     "usf_sophiag_hessian_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p]),
+    "usf_adam_step_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double,
+                                    C.c_double, C.c_int32, C.c_void_p]),
+    "usf_grad_sqnorm_partials_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "usf_grad_clip_scale_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p]),
     "usf_colsum_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_float, C.c_float, _fp, C.c_int64,
                                  C.c_void_p]),
     "usf_act_grad_f32": (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_float,

@@ -23,7 +23,7 @@ from ._abi import (  # noqa: E402,F401  -- the declarations, re-exported: caller
     BASE_LPNORM1, BASE_LPNORM2, BASE_LPNORMINF, BASE_ROWSUM, NORM_LOGNORMAL, NORM_GAMMA, NORM_RAW_PARAMS, RADIAL_MAX_K, OP_LINEAR,
     OP_COUPLING, OP_PACK_PLANES, OP_GEMM_PLANES, OP_COUPLING_PLANES, OP_GATED_NORM, OP_CALL, PLANES_BF16X3, PLANES_F16X2, CALL_FNS,
     FN_COUPLING_PLANES_CTX, FN_COUPLING_VCTX, VCTX_MAX,
-    _fp, LinearDesc, CouplingDesc, PackPlanesDesc, GemmPlanesDesc, CouplingPlanesDesc, MtChunk, GatedNormDesc, GatedNormBwdDesc,
+    _fp, LinearDesc, CouplingDesc, PackPlanesDesc, GemmPlanesDesc, CouplingPlanesDesc, MtChunk, AdamChunk, GradChunk, GatedNormDesc, GatedNormBwdDesc,
     CallDesc, _OpUnion, Op, LuPrepDesc, PackJob, PsumJob, WgradJob, WReduceJob, WPlanesJob, GradJob, SIZEOF_KINDS, PUBLIC_SYMBOLS,
     INTERNAL_SYMBOLS, SYMBOLS)
 
@@ -1406,3 +1406,25 @@ def sophiag_step(chunks_dev: torch.Tensor, n_chunks: int, *, decay, beta1, rho_b
 def sophiag_hessian(chunks_dev: torch.Tensor, n_chunks: int, *, beta2) -> None:
     _launch("usf_sophiag_hessian_f32", (chunks_dev.data_ptr(), n_chunks, beta2, 1.0 - beta2,
                                         current_stream(chunks_dev.device)), keep=chunks_dev)
+
+
+ADAM_MAXIMIZE, ADAM_AMSGRAD, ADAM_DECOUPLED = 1, 2, 4
+
+
+def adam_step(chunks_dev: torch.Tensor, n_chunks: int, steps_dev: torch.Tensor, *, lr, beta1, beta2, eps, weight_decay,
+              maximize=False, amsgrad=False, decoupled=False) -> None:
+    """usf_adam_step_f32 on a device table of usf_adam_chunk and the int64 step counters it names (usflows_amd/optim.py)"""
+    flags = (ADAM_MAXIMIZE if maximize else 0) | (ADAM_AMSGRAD if amsgrad else 0) | (ADAM_DECOUPLED if decoupled else 0)
+    _launch("usf_adam_step_f32", (chunks_dev.data_ptr(), n_chunks, steps_dev.data_ptr(), steps_dev.numel(), float(lr), float(beta1),
+                                  float(beta2), float(eps), float(weight_decay), flags, current_stream(chunks_dev.device)),
+            keep=(chunks_dev, steps_dev))
+
+
+def grad_clip(chunks_dev: torch.Tensor, n_chunks: int, partials_dev: torch.Tensor, max_norm: float) -> None:
+    """clip_grad_norm_ over a device table of usf_grad_chunk: usf_grad_sqnorm_partials_f32, then usf_grad_clip_scale_f32"""
+    assert partials_dev.dtype == torch.float64 and partials_dev.numel() >= n_chunks
+    stream = current_stream(chunks_dev.device)
+    _launch("usf_grad_sqnorm_partials_f32", (chunks_dev.data_ptr(), n_chunks, partials_dev.data_ptr(), stream),
+            keep=(chunks_dev, partials_dev))
+    _launch("usf_grad_clip_scale_f32", (chunks_dev.data_ptr(), n_chunks, partials_dev.data_ptr(), float(max_norm), stream),
+            keep=(chunks_dev, partials_dev))

@@ -157,6 +157,10 @@ int conv2d_weight_planes(const float* w, void* planes, int64_t cin, int64_t cout
 int sophiag_step(const usf_mt_chunk* chunks, int64_t n_chunks, float decay, float beta1, float one_minus_beta1, float rho_bs,
                  float neg_lr, int32_t maximize, hipStream_t stream);
 int sophiag_hessian(const usf_mt_chunk* chunks, int64_t n_chunks, float beta2, float one_minus_beta2, hipStream_t stream);
+int adam_step(const usf_adam_chunk* chunks, int64_t n_chunks, int64_t* steps, int64_t n_slots, double lr, double beta1,
+              double beta2, double eps, double weight_decay, int32_t flags, hipStream_t stream);
+int grad_sqnorm_partials(const usf_grad_chunk* chunks, int64_t n_chunks, double* partials, hipStream_t stream);
+int grad_clip_scale(const usf_grad_chunk* chunks, int64_t n_chunks, const double* partials, double max_norm, hipStream_t stream);
 int wgrad(const float* Y, int64_t ldy, const float* A, int64_t lda, int64_t M, int64_t N, int64_t K, float* G,
           int64_t ldg, float alpha, float beta, int32_t mode, float* workspace, int64_t workspace_floats,
           hipStream_t stream, float* colsum_out = nullptr, float cs_alpha = 0.f, float cs_beta = 0.f);
@@ -228,6 +232,8 @@ int usf_sizeof_desc(int32_t kind) {
     case 14: return (int)sizeof(usf_wgrad_job);
     case 15: return (int)sizeof(usf_wreduce_job);
     case 16: return (int)sizeof(usf_wplanes_job);
+    case 17: return (int)sizeof(usf_adam_chunk);
+    case 18: return (int)sizeof(usf_grad_chunk);
     default: return -1;
   }
 }
@@ -358,6 +364,17 @@ int usf_sophiag_step_f32(const usf_mt_chunk* chunks, int64_t n_chunks, float dec
 int usf_sophiag_hessian_f32(const usf_mt_chunk* chunks, int64_t n_chunks, float beta2, float one_minus_beta2,
                             usf_stream_t stream) {
   return usf::sophiag_hessian(chunks, n_chunks, beta2, one_minus_beta2, (hipStream_t)stream);
+}
+int usf_adam_step_f32(const usf_adam_chunk* chunks, int64_t n_chunks, int64_t* steps, int64_t n_slots, double lr, double beta1,
+                      double beta2, double eps, double weight_decay, int32_t flags, usf_stream_t stream) {
+  return usf::adam_step(chunks, n_chunks, steps, n_slots, lr, beta1, beta2, eps, weight_decay, flags, (hipStream_t)stream);
+}
+int usf_grad_sqnorm_partials_f32(const usf_grad_chunk* chunks, int64_t n_chunks, double* partials, usf_stream_t stream) {
+  return usf::grad_sqnorm_partials(chunks, n_chunks, partials, (hipStream_t)stream);
+}
+int usf_grad_clip_scale_f32(const usf_grad_chunk* chunks, int64_t n_chunks, const double* partials, double max_norm,
+                            usf_stream_t stream) {
+  return usf::grad_clip_scale(chunks, n_chunks, partials, max_norm, (hipStream_t)stream);
 }
 int usf_layernorm_channels_f32(const float* x, float* y, int64_t B, int64_t C, int64_t P, const float* gamma,
                                const float* beta, float eps, int32_t act, float slope, usf_stream_t stream) {

@@ -143,6 +143,8 @@ class FitMixin:
             device = torch.device("cuda:0") if torch.cuda.is_available() else torch.device("cpu")
         model = self.to(device)
         optim = optim(model.parameters(), **optim_params) if optim_params is not None else optim(model.parameters())
+        from .optim import adopt
+        optim = adopt(optim) or optim        # torch's Adam / AdamW: one arithmetic for eager and replayed steps (optim.py)
         N = len(data_train)
         epoch_losses = []
         with self.fit_stream(device):
@@ -170,6 +172,10 @@ class FitMixin:
 
     def _fit_epochs(self, model, optim, data_train, N, epochs, batch_size, shuffle, gradient_clip, device, epoch_losses):
         feed = None
+        clip = None
+        if gradient_clip is not None:
+            from .optim import GradClip
+            clip = GradClip(model.parameters(), gradient_clip)     # (torch's clip_grad_norm_ for anything but device gradients)
         for _ in range(epochs):
             losses = []
             if shuffle:
@@ -195,7 +201,7 @@ class FitMixin:
                     # conditioning scale recommended by SoftFlow (flows.py:188-191)
                     noise = noise.unsqueeze(-1).detach() * 2 / self.training_noise_prior.high
                 dp = self.__dict__.get("_grad_allreduce")      # parallel.data_parallel_training on a flow without the flat arena
-                graphed = model._train_graph_step(optim, sample, noise) if (gradient_clip is None and dp is None) else None
+                graphed = model._train_graph_step(optim, sample, noise, clip) if dp is None else None
                 if graphed is not None:
                     losses.append(graphed)
                 else:
@@ -209,8 +215,8 @@ class FitMixin:
                     if dp is not None:
                         from .parallel import allreduce_gradients
                         allreduce_gradients(model, sample.shape[0], group=dp[0], average=dp[1])
-                    if gradient_clip is not None:
-                        torch.nn.utils.clip_grad_norm_(model.parameters(), gradient_clip)
+                    if clip is not None:
+                        clip()
                     optim.step()
                     # (drop the step's autograd graph now: it keeps the parameters' AccumulateGrad nodes alive, and those are
                     # bound to the stream they were created on -- a later capture of the step must create its own)
@@ -231,8 +237,10 @@ class FitMixin:
     train_graph_max_rows = 4096   # flat flows with a device backward: above this the step is not launch-bound any more
     _TRAIN_GRAPH_EAGER_STEPS = 3
 
-    def _train_graph_step(self, optim, sample: torch.Tensor, noise) -> Optional[float]:
-        """one optimiser step as a graph replay; the loss as a float, or None when the step has to run eagerly.  The caller
+    def _train_graph_step(self, optim, sample: torch.Tensor, noise, clip=None) -> Optional[float]:
+        """one optimiser step as a graph replay; the loss as a float, or None when the step has to run eagerly.  ``clip``
+        (optim.GradClip) runs between the backward pass and the update.  A plain torch.optim.Adam / AdamW is stepped through
+        the object ``optim.adopt`` makes of it (same param_groups and state), kept in the graph state.  The caller
         must not hold the loss tensor (or anything else with a grad_fn over the parameters) of an earlier eager step: the
         parameters' gradient-accumulation nodes stay bound to the eager stream through it, and a capture that reaches over
         to that stream does not survive hipStreamEndCapture."""
@@ -241,8 +249,14 @@ class FitMixin:
                 and not getattr(self, "_train_graph_failed", False) and not torch.cuda.is_current_stream_capturing()):
             return None
         from .sophia import SophiaG
-        if not (isinstance(optim, SophiaG) or type(optim) is torch.optim.SGD):
-            return None               # (optimisers whose step is known to be free of host synchronisation)
+        from .optim import adopt
+        st = self.__dict__.get("_train_graph_state")
+        if st is not None and st.get("given") is optim:
+            given, optim = optim, st["optim"]
+        else:
+            given, optim = optim, (optim if type(optim) is torch.optim.SGD else adopt(optim))
+        if optim is None:
+            return None               # (optimisers whose step is known to be free of host synchronisation: SGD, SophiaG, Adam)
         if any(g_.get("capturable") for g_ in optim.param_groups if isinstance(optim, SophiaG)):
             return None
         # bases that build a fresh, argument-validating torch distribution on every log_prob (DistributionModule) read a
@@ -266,10 +280,9 @@ class FitMixin:
                 if torch.cuda.current_stream(sample.device) != self.__dict__.get("_fit_stream") or \
                         sample.shape[0] > self.train_graph_max_rows:
                     return None
-        st = self.__dict__.get("_train_graph_state")
         key = (tuple(sample.shape), None if noise is None else tuple(noise.shape))
-        if st is None or st["optim"] is not optim:
-            st = self.__dict__["_train_graph_state"] = dict(optim=optim, key=key, seen=0, graph=None, replays=0)
+        if st is None or st.get("given") is not given or st.get("clip") is not clip:
+            st = self.__dict__["_train_graph_state"] = dict(optim=optim, given=given, clip=clip, key=key, seen=0, graph=None, replays=0)
         if st["key"] != key:
             if st["graph"] is not None:
                 return None           # ragged last batch of an epoch: eagerly; the captured graph serves the next epoch
@@ -284,13 +297,14 @@ class FitMixin:
             sx = sample.detach().clone()
             sc = noise.detach().clone() if noise is not None else None
             gflat = None
+            owners = [o for o in (clip, optim) if hasattr(o, "defer_uploads")]      # (chunk tables: _mt_tables.ChunkTables)
             with torch.enable_grad():
                 tp = self._train_path(sample, noise)
             if tp is not None and tp.bind_flat_grads():
                 # flat flows: the gradients become views of one buffer -- zeroed and accumulated by one launch each
                 gflat = tp._gflat
-                if hasattr(optim, "prepare_tables"):
-                    optim.prepare_tables()
+                for o in owners:
+                    o.prepare_tables()
             bound = set() if gflat is None else {id(e[0]) for e in tp._gflat_views.values()}
 
             def body():
@@ -313,6 +327,8 @@ class FitMixin:
                 finally:
                     if gflat is not None:
                         tp.use_bound_node = False
+                if clip is not None:
+                    clip()              # (behind the backward scope: the deferred weight-gradient sums have been flushed)
                 optim.step()
                 return loss.detach()
 
@@ -321,21 +337,21 @@ class FitMixin:
                 graph = torch.cuda.CUDAGraph()
                 cur = torch.cuda.current_stream(sample.device)
                 on_own = cur == self.__dict__.get("_fit_stream")
-                if hasattr(optim, "defer_uploads"):
-                    optim.defer_uploads(True)
+                for o in owners:
+                    o.defer_uploads(True)
                 tables = _ext.capture_tables(sample.device)          # (job tables of launches inside the capture: _ext.conv_wgrad)
                 try:
                     with tables, (torch.cuda.graph(graph, stream=cur) if on_own else torch.cuda.graph(graph)):
                         sl = body()
                 finally:
-                    if hasattr(optim, "defer_uploads"):
-                        optim.defer_uploads(False)
-                if hasattr(optim, "flush_uploads"):
-                    optim.flush_uploads()
+                    for o in owners:
+                        o.defer_uploads(False)
+                for o in owners:
+                    o.flush_uploads()
                 tables.upload()
             except Exception as e:      # noqa: BLE001  (an op that cannot be captured: eager steps from now on)
                 self._train_graph_failed = True
-                self._recover_from_failed_capture(optim, params)
+                self._recover_from_failed_capture(optim, params, clip)
                 import traceback
                 where = " <- ".join(f"{f.name} ({os.path.basename(f.filename)}:{f.lineno})"
                                     for f in reversed(traceback.extract_tb(e.__traceback__)[-4:]))
@@ -346,7 +362,8 @@ class FitMixin:
             # the graph holds raw addresses: keep what it writes to and reads from alive whatever happens to `p.grad` or to
             # the optimiser's pointer tables afterwards (an eager step in between -- the ragged last batch of an epoch --
             # must not free them: a replay into freed gradient buffers is a GPU memory fault waiting for the allocator)
-            keep = ([p.grad for p in params], dict(getattr(optim, "_tables", {}) or {}), tables.keep)
+            keep = ([p.grad for p in params], dict(getattr(optim, "_tables", {}) or {}), tables.keep,
+                    dict(getattr(clip, "_tables", {}) or {}))
             st.update(graph=graph, x=sx, ctx=sc, loss=sl, params=params, keep=keep)
         st["x"].copy_(sample)
         if st["ctx"] is not None:
@@ -359,7 +376,7 @@ class FitMixin:
             torch.autograd.graph.increment_version(p)      # a replay runs no Python: tell the version-keyed caches
         return float(st["loss"])
 
-    def _recover_from_failed_capture(self, optim, params) -> None:
+    def _recover_from_failed_capture(self, optim, params, clip=None) -> None:
         """A capture that broke off ran no GPU work, but its Python side ran: version counters moved, the engine took its
         parameter pack for refreshed (the refreshing launches were only recorded, then discarded) and the training path
         its tapes for current.  Drop every cache keyed on them -- the next (eager) step rebuilds from the parameters'
@@ -392,11 +409,9 @@ class FitMixin:
             eng._ws.clear()
         self._train_obj = None
         self.__dict__.pop("_train_graph_state", None)
-        if hasattr(optim, "_tables"):
-            # (a pointer table built during the broken capture was never uploaded, and a later allocation may land on the
-            # addresses it is keyed on)
-            optim._tables = {}
-            optim._pending_uploads = []
+        for o in (optim, clip):
+            if hasattr(o, "reset_tables"):
+                o.reset_tables()
         for p in params:
             if p.grad is not None:
                 p.grad = None
@@ -416,7 +431,7 @@ class FitMixin:
         gradients are zeroed IN PLACE: the captured graph (and the optimiser's pointer table inside it) address exactly these
         buffers, and autograd accumulates into an existing ``.grad`` in place, so eager steps and replays keep sharing them"""
         st = self.__dict__.get("_train_graph_state")
-        if st is not None and st.get("graph") is not None and st["optim"] is optim:
+        if st is not None and st.get("graph") is not None and (st["optim"] is optim or st.get("given") is optim):
             for p, g in zip(st["params"], st["keep"][0]):
                 if g is not None:
                     if p.grad is not g:
