@@ -1,6 +1,6 @@
 """Canonical dumps of what the host side of the flat-flow path hands to the library, for comparing two checkouts on the CPU.
 
-    python tools/plan_dump.py plans  > plans.txt     # one record per plan of a fixed list of configurations
+    python tools/plan_dump.py plans  > plans.txt     # one record per plan of a fixed list of configurations (--only NAME...: a part)
     python tools/plan_dump.py trace  > trace.txt     # the call sequence of one log_prob_with_grad + backward per configuration
 
 Both run without a GPU under tests/emulator.py's emulation of the entry points (the library is loaded for its host-only
@@ -30,16 +30,25 @@ class Patch:
     """the part of pytest's monkeypatch the emulator's install functions use"""
 
     def __init__(self):
-        self.done = []
+        self.done, self.items = [], []
 
     def setattr(self, obj, name, value):
         self.done.append((obj, name, getattr(obj, name)))
         setattr(obj, name, value)
 
+    def setitem(self, mapping, key, value):
+        self.items.append((mapping, key, key in mapping, mapping.get(key)))
+        mapping[key] = value
+
     def undo(self):
         for obj, name, old in reversed(self.done):
             setattr(obj, name, old)
-        self.done = []
+        for mapping, key, had, old in reversed(self.items):
+            if had:
+                mapping[key] = old
+            else:
+                mapping.pop(key, None)
+        self.done, self.items = [], []
 
 
 # ---- naming tensors ----------------------------------------------------------------------------------------------------
@@ -147,7 +156,9 @@ def op_record(op, names, _ext):
     d = getattr(op.u, member)
     if member == "call":
         a = [int(d.a[j]) for j in range(d.n_args)]
-        if _ext.is_ctx_prefix(op):
+        if d.fn == _ext.FN_COUPLING_VCTX:          # ctx, ld_ctx, ctx_dim, W_ctx_t, ldw_ctx, b_ctx
+            a = [names.of_ptr(a[0]), a[1], a[2], names.of_ptr(a[3]), a[4], names.of_ptr(a[5])]
+        elif _ext.is_ctx_prefix(op):               # ctx, ctx_stride, w_ctx, b_ctx
             a = [names.of_ptr(a[0]), a[1], names.of_ptr(a[2]), names.of_ptr(a[3])]
         return f"call fn={d.fn} n_args={d.n_args} a={a}"
     parts = [f"{name}={_field(getattr(d, name), t, names, _ext)}" for name, t in d._fields_]
@@ -242,7 +253,65 @@ def _planes_train_ctx_flow():
     return flow, eng
 
 
-def dump_plans(emit):
+def _single_layer_plans(one, name, dev):
+    """every layer of a flow as an engine of its own, as layer.forward / layer.backward dispatch: the one place a stand-alone
+    scale launch and the gather in front of a coupling occur"""
+    from golden_util import load_case
+    from model_util import build_flow
+    from usflows_amd.engine import FlowEngine
+    spec, sd, _a = load_case(name)
+    for j, layer in enumerate(build_flow(spec, sd).layers):
+        eng = FlowEngine([layer])
+        _switches(eng, False, False)
+        for direction in ("forward", "backward"):
+            one(f"single {name} layer{j} {type(layer).__name__} B=37 {direction} user", eng, direction, 37, dev, False, "user")
+
+
+def _flat_branch_plans(one, want, dev):
+    """the branches of the fp32-row builder the golden list never enters: the tiny-layer kernel, vector contexts, a general
+    conditioner in training, A_planes_out, hidden activations saved by the fused kernel, one-layer engines"""
+    import vctx_cases
+    from golden_util import load_case
+    from model_util import build_flow
+    for name in ("init_d10_k10_gmlive", "init_d2_k10_gmlive"):               # engine defaults: every coupling is "tiny"
+        if want(f"tiny:{name}"):
+            spec, sd, _a = load_case(name)
+            for train in (False, True):
+                eng = build_flow(spec, sd).engine()
+                eng.keep_factors = True
+                one(f"tiny {name} defaults B=32 train={train}", eng, "backward", 32, dev, False, "nat", train=train)
+    for name in ("d7_k3", "d16_k3", "d33_k2", "d64_k2_c10"):
+        if want(f"vctx:{name}"):
+            B = vctx_cases.CASES[name][2]
+            for train in (False, True):
+                eng = vctx_cases.build(name).engine()
+                eng.keep_factors = True
+                if name == "d64_k2_c10":
+                    eng.gemm_mode = "bf16x3"
+                one(f"vctx {name} B={B} mode={eng.gemm_mode} train={train}", eng, "backward", B, dev, True, "nat", train=train)
+    for name in ("synth_d16_k3_convnet_gated_ln", "synth_d33_k2_convnet_gated_conj"):
+        if want(f"general-train:{name}"):
+            spec, sd, _a = load_case(name)
+            eng = build_flow(spec, sd).engine()
+            eng.keep_factors = True
+            one(f"general-train {name} B=37", eng, "backward", 37, dev, False, "nat", train=True)
+    # fp32 rows in bf16x3 mode: (the planes flow, rows, fused override) -- A_planes_out needs usf_wgrad_planes_ok's 8192+ rows,
+    # the fused kernel's saved hidden activations hmax >= 256 and >= 1024 rows
+    for tag, cfg, B, fused in (("A_planes_out", (160, 2, [96, 64], False, 0), 40960, False),
+                               ("fused_hidden", (64, 2, [200, 256], False, 1), 1100, True)):
+        if want(f"rows-train:{tag}"):
+            _flow, eng = _planes_train_flow(*cfg)
+            eng.use_train_planes, eng.use_planes, eng.gemm_mode, eng.keep_factors = False, False, "bf16x3", True
+            if fused:
+                eng.use_fused_coupling = True
+                eng._fused_ok = lambda cp: len(cp["hidden"]) <= 3
+            one(f"rows-train {tag} {cfg} bf16x3 B={B}", eng, "backward", B, dev, False, "nat", train=True)
+    if want("single:synth_d7_k3_hh1_conj_normal"):
+        _single_layer_plans(one, "synth_d7_k3_hh1_conj_normal", dev)
+
+
+def dump_plans(emit, only=None):
+    """only: the case names to dump (a golden case's name, or a ``group:name`` of the lists below); None = all of them"""
     import torch
     from golden_util import case_names, load_case
     from model_util import build_flow
@@ -253,6 +322,7 @@ def dump_plans(emit):
     emulator.install_prep_emulation(patch)
     dev = torch.device("cpu")
     n = 0
+    want = lambda case: only is None or case in only      # noqa: E731
 
     def one(title, eng, *args, **kw):
         nonlocal n
@@ -264,34 +334,42 @@ def dump_plans(emit):
             emit(plan_record(title, eng, plan, _ext))
         n += 1
 
-    for name in case_names(small_only=True):
-        spec, sd, a = load_case(name)
-        natural = a.get("context") is not None or bool(spec.soft_training)
-        rows = (37, 32, 300) if name.endswith("_gmlive") else (37,)
-        for vname, fused, planes in VARIANTS:
-            for has_ctx in ((True, False) if name in CTX_CASES else (natural,)):
-                for B in rows:
-                    eng = FlowEngine(build_flow(spec, sd).layers)
-                    _switches(eng, fused, planes)
-                    for direction in ("backward", "forward"):
-                        for final in ("user", "nat", "base0"):
-                            one(f"{name} {vname} ctx={has_ctx} B={B} {direction} {final}", eng, direction, B, dev, has_ctx, final)
-    for name in TRAIN_F32:
-        spec, sd, a = load_case(name)
-        has_ctx = a.get("context") is not None or bool(spec.soft_training)
-        for fused in (False, True):
-            eng = build_flow(spec, sd).engine()
-            _switches(eng, fused, False)
+    try:
+        for name in case_names(small_only=True):
+            if not want(name):
+                continue
+            spec, sd, a = load_case(name)
+            natural = a.get("context") is not None or bool(spec.soft_training)
+            rows = (37, 32, 300) if name.endswith("_gmlive") else (37,)
+            for vname, fused, planes in VARIANTS:
+                for has_ctx in ((True, False) if name in CTX_CASES else (natural,)):
+                    for B in rows:
+                        eng = FlowEngine(build_flow(spec, sd).layers)
+                        _switches(eng, fused, planes)
+                        for direction in ("backward", "forward"):
+                            for final in ("user", "nat", "base0"):
+                                one(f"{name} {vname} ctx={has_ctx} B={B} {direction} {final}", eng, direction, B, dev, has_ctx, final)
+        for name in TRAIN_F32:
+            if not want(f"train:{name}"):
+                continue
+            spec, sd, a = load_case(name)
+            has_ctx = a.get("context") is not None or bool(spec.soft_training)
+            for fused in (False, True):
+                eng = build_flow(spec, sd).engine()
+                _switches(eng, fused, False)
+                eng.keep_factors = True
+                one(f"{name} train f32 fused={fused} B=37", eng, "backward", 37, dev, has_ctx, "nat", train=True)
+        if want("planes-train"):
+            for cfg in PLANES_TRAIN:
+                flow, eng = _planes_train_flow(*cfg)
+                eng.keep_factors = True
+                one(f"planes-train {cfg} B=37", eng, "backward", 37, dev, False, "nat", train=True)
+            flow, eng = _planes_train_ctx_flow()
             eng.keep_factors = True
-            one(f"{name} train f32 fused={fused} B=37", eng, "backward", 37, dev, has_ctx, "nat", train=True)
-    for cfg in PLANES_TRAIN:
-        flow, eng = _planes_train_flow(*cfg)
-        eng.keep_factors = True
-        one(f"planes-train {cfg} B=37", eng, "backward", 37, dev, False, "nat", train=True)
-    flow, eng = _planes_train_ctx_flow()
-    eng.keep_factors = True
-    one("planes-train ctx B=600", eng, "backward", 600, dev, True, "nat", train=True)
-    patch.undo()
+            one("planes-train ctx B=600", eng, "backward", 600, dev, True, "nat", train=True)
+        _flat_branch_plans(one, want, dev)
+    finally:
+        patch.undo()
     return n
 
 
@@ -350,14 +428,17 @@ class Trace:
         return out
 
 
-def trace_one(title, flow, eng, x, ctx, g_lp, emit, defer=True, fused=None):
+def trace_one(title, flow, eng, x, ctx, g_lp, emit, defer=True, fused=None, vctx=False):
     import emulator
     import emulator_ctx
+    import emulator_vctx
     from usflows_amd import _ext, training
     from usflows_amd.training import TrainPath
     patch = Patch()
     emulator.install_training_emulation(patch)
     emulator_ctx.install(patch)
+    if vctx:
+        emulator_vctx.install(patch)
     tr = Trace(_ext)
     wrapped = set()
     for obj, name, _old in list(patch.done):
@@ -428,12 +509,24 @@ def dump_trace(emit):
         g_lp = torch.randn(x.shape[0], generator=torch.Generator().manual_seed(1))
         trace_one(f"{title}: {name} B={x.shape[0]}", flow, flow.engine(), x.contiguous(), ctx, g_lp, emit, defer=defer, fused=fused)
         n += 1
-    return n
+    # fp32 rows: a vector context (above the tiny kernel's rows) and a general (gated / layer-norm) conditioner
+    import vctx_cases
+    x, _zin, ctx = vctx_cases.inputs("d33_k2")
+    flow = vctx_cases.build("d33_k2")
+    g_lp = torch.randn(x.shape[0], generator=torch.Generator().manual_seed(1))
+    trace_one(f"f32 vector ctx: d33_k2 B={x.shape[0]}", flow, flow.engine(), x.contiguous(), ctx, g_lp, emit, vctx=True)
+    spec, sd, a = load_case("synth_d16_k3_convnet_gated_ln")
+    flow = build_flow(spec, sd)
+    g_lp = torch.randn(a["x"].shape[0], generator=torch.Generator().manual_seed(1))
+    trace_one(f"f32 general conditioner: synth_d16_k3_convnet_gated_ln B={a['x'].shape[0]}", flow, flow.engine(), a["x"].contiguous(),
+              None, g_lp, emit)
+    return n + 2
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("mode", choices=["plans", "trace"])
+    ap.add_argument("--only", nargs="+", default=None, help="plans: the case names to dump (default: all)")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                     help="the checkout whose usflows_amd / tests are used (default: this file's)")
     args = ap.parse_args()
@@ -445,7 +538,7 @@ def main():
         sha.update(text.encode())
         sys.stdout.write(text)
 
-    n = dump_plans(emit) if args.mode == "plans" else dump_trace(emit)
+    n = dump_plans(emit, args.only) if args.mode == "plans" else dump_trace(emit)
     print(f"{args.mode}: {n} records, sha1 {sha.hexdigest()}", file=sys.stderr)
 
 

@@ -9,7 +9,7 @@ from typing import List
 import torch
 
 from . import _ext
-from ._plan_util import EngineUnsupported, _image_triple, _refreshed, _round_up, arange_padded
+from ._plan_util import EngineUnsupported, _image_triple, _refreshed, _round_up, affine_span, arange_padded, folded_bias
 from .networks import ConditionalDenseNN, ConvNet, DenseNN
 
 
@@ -328,12 +328,10 @@ class _PlanesPlan:
     def affine(self, k: int, prim: str, i: int) -> int:
         """an affine block (with the flow's last ScaleTransform in its epilogue): ONE GEMM, planes -> planes, or -> the fp32
         result when it is the last layer; returns how many primitives it took"""
-        e, pk, nkb, n = self.eng, self.pk, self.nkb, len(self.prims)
-        nxt = self.prims[k + 1] if k + 1 < n else None
+        e, pk, nkb = self.eng, self.pk, self.nkb
         blk = e._step(i).module
         a = e._affine_entry(pk, blk)
-        fuse_post = prim == "affine_fwd" and nxt is not None and nxt[0] == "scale_mul"
-        is_last = (k == n - 1) or (fuse_post and k == n - 2)
+        fuse_post, is_last, taken = affine_span(self.prims, k)      # (_planes_ok admits a scale_mul at the very end only)
         is_head = len(self.ops) == 1                    # the first layer behind the pack op: the head's prologue belongs to it
         lay, out_sel = ("natp", e.natp_idx) if is_last else ("segp", e.segp_idx)
         if self.train:
@@ -347,16 +345,10 @@ class _PlanesPlan:
         if prim == "affine_fwd":
             kw["bias"] = e._planes_vec(pk, ("pl_b", id(blk), lay), a["b"], out_sel).data_ptr()
         elif not (is_head and self.bias_in_head):       # (x / s - b) @ Minv^T: bias already subtracted by the head
-            # (y - b) @ Minv^T == y @ Minv^T + c, c = -(Minv b) formed in fp64 at pack time ("bias folding")
-            if "c" not in a:
-                a["c"] = torch.empty(a["b"].shape, dtype=torch.float64, device=a["b"].device)
-                # (launched now, in front of the queued image jobs: it reads the prepared M^-1 and b only, and the job that
-                # packs c runs with the batch behind the layout loop -- no flush: the images of ALL layers stay one batch)
-                _ext.matvec_f64(a["Minv"], a["b"].contiguous(), alpha=-1.0, out64=a["c"])
-            kw["bias"] = e._planes_vec(pk, ("pl_c", id(blk), lay), a["c"], out_sel).data_ptr()
+            kw["bias"] = e._planes_vec(pk, ("pl_c", id(blk), lay), folded_bias(a), out_sel).data_ptr()
         if is_last:
             if fuse_post:
-                s2 = e._step(nxt[1]).module
+                s2 = e._step(self.prims[k + 1][1]).module
                 kw["post_mul"] = e._planes_vec(pk, ("pl_scale", id(s2), "natp"), pk["scale"][id(s2)], e.natp_idx, 1.0).data_ptr()
             self._final_store(kw)
         else:
@@ -369,7 +361,7 @@ class _PlanesPlan:
         if self.train:
             self.meta[-1]["out_buf"] = self.out_buf[0] if is_last else self.z_name
         self.ops.append(self.gemm_op(W, **kw))
-        return 2 if (is_last and fuse_post) else 1
+        return taken
 
     def _final_store(self, kw: dict) -> None:
         """where the last GEMM's fp32 result goes (``final``): sets its descriptor fields in kw and ``out_buf``"""
@@ -389,9 +381,7 @@ class _PlanesPlan:
                       base_part=ws["bpart"].data_ptr(), base=int(final[4:]))
             self.out_buf = ("bpart", "part", 8)
         else:
-            if "nat2" not in ws:
-                ws["nat2"] = torch.zeros(B, e.LDn, dtype=torch.float32, device=self.device)
-            kw.update(C_f32=ws["nat2"].data_ptr(), ldc=e.LDn, N=e.D)
+            kw.update(C_f32=e._nat2(ws, B, self.device).data_ptr(), ldc=e.LDn, N=e.D)
             self.out_buf = ("nat2", "nat", e.LDn)
 
     def coupling(self, prim: str, i: int) -> int:

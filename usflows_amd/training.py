@@ -2,7 +2,7 @@
 forward is the engine's launch list and whose backward is hand-derived -- what ``Flow.fit`` (flows.py:196-199:
 ``loss = -log_prob(batch).mean() - log_prior()``) asks autograd to differentiate.
 
-forward   the log_prob launch list (engine.py) with every affine output kept in a buffer of its own (the saved
+forward   the log_prob launch list (engine_flat.py) with every affine output kept in a buffer of its own (the saved
           activations; couplings update their transformed half in place, and their conditioning half -- all the
           backward needs of them -- is untouched), then the base-density tail.
 backward  usf_base_logprob_grad_f32 -> per layer, last to first:
@@ -241,26 +241,6 @@ class TrainPath:
             t = torch.zeros(rows, cols, dtype=dtype, device=ws["zA"].device)
             ws[name] = t
         return t
-
-    def _mat_t(self, pk, blk, which, out_layout, in_layout):
-        """transposed image [n_in, n_out] of the affine weight (+ planes): the data-gradient operand"""
-        eng = self.eng
-        key = (id(blk), which, out_layout, in_layout, "T")
-        if key not in pk["mats"]:
-            src = pk["affine"][id(blk)][which]
-            dev = src.device
-            oi, ii = eng._idx_dev(out_layout, dev), eng._idx_dev(in_layout, dev)
-            n_out, n_in = int(oi.numel()), int(ii.numel())
-            Wt = torch.empty(n_in, n_out, dtype=torch.float32, device=dev)
-            planes = None
-            if eng._wants_planes(n_in, n_out):
-                planes = torch.empty(3, n_in, _round_up(n_out, 32), dtype=torch.bfloat16, device=dev)
-            with eng._pk_record(pk):
-                _ext.pack_weight(src, ii, n_in, oi, n_out, W=Wt, ldw=n_out, planes=planes, transpose=True)
-            pk["mats"][key] = Wt
-            if planes is not None:
-                pk["mats"][("planes", Wt.data_ptr())] = planes
-        return pk["mats"][key]
 
     def _linear(self, pk, A, a_off, lda, W, Cbuf, c_off, ldc, M, N, K, **kw):
         """one usf_linear_f32 launch (bf16x3 planes attached when the engine's mode wants them)"""
@@ -766,7 +746,7 @@ class TrainPath:
                         self._transposed(pk, un["W_out"])
                     elif m is not first_meta or getattr(self, "_want_dx", False):
                         which = "Minv" if m["prim"] == "affine_bwd" else "M"
-                        self._mat_t(pk, m["blk"], which, m["out_layout"], m["in_layout"])
+                        eng._mat(pk, m["blk"], which, m["out_layout"], m["in_layout"], transpose=True)
 
     def _fused_cbwd(self, m, B) -> bool:
         """the data-gradient chain of this coupling layer's conditioner as ONE launch of the fused kernel (engine.
@@ -831,7 +811,7 @@ class TrainPath:
             gpl = ws.get("gpl")
             if gpl is None or gpl.shape[1] != -(-B // 32) * 32 or gpl.shape[2] < -(-n_out // 32) * 32:
                 gpl = ws["gpl"] = _ext.row_planes(B, max(n_out, eng.LD, eng.LDn), dev)
-            Wt = self._mat_t(pk, blk, which, m["out_layout"], m["in_layout"])
+            Wt = eng._mat(pk, blk, which, m["out_layout"], m["in_layout"], transpose=True)
             self._linear(pk, g_cur, 0, g_ld, Wt, g_other, 0, n_in, B, n_in, n_out, planes_out=gpl)
             gs = self._buf(ws, f"gs{m['op']}", 1, wid)
             cs_fused = (config.fused_bias                                                  # the bias gradient from the same pass
@@ -854,7 +834,7 @@ class TrainPath:
         if from_planes:
             return g_other, g_cur, n_in
         if need_dgrad:
-            Wt = self._mat_t(pk, blk, which, m["out_layout"], m["in_layout"])
+            Wt = eng._mat(pk, blk, which, m["out_layout"], m["in_layout"], transpose=True)
             if self._defer:                       # g_cur waits for this layer's queued gradient jobs: never written again
                 dst = self._buf(ws, f"gD{m['op']}", B, wid)
                 self._linear(pk, g_cur, 0, g_ld, Wt, dst, 0, n_in, B, n_in, n_out)
@@ -893,7 +873,7 @@ class TrainPath:
 
     def _coupling_backward_general(self, plan, m, g_cur, g_ld, grads):
         """backward of a coupling layer whose conditioner is the vector ConvNet with GatedMLP / LayerNormVector blocks
-        (reference networks.py:206-245, 287-308; forward: engine._general_coupling_ops).  The conditioner runs once more from the
+        (reference networks.py:206-245, 287-308; forward: engine_flat._FlatPlan._coupling_general).  The conditioner runs once more from the
         layer's saved input with every intermediate kept (x_j, f(x_j), the hidden activations, [val, gate], the projected skip),
         then block by block backwards: usf_gated_norm_rows_bwd_f32 (layer norm + gate), usf_wgrad_f32 / usf_colsum_f32 for the
         parameters, usf_linear_f32 on the transposed images for the data gradients (the (Leaky)ReLU derivative in its epilogue:
@@ -1069,12 +1049,13 @@ class TrainPath:
         nl = len(un["layers"])
         act, slope = cp["act"], cp["slope"]
         # 1. hidden activations again (the conditioning half of the saved buffer is what the forward saw)
-        saved_fused = bool(m.get("hidden_saved_fused"))       # large batches: the fused forward kernel left them (engine.py)
+        saved_fused = bool(m.get("hidden_saved_fused"))       # large batches: the fused forward kernel left them (engine_flat.py)
         saved = saved_fused or bool(m.get("hidden_saved"))    # ... or the unfused forward's GEMMs wrote them into the layer's own buffers
         own = f"_{m['step']}" if (self._defer or saved) else ""         # deferred gradient jobs read these after the layer loop
-        hbufs = [self._buf(ws, f"Hs{j}{own}", B, hmax) for j in range(nl)]
+        # (the layer's own buffers are the forward plan's -- engine_flat.py, `_hidden_bufs`; without them a shared set, recomputed)
+        hbufs = eng._hidden_bufs(ws, m["step"], nl, B, zbuf.device) if own else [self._buf(ws, f"Hs{j}", B, hmax) for j in range(nl)]
         src, src_off, src_ld, src_K = zbuf, cp["pass_off"], LD, cp["pass_n"]
-        # (small batches: the forward plan left the hidden activations in exactly these buffers -- engine.py, `hidden_saved`)
+        # (small batches: the forward plan left the hidden activations in exactly these buffers -- engine_flat.py, `hidden_saved`)
         recompute = not saved
         for j, (W, b) in enumerate(un["layers"] if recompute else []):
             kw = {}
