@@ -210,15 +210,28 @@ int usf_radial_sample_f32(float* z, int64_t ldz, int64_t M, int64_t D, int32_t b
  * with the norm distribution a K-component mixture (1 <= K <= 64; K == 1: no mixture, logits may be NULL) of
  *     USF_NORM_LOGNORMAL: f_k = torch LogNormal(par_a[k], softplus(par_b[k]))        (distributions.py:181-197, 822-834)
  *     USF_NORM_GAMMA:     f_k = torch Gamma(softplus(par_a[k]), softplus(par_b[k]))  (distributions.py:162-179, 674-707)
+ *     USF_NORM_WEIBULL:   f_k = torch Weibull(scale = softplus(par_a[k]), concentration = softplus(par_b[k]))  (:835-850)
+ *     USF_NORM_HALFNORMAL: f_k = torch HalfNormal(softplus(par_a[k]))                 (one parameter: par_b is ignored, may be NULL)
+ *     USF_NORM_CHI:       f_k = Chi(df = par_a[k], scale = par_b[k])                  (:55-115; only with USF_NORM_RAW_PARAMS --
+ *                         the reference's Chi is a plain distribution whose scale is a constant)
+ * (torch Exponential(rate) is Gamma(1, rate) and torch Chi2(df) is Gamma(df / 2, 1/2): the caller passes them as
+ * USF_NORM_GAMMA.)  With x = log r - log lambda the new kinds are
+ *     Weibull:    log f = log k - log lambda + (k - 1) x - e^{k x}
+ *     HalfNormal: log f = log 2 - log sigma - log sqrt(2 pi) - r^2 / (2 sigma^2)
+ *     Chi:        log f = (1 - nu/2) log 2 - lgamma(nu/2) + (nu - 1) x - e^{2x} / 2 - log s          (lambda = s)
  * pi = softmax(logits) (MixtureSameFamily).  par_* are the modules' STORED parameters (positive ones through softplus, as
  * DistributionModule._get_distribution_params applies it); OR-ing USF_NORM_RAW_PARAMS into `norm` takes them as they are
  * (a plain torch distribution).  logdv_const = the r-independent part of log_delta_volume(p, r) (distributions.py:513-549),
- * computed by the caller in fp64.  The O(K) finishing math runs in fp64 inside the kernel.  r_out (optional, [M]) receives the
+ * computed by the caller in fp64.  The O(K) finishing math runs in fp64 inside the kernel.  A row at which every component's
+ * log-density is -inf (a Weibull far in its tail) gets -inf, as torch.logsumexp gives it.  r_out (optional, [M]) receives the
  * radii for the backward pass; sum_out as usf_base_logprob_f32.
  * z == NULL: the radii are GIVEN -- the forward reads r_out as its input (the finishing formula alone).
  */
 #define USF_NORM_LOGNORMAL 0
 #define USF_NORM_GAMMA 1
+#define USF_NORM_WEIBULL 2
+#define USF_NORM_HALFNORMAL 3
+#define USF_NORM_CHI 4
 #define USF_NORM_RAW_PARAMS 0x100
 int usf_radial_logprob_f32(const float* z, int64_t ldz, int64_t M, int64_t D, int32_t p_id, const float* loc, int32_t norm,
                            int32_t K, const float* par_a, const float* par_b, const float* logits, double logdv_const,

@@ -10,6 +10,7 @@ USF_MAX_HIDDEN = 4
 ACT_NONE, ACT_LEAKY_RELU, ACT_GATE = 0, 1, 2
 BASE_LAPLACE, BASE_NORMAL, BASE_LPNORM1, BASE_LPNORM2, BASE_LPNORMINF, BASE_ROWSUM = 0, 1, 2, 3, 4, 5
 NORM_LOGNORMAL, NORM_GAMMA, NORM_RAW_PARAMS = 0, 1, 0x100
+NORM_WEIBULL, NORM_HALFNORMAL, NORM_CHI = 2, 3, 4
 RADIAL_MAX_K = 64
 OP_LINEAR, OP_COUPLING, OP_PACK_PLANES, OP_GEMM_PLANES, OP_COUPLING_PLANES, OP_GATED_NORM, OP_CALL = 1, 2, 5, 6, 7, 9, 10
 PLANES_BF16X3, PLANES_F16X2 = 0, 1

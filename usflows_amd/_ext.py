@@ -20,7 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 from .config import config  # noqa: E402
 from ._abi import (  # noqa: E402,F401  -- the declarations, re-exported: callers say _ext.LinearDesc, _ext.ACT_GATE, ...
     USF_ABI_VERSION, USF_INTERNAL_VERSION, USF_MAX_HIDDEN, ACT_NONE, ACT_LEAKY_RELU, ACT_GATE, BASE_LAPLACE, BASE_NORMAL,
-    BASE_LPNORM1, BASE_LPNORM2, BASE_LPNORMINF, BASE_ROWSUM, NORM_LOGNORMAL, NORM_GAMMA, NORM_RAW_PARAMS, RADIAL_MAX_K, OP_LINEAR,
+    BASE_LPNORM1, BASE_LPNORM2, BASE_LPNORMINF, BASE_ROWSUM, NORM_LOGNORMAL, NORM_GAMMA, NORM_RAW_PARAMS, NORM_WEIBULL, NORM_HALFNORMAL, NORM_CHI, RADIAL_MAX_K, OP_LINEAR,
     OP_COUPLING, OP_PACK_PLANES, OP_GEMM_PLANES, OP_COUPLING_PLANES, OP_GATED_NORM, OP_CALL, PLANES_BF16X3, PLANES_F16X2, CALL_FNS,
     FN_COUPLING_PLANES_CTX, FN_COUPLING_VCTX, VCTX_MAX,
     _fp, LinearDesc, CouplingDesc, PackPlanesDesc, GemmPlanesDesc, CouplingPlanesDesc, MtChunk, AdamChunk, GradChunk, GatedNormDesc, GatedNormBwdDesc,
@@ -331,7 +331,7 @@ def radial_logprob(z, ldz, M, D, p_id, loc, norm, K, par_a, par_b, logits, logdv
     """usf_radial_logprob_f32: RadialDistribution.log_prob of the rows of z in one launch (include/usflows_hip.h); z None:
     the radii are given in r_out"""
     _launch("usf_radial_logprob_f32", (ptr(z), ldz, M, D, int(p_id), ptr(loc), int(norm), int(K), par_a.data_ptr(),
-                                       par_b.data_ptr(), ptr(logits), float(logdv_const), float(logdet_const), ptr(logdet_dev),
+                                       ptr(par_b), ptr(logits), float(logdv_const), float(logdet_const), ptr(logdet_dev),
                                        out.data_ptr(), ptr(r_out), ptr(sum_out), current_stream(out.device)),
             keep=(z, loc, par_a, par_b, logits, logdet_dev, out, r_out, sum_out))
 
@@ -343,7 +343,7 @@ def radial_logprob_grad(z, ldz, r, g_lp, M, D, p_id, loc, norm, K, par_a, par_b,
     ws_n = max(8, lib.usf_radial_logprob_grad_workspace(max(M, 1), D))
     ws = torch.empty((ws_n + 7) // 8, dtype=torch.float64, device=r.device)
     _launch("usf_radial_logprob_grad_f32", (ptr(z), ldz, r.data_ptr(), g_lp.data_ptr(), M, D, int(p_id), ptr(loc),
-                                            int(norm), int(K), par_a.data_ptr(), par_b.data_ptr(), ptr(logits), g.data_ptr(), ldg,
+                                            int(norm), int(K), par_a.data_ptr(), ptr(par_b), ptr(logits), g.data_ptr(), ldg,
                                             ptr(d_loc), ptr(d_a), ptr(d_b), ptr(d_logits), ws.data_ptr(), ws.numel() * 8,
                                             current_stream(r.device)),
             keep=(z, r, g_lp, loc, par_a, par_b, logits, g, d_loc, d_a, d_b, d_logits, ws))

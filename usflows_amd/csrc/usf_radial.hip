@@ -3,7 +3,9 @@
 //       logp = norm_distribution.log_prob(r) - log_delta_volume(p, r)                       (:513-549)
 //   norm_distribution = LogNormal (:181-197, experiments/mnist/mnist.yaml:79-92, cifar/cifar.yaml) or GammaMM (:674-707,
 //       experiments/fashion/fashionclasses_veriflow.yaml:79-93) -- generally a K-component mixture (K <= 64) of
-//       torch LogNormal / Gamma components whose positive parameters are stored through softplus (:117-197, 730-795).
+//       torch LogNormal / Gamma components whose positive parameters are stored through softplus (:117-197, 730-795);
+//       the norm-distribution study's radii (experiments/mnist/mnist_digits_minimal_radial_*.yaml, WeibullMM :835-850, Chi
+//       :55-115) are three more component kinds: Weibull, HalfNormal and Chi (Exponential and Chi2 are Gammas).
 // HBM-bound: one wave per row reduces the radius with 16-byte lane loads (4 D bytes per sample), then lanes 0..K-1 of the
 // same wave evaluate one mixture component each and a wave log-sum-exp finishes the row -- O(K) work per sample in fp64,
 // no second launch, no host round trip (the torch formulation builds a validating distribution object per call, which
@@ -46,11 +48,17 @@ __device__ __forceinline__ double digamma_d(double x) {
 
 // per-component constants, one set per block in LDS:  lp_k(r) = c + ... (see comp_logp)
 struct RadTab {
-  double a[RAD_MAXK];      // LogNormal: mu            Gamma: concentration
-  double b[RAD_MAXK];      // LogNormal: sigma         Gamma: rate
+  double a[RAD_MAXK];      // LogNormal: mu            Gamma: concentration      Weibull: scale      HalfNormal: sigma      Chi: df
+  double b[RAD_MAXK];      // LogNormal: sigma         Gamma: rate               Weibull: concentration                     Chi: scale
   double c[RAD_MAXK];      // LogNormal: -log sigma - log sqrt(2 pi) + log pi_k      Gamma: a log b - lgamma(a) + log pi_k
+                           // Weibull: log k - log lambda + log pi_k                 HalfNormal: log 2 - log sigma - log sqrt(2 pi) + log pi_k
+                           // Chi: (1 - nu/2) log 2 - lgamma(nu/2) - log s + log pi_k
+  double ll[RAD_MAXK];     // Weibull: log scale       Chi: log scale       (x = log r - ll)
   double pi[RAD_MAXK];     // mixture weight softmax(logits)_k (1 when there are no logits)
 };
+
+constexpr double RAD_LOG2 = 0.69314718055994530942;
+constexpr double RAD_HALF_LOG_2PI = 0.91893853320467274178;
 
 // called by the first wave of a block (all 64 lanes); others wait at the barrier that follows
 __device__ __forceinline__ void build_tab(RadTab& t, int norm, int K, const float* __restrict__ par_a,
@@ -66,30 +74,59 @@ __device__ __forceinline__ void build_tab(RadTab& t, int norm, int K, const floa
     lw = l - mx - log(s);
   }
   if (on) {
-    const double pa = (double)par_a[lane], pb = (double)par_b[lane];
-    double a, b, c;
+    const double pa = (double)par_a[lane], pb = par_b ? (double)par_b[lane] : 1.0;      // (one-parameter kinds: no par_b)
+    double a, b, c, ll = 0.0;
     if (kind == USF_NORM_LOGNORMAL) {
       a = pa;
       b = raw ? pb : softplus_d(pb);
       c = -log(b) - 0.91893853320467274178 + lw;
-    } else {
+    } else if (kind == USF_NORM_GAMMA) {
       a = raw ? pa : softplus_d(pa);
       b = raw ? pb : softplus_d(pb);
       c = a * log(b) - lgamma(a) + lw;
+    } else if (kind == USF_NORM_WEIBULL) {
+      a = raw ? pa : softplus_d(pa);
+      b = raw ? pb : softplus_d(pb);
+      ll = log(a);
+      c = log(b) - ll + lw;
+    } else if (kind == USF_NORM_HALFNORMAL) {
+      a = raw ? pa : softplus_d(pa);
+      b = 1.0;
+      c = RAD_LOG2 - log(a) - RAD_HALF_LOG_2PI + lw;
+    } else {                                    // USF_NORM_CHI: df and the constant scale, always as they are
+      a = pa;
+      b = pb;
+      ll = log(b);
+      c = (1.0 - 0.5 * a) * RAD_LOG2 - lgamma(0.5 * a) - ll + lw;
     }
-    t.a[lane] = a; t.b[lane] = b; t.c[lane] = c; t.pi[lane] = exp(lw);
+    t.a[lane] = a; t.b[lane] = b; t.c[lane] = c; t.ll[lane] = ll; t.pi[lane] = exp(lw);
   }
 }
 
 // log of (mixture weight x component density) at radius r (lr = log r):
 //   torch LogNormal.log_prob(r) = Normal(mu, sigma).log_prob(log r) - log r      (TransformedDistribution + ExpTransform)
 //   torch Gamma.log_prob(r)     = xlogy(a, b) + xlogy(a - 1, r) - b r - lgamma(a)
+//   torch Weibull.log_prob(r)   = log k - log lambda + (k - 1) x - e^{k x},  x = log r - log lambda   (Exponential(1) under
+//                                 PowerTransform(1/k) and AffineTransform(0, lambda))
+//   torch HalfNormal.log_prob(r) = log 2 + Normal(0, sigma).log_prob(r)
+//   Chi(nu, s).log_prob(r)      = Chi2(nu).log_prob((r/s)^2) + log(2 r/s) - log s        (distributions.py:85-94)
+//                               = (1 - nu/2) log 2 - lgamma(nu/2) + (nu - 1) x - e^{2x}/2 - log s,  x = log r - log s
 __device__ __forceinline__ double comp_logp(const RadTab& t, int kind, int k, double r, double lr) {
   if (kind == USF_NORM_LOGNORMAL) {
     const double d = lr - t.a[k];
     return t.c[k] - d * d / (2.0 * t.b[k] * t.b[k]) - lr;
   }
-  return t.c[k] + (t.a[k] - 1.0) * lr - t.b[k] * r;
+  if (kind == USF_NORM_GAMMA) return t.c[k] + (t.a[k] - 1.0) * lr - t.b[k] * r;
+  if (kind == USF_NORM_WEIBULL) {
+    const double x = lr - t.ll[k];
+    return t.c[k] + (t.b[k] - 1.0) * x - exp(t.b[k] * x);
+  }
+  if (kind == USF_NORM_HALFNORMAL) {
+    const double q = r / t.a[k];
+    return t.c[k] - 0.5 * q * q;
+  }
+  const double x = lr - t.ll[k];
+  return t.c[k] + (t.a[k] - 1.0) * x - 0.5 * exp(2.0 * x);
 }
 
 template <int P_ID>
@@ -140,8 +177,10 @@ __global__ __launch_bounds__(64 * RAD_WPB) void radial_logprob_kernel(
       lp = comp_logp(tab, kind, 0, r, lr);
     } else {
       const double v = lane < K ? comp_logp(tab, kind, lane, r, lr) : -INFINITY;
+      // (every component at -inf -- a Weibull far in its tail: the row is -inf as torch.logsumexp gives it, not inf - inf)
       const double mx = wave_max_d(v);
-      lp = mx + log(wave_sum_d(lane < K ? exp(v - mx) : 0.0));
+      if (mx == -INFINITY) lp = -INFINITY;
+      else lp = mx + log(wave_sum_d(lane < K ? exp(v - mx) : 0.0));
     }
     const float out = (float)(lp - (logdv_const + (double)(D - 1) * lr) + logdet);
     if (lane == 0) {
@@ -170,8 +209,12 @@ static bool radial_args_ok(const char* what, int64_t M, int64_t D, int64_t ldz, 
     return false;
   }
   const int kind = norm & 0xff;
-  if ((kind != USF_NORM_LOGNORMAL && kind != USF_NORM_GAMMA) || (norm & ~(0xff | USF_NORM_RAW_PARAMS))) {
+  if (kind < USF_NORM_LOGNORMAL || kind > USF_NORM_CHI || (norm & ~(0xff | USF_NORM_RAW_PARAMS))) {
     set_error("%s: unknown norm-distribution id %d", what, norm);
+    return false;
+  }
+  if (kind == USF_NORM_CHI && !(norm & USF_NORM_RAW_PARAMS)) {
+    set_error("%s: USF_NORM_CHI takes df and scale as they are (USF_NORM_RAW_PARAMS)", what);
     return false;
   }
   if (K < 1 || K > RAD_MAXK) { set_error("%s: K = %d components (1..%d served)", what, K, RAD_MAXK); return false; }
@@ -183,7 +226,10 @@ int radial_logprob(const float* z, int64_t ldz, int64_t M, int64_t D, int32_t p_
                    const double* logdet_dev, float* logp, float* r_out, double* sum_out, hipStream_t stream) {
   if (!radial_args_ok("usf_radial_logprob_f32", M, D, ldz, p_id, norm, K, z != nullptr)) return -2;
   if (M == 0) return 0;
-  if ((z && !loc) || (!z && !r_out) || !par_a || !par_b || !logp || (K > 1 && !logits)) { set_error("usf_radial_logprob_f32: null pointer"); return -1; }
+  if ((z && !loc) || (!z && !r_out) || !par_a || (!par_b && (norm & 0xff) != USF_NORM_HALFNORMAL) || !logp || (K > 1 && !logits)) {
+    set_error("usf_radial_logprob_f32: null pointer");
+    return -1;
+  }
   int64_t blocks = (M + RAD_WPB - 1) / RAD_WPB;
   if (blocks > 256 * 8) blocks = 256 * 8;
   dim3 g((unsigned)blocks), b(64 * RAD_WPB);
@@ -222,6 +268,7 @@ __global__ __launch_bounds__(64 * RAD_WPB) void radial_grad_kernel(
   if (wib == 0) {
     build_tab(tab, norm, K, par_a, par_b, logits, lane);
     if (lane < K && kind == USF_NORM_GAMMA) dig[lane] = digamma_d(tab.a[lane]);
+    if (lane < K && kind == USF_NORM_CHI) dig[lane] = digamma_d(0.5 * tab.a[lane]);
   }
   __syncthreads();
   const bool vec = ((ldz & 3) == 0) && ((ldg & 3) == 0) && ((reinterpret_cast<uintptr_t>(z) & 15u) == 0) &&
@@ -236,8 +283,9 @@ __global__ __launch_bounds__(64 * RAD_WPB) void radial_grad_kernel(
     if (K > 1) {
       const double v = on ? comp_logp(tab, kind, lane, r, lr) : -INFINITY;
       const double mx = wave_max_d(v);
-      const double e = on ? exp(v - mx) : 0.0;
-      w = e / wave_sum_d(e);
+      const double e = (on && mx != -INFINITY) ? exp(v - mx) : 0.0;
+      const double es = wave_sum_d(e);
+      w = es > 0.0 ? e / es : 0.0;             // (every component at -inf: no posterior; the forward's row is -inf)
     }
     double dr_k = 0.0;
     if (on) {
@@ -246,11 +294,25 @@ __global__ __launch_bounds__(64 * RAD_WPB) void radial_grad_kernel(
         dr_k = w * (-d * is2 - 1.0) / r;
         acc_a += gm * w * d * is2;                               // d/dmu
         acc_b += gm * w * (d * d * is2 / s - 1.0 / s);           // d/dsigma
-      } else {
+      } else if (kind == USF_NORM_GAMMA) {
         const double a = tab.a[lane], b = tab.b[lane];
         dr_k = w * ((a - 1.0) / r - b);
         acc_a += gm * w * (log(b) + lr - dig[lane]);             // d/dconcentration
         acc_b += gm * w * (a / b - r);                           // d/drate
+      } else if (kind == USF_NORM_WEIBULL) {
+        const double l = tab.a[lane], k = tab.b[lane], x = lr - tab.ll[lane], e = exp(k * x);
+        dr_k = w * ((k - 1.0) - k * e) / r;
+        acc_a += gm * w * (k / l) * (e - 1.0);                   // d/dscale
+        acc_b += gm * w * (1.0 / k + x - x * e);                 // d/dconcentration
+      } else if (kind == USF_NORM_HALFNORMAL) {
+        const double s = tab.a[lane], is2 = 1.0 / (s * s);
+        dr_k = w * (-r * is2);
+        acc_a += gm * w * (r * r * is2 / s - 1.0 / s);           // d/dsigma
+      } else {
+        const double nu = tab.a[lane], x = lr - tab.ll[lane], e = exp(2.0 * x);
+        dr_k = w * ((nu - 1.0) - e) / r;
+        acc_a += gm * w * (x - 0.5 * RAD_LOG2 - 0.5 * dig[lane]);        // d/ddf
+        acc_b += gm * w * (e - nu) / tab.b[lane];                // d/dscale
       }
       acc_l += gm * (w - tab.pi[lane]);
     }
@@ -325,10 +387,10 @@ __global__ __launch_bounds__(64) void radial_grad_finish_kernel(const double* __
   const bool raw = (norm & USF_NORM_RAW_PARAMS) != 0;
   const int kind = norm & 0xff;
   if (q == 0) {
-    if (!raw && kind == USF_NORM_GAMMA) t *= softplus_grad_d((double)par_a[k]);
+    if (!raw && kind != USF_NORM_LOGNORMAL) t *= softplus_grad_d((double)par_a[k]);
     if (d_a) d_a[k] = (float)t;
   } else if (q == 1) {
-    if (!raw) t *= softplus_grad_d((double)par_b[k]);
+    if (!raw && par_b) t *= softplus_grad_d((double)par_b[k]);     // (HalfNormal has no par_b: its sum is zero)
     if (d_b) d_b[k] = (float)t;
   } else if (d_logits) {
     d_logits[k] = (float)t;
@@ -362,7 +424,8 @@ int radial_grad(const float* z, int64_t ldz, const float* r, const float* g_lp, 
     if (d_logits) (void)hipMemsetAsync(d_logits, 0, (size_t)K * sizeof(float), stream);
     return check_launch("usf_radial_logprob_grad_f32(empty)");
   }
-  if ((z && !loc) || (!z && d_loc) || !r || !g_lp || !par_a || !par_b || !g || (K > 1 && !logits) || !workspace) {
+  if ((z && !loc) || (!z && d_loc) || !r || !g_lp || !par_a || (!par_b && (norm & 0xff) != USF_NORM_HALFNORMAL) || !g ||
+      (K > 1 && !logits) || !workspace) {
     set_error("usf_radial_logprob_grad_f32: null pointer");
     return -1;
   }

@@ -3,7 +3,8 @@
 ``Flow.__init__`` applies, the ``DistributionModule`` family (LogNormal / Laplace / Normal / Gamma)
 and the Lp-``RadialDistribution`` with its unit-ball sampler and UDL profile helpers, and the mixture families
 used as radial norm distributions / data generators by the live configs (``GammaMM``, ``MixtureModel`` with
-``GMM`` / ``LogNormalMM`` / ``WeibullMM``).  ``RotatedLaplace`` / ``Chi`` are out of scope.
+``GMM`` / ``LogNormalMM`` / ``WeibullMM``) and the ``Chi`` radius distribution of the norm-distribution
+study (experiments/mnist/mnist_digits_minimal_radial_chi.yaml).  ``RotatedLaplace`` is out of scope.
 
 On the device fast path the per-sample reduction over the feature axis (the only per-sample
 reduction on the whole path) runs in ``usf_base_logprob_f32``; the code here is the host-side
@@ -35,6 +36,45 @@ class Independent(nn.Module, torch.distributions.Independent):
         self._base_distribution = base_distribution
         torch.distributions.Independent.__init__(
             self, self._base_distribution, reinterpreted_batch_ndims=reinterpreted_batch_ndims, *args, **kwargs)
+
+
+class Chi(Distribution):
+    """Chi distribution with ``df`` degrees of freedom, scaled by the constant ``scale`` (distributions.py:55-115): the law of
+    ``scale * sqrt(Y)`` with ``Y ~ Chi2(df)``.  With x = log(r / scale):
+
+        log f(r) = (1 - df/2) log 2 - lgamma(df/2) + (df - 1) x - e^{2x} / 2 - log scale
+        F(r)     = P(df/2, (r / scale)^2 / 2)                      (the regularised lower incomplete gamma function)
+
+    ``entropy`` returns what the reference returns, ``Chi2(df).entropy() / 2 + log 2 + log scale``."""
+
+    arg_constraints = {"df": constraints.positive}
+    support = constraints.positive
+    has_enumerate_support = False
+
+    def __init__(self, df, scale: float = 1.0, validate_args=None):
+        self.chi2 = torch.distributions.Chi2(df)
+        self.df = df
+        self.scale = scale
+        super().__init__(self.chi2.batch_shape, self.chi2.event_shape, validate_args=validate_args)
+
+    def _log_scale(self):
+        return torch.log(torch.as_tensor(self.scale))
+
+    def sample(self, sample_shape=torch.Size()):
+        return self.scale * torch.sqrt(self.chi2.sample(sample_shape))
+
+    def log_prob(self, value):
+        half = 0.5 * self.chi2.df
+        x = torch.log(value) - self._log_scale()
+        return (1.0 - half) * math.log(2.0) - torch.lgamma(half) + (2.0 * half - 1.0) * x - 0.5 * torch.exp(2.0 * x) - self._log_scale()
+
+    def cdf(self, value):
+        return torch.special.gammainc(0.5 * self.chi2.df, 0.5 * (value / self.scale) ** 2)
+
+    def entropy(self):
+        half = 0.5 * self.chi2.df
+        h2 = half + math.log(2.0) + torch.lgamma(half) + (1.0 - half) * torch.digamma(half)         # Chi2(df).entropy()
+        return 0.5 * h2 + math.log(2.0) + self._log_scale()
 
 
 class DistributionModule(Module):

@@ -16,15 +16,21 @@ synchronisation, capturable, for flat AND image-shaped events.
 
 Served norm distributions (``norm_spec``): the ``LogNormal`` / ``Gamma`` modules with one-element parameters, ``GammaMM`` and
 ``MixtureModel`` over ``torch.distributions.LogNormal`` (``LogNormalMM``) with up to 64 components along one axis, and plain
-``torch.distributions.LogNormal`` / ``Gamma`` objects with one-element parameters on the device.  Anything else keeps the
-distribution object's op chain.
+``torch.distributions.LogNormal`` / ``Gamma`` objects with one-element parameters on the device; the radii of the reference's
+norm-distribution study (experiments/mnist/mnist_digits_minimal_radial_*.yaml): ``WeibullMM`` and ``MixtureModel`` over torch
+``Weibull`` / ``Exponential`` / ``HalfNormal`` / ``Chi2``, and plain ``Weibull`` / ``Exponential`` / ``HalfNormal`` / ``Chi2`` /
+``Chi`` objects with one-element parameters (``Exponential(rate)`` is ``Gamma(1, rate)``, ``Chi2(df)`` is ``Gamma(df / 2, 1/2)``:
+both run as the Gamma kind; the study's radii are served for a GPU device only, ``study_norm_spec`` is their mapping for
+any device).  Anything else keeps the distribution object's op chain.
 """
 from __future__ import annotations
 
 import math
+import weakref
 from typing import Optional
 
 import torch
+from torch.nn.functional import softplus
 
 from . import _ext
 from . import distributions as D_
@@ -50,9 +56,103 @@ def _dev_f32(t, device) -> bool:
     return torch.is_tensor(t) and t.dtype == torch.float32 and t.device == device and t.is_contiguous()
 
 
+_consts = {}         # (device, K, value) -> fp32 [K] tensor filled with value
+_host_copies = {}    # (data_ptr, _version, device) -> (weak reference to the host tensor, its fp32 device copy)
+
+
+def _const(device, K, value):
+    """a constant parameter of a component kind (the concentration 1 of an Exponential, the rate 1/2 of a Chi2)"""
+    key = (str(device), int(K), float(value))
+    t = _consts.get(key)
+    if t is None:
+        t = _consts[key] = torch.full((int(K),), float(value), dtype=torch.float32, device=device)
+    return t
+
+
+def _servable(t, device) -> bool:
+    """whether ``_served`` has a device form of this parameter of one of the study's norm distributions"""
+    if isinstance(t, (int, float)) and not isinstance(t, bool):
+        return True
+    if not torch.is_tensor(t) or t.numel() != 1:
+        return False
+    return _dev_f32(t, device) or (t.device.type == "cpu" and device.type != "cpu" and not t.requires_grad and t.is_floating_point())
+
+
+def _served(t, device):
+    """a one-element parameter as the kernels can read it: an fp32 device tensor as it is; a Python number as a cached
+    constant; a HOST-resident tensor without grad (the study files pass Python floats and host tensors, which torch keeps on
+    the host) through one cached fp32 device copy, keyed on (data_ptr, _version)"""
+    if not torch.is_tensor(t):
+        return _const(device, 1, float(t))
+    if _dev_f32(t, device):
+        return t
+    key = (t.data_ptr(), t._version, str(device))
+    hit = _host_copies.get(key)
+    if hit is not None and hit[0]() is t:
+        return hit[1]
+    if len(_host_copies) >= 256:
+        _host_copies.clear()
+    c = t.detach().to(device=device, dtype=torch.float32).contiguous()
+    _host_copies[key] = (weakref.ref(t), c)
+    return c
+
+
+def _positive(nd, name) -> bool:
+    """whether MixtureModel stores this parameter through softplus (distributions.py:762)"""
+    c = nd.param_constraints.get(name)
+    return isinstance(c, type(torch.distributions.constraints.positive)) and getattr(c, "lower_bound", None) == 0.0
+
+
+def _study_mixture_spec(nd, device):
+    """MixtureModel over torch Weibull / Exponential / HalfNormal / Chi2 components (WeibullMM included)"""
+    cls, names = nd.component_distribution_class, list(nd.param_names)
+    ps, l = list(nd.unconstrained_params), nd.mixture_logits
+    K = ps[0].numel()
+    if not (all(q.dim() == 1 and q.shape == l.shape for q in ps) and 1 <= K <= _ext.RADIAL_MAX_K
+            and all(_dev_f32(t, device) for t in ps + [l])):
+        return None
+    pos = [_positive(nd, n) for n in names]
+    raw = 0 if pos[0] else _ext.NORM_RAW_PARAMS
+    if cls is torch.distributions.Weibull and names == ["scale", "concentration"]:
+        if pos[0] != pos[1]:
+            return None
+        return _ext.NORM_WEIBULL | raw, K, ps[0], ps[1], l
+    if cls is torch.distributions.HalfNormal and names == ["scale"]:
+        return _ext.NORM_HALFNORMAL | raw, K, ps[0], None, l
+    # the two Gammas: the constrained parameter is formed here (one or two tensor ops, differentiable), the kernel takes it raw
+    if cls is torch.distributions.Exponential and names == ["rate"]:
+        return _ext.NORM_GAMMA | _ext.NORM_RAW_PARAMS, K, _const(device, K, 1.0), softplus(ps[0]) if pos[0] else ps[0], l
+    if cls is torch.distributions.Chi2 and names == ["df"]:
+        return _ext.NORM_GAMMA | _ext.NORM_RAW_PARAMS, K, 0.5 * (softplus(ps[0]) if pos[0] else ps[0]), _const(device, K, 0.5), l
+    return None
+
+
+def _study_plain_spec(nd, device):
+    """plain torch Weibull / Exponential / HalfNormal / Chi2 objects and the mirror's Chi, one-element parameters"""
+    if type(nd) is D_.Chi:
+        kind, a, b = _ext.NORM_CHI, nd.df, nd.scale
+    elif len(nd.batch_shape) > 1:
+        return None
+    elif type(nd) is torch.distributions.Weibull:
+        kind, a, b = _ext.NORM_WEIBULL, nd.scale, nd.concentration
+    elif type(nd) is torch.distributions.HalfNormal:
+        kind, a, b = _ext.NORM_HALFNORMAL, nd.scale, None
+    elif type(nd) is torch.distributions.Exponential:
+        kind, a, b = _ext.NORM_GAMMA, 1.0, nd.rate
+    else:                                       # Chi2(df) IS torch's Gamma(df / 2, 1/2): concentration carries the link to df
+        kind, a, b = _ext.NORM_GAMMA, nd.concentration, nd.rate
+    if not _servable(a, device) or not (b is None or _servable(b, device)):
+        return None
+    return kind | _ext.NORM_RAW_PARAMS, 1, _served(a, device), None if b is None else _served(b, device), None
+
+
+_STUDY_COMPONENTS = (torch.distributions.Weibull, torch.distributions.Exponential, torch.distributions.HalfNormal,
+                     torch.distributions.Chi2)
+
+
 def norm_spec(nd, device):
-    """(norm id, K, par_a, par_b, logits | None) -- the STORED tensors of the norm distribution, as the kernels read them --
-    or None when this norm distribution has no device form"""
+    """(norm id, K, par_a, par_b | None, logits | None) -- the STORED tensors of the norm distribution, as the kernels read
+    them -- or None when this norm distribution has no device form"""
     device = torch.device(device)
     if isinstance(nd, D_.LogNormal) and type(nd) is D_.LogNormal:
         a, b = nd.loc, nd.scale_unconstrained
@@ -92,6 +192,20 @@ def norm_spec(nd, device):
         if a.numel() == 1 and b.numel() == 1 and len(nd.batch_shape) <= 1 and _dev_f32(a, device) and _dev_f32(b, device):
             return _ext.NORM_GAMMA | _ext.NORM_RAW_PARAMS, 1, a, b, None
         return None
+    # the study's radii are served where the kernels run: asked about a host device (the CPU formulation, which has no
+    # kernel behind it) they have no device form
+    return study_norm_spec(nd, device) if device.type == "cuda" else None
+
+
+def study_norm_spec(nd, device):
+    """``norm_spec`` of the radius distributions of the norm-distribution study -- WeibullMM / MixtureModel over torch
+    Weibull, Exponential, HalfNormal, Chi2; those plain objects; Chi -- for tensors on ``device``, whatever its type (the
+    mapping itself needs no GPU); None for everything else"""
+    device = torch.device(device)
+    if isinstance(nd, D_.MixtureModel) and nd.component_distribution_class in _STUDY_COMPONENTS:
+        return _study_mixture_spec(nd, device)
+    if type(nd) in _STUDY_COMPONENTS or type(nd) is D_.Chi:
+        return _study_plain_spec(nd, device)
     return None
 
 
@@ -121,12 +235,12 @@ class RadialLogProb(torch.autograd.Function):
         locf = loc.detach().reshape(-1)
         out = torch.empty(B, dtype=torch.float32, device=z.device)
         r = torch.empty(B, dtype=torch.float32, device=z.device)
-        a, b = par_a.detach(), par_b.detach()
+        a, b = par_a.detach(), (None if par_b is None else par_b.detach())        # (a one-parameter kind has no par_b)
         lg = None if logits is None else logits.detach()
         if B > 0:
             _ext.radial_logprob(zf, d, B, d, p_id, locf, norm, K, a, b, lg, logdv, 0.0, out, r_out=r)
         ctx.save_for_backward(zf, r, locf, a, b, lg)
-        ctx.cfg = (p_id, norm, K, tuple(z.shape), tuple(loc.shape), tuple(par_a.shape), tuple(par_b.shape),
+        ctx.cfg = (p_id, norm, K, tuple(z.shape), tuple(loc.shape), tuple(par_a.shape), None if par_b is None else tuple(par_b.shape),
                    None if logits is None else tuple(logits.shape))
         return out
 
@@ -140,7 +254,7 @@ class RadialLogProb(torch.autograd.Function):
         g = torch.empty_like(zf)
         d_loc = torch.empty(d, dtype=torch.float32, device=dev) if need[1] else None
         d_a = torch.empty(K, dtype=torch.float32, device=dev) if need[2] else None
-        d_b = torch.empty(K, dtype=torch.float32, device=dev) if need[3] else None
+        d_b = torch.empty(K, dtype=torch.float32, device=dev) if (b is not None and need[3]) else None
         d_l = torch.empty(K, dtype=torch.float32, device=dev) if (lg is not None and need[4]) else None
         _ext.radial_logprob_grad(zf, d, r, g_lp.contiguous(), B, d, p_id, locf, norm, K, a, b, lg, g, d, d_loc=d_loc, d_a=d_a,
                                  d_b=d_b, d_logits=d_l)
@@ -160,12 +274,13 @@ class RadialFinish(torch.autograd.Function):
         B = r.shape[0]
         rc = r.detach().contiguous()
         out = torch.empty(B, dtype=torch.float32, device=r.device)
-        a, b = par_a.detach(), par_b.detach()
+        a, b = par_a.detach(), (None if par_b is None else par_b.detach())
         lg = None if logits is None else logits.detach()
         if B > 0:
             _ext.radial_logprob(None, 0, B, d, p_id, None, norm, K, a, b, lg, logdv, 0.0, out, r_out=rc)
         ctx.save_for_backward(rc, a, b, lg)
-        ctx.cfg = (p_id, norm, K, d, tuple(par_a.shape), tuple(par_b.shape), None if logits is None else tuple(logits.shape))
+        ctx.cfg = (p_id, norm, K, d, tuple(par_a.shape), None if par_b is None else tuple(par_b.shape),
+                   None if logits is None else tuple(logits.shape))
         return out
 
     @staticmethod
@@ -177,7 +292,7 @@ class RadialFinish(torch.autograd.Function):
         dev = rc.device
         g = torch.empty(B, dtype=torch.float32, device=dev)
         d_a = torch.empty(K, dtype=torch.float32, device=dev) if need[1] else None
-        d_b = torch.empty(K, dtype=torch.float32, device=dev) if need[2] else None
+        d_b = torch.empty(K, dtype=torch.float32, device=dev) if (b is not None and need[2]) else None
         d_l = torch.empty(K, dtype=torch.float32, device=dev) if (lg is not None and need[3]) else None
         _ext.radial_logprob_grad(None, 0, rc, g_lp.contiguous(), B, d, p_id, None, norm, K, a, b, lg, g, 0, d_a=d_a, d_b=d_b,
                                  d_logits=d_l)
@@ -219,7 +334,8 @@ def log_prob(base, z: torch.Tensor, logdet_dev: Optional[torch.Tensor] = None, s
         zf = z
     lg = sp["logits"]
     _ext.radial_logprob(zf, ldz, B, d, sp["p_id"], sp["loc"].detach().reshape(-1), sp["norm"], sp["K"], sp["a"].detach(),
-                        sp["b"].detach(), None if lg is None else lg.detach(), sp["logdv"], 0.0, out, sum_out=sum_out,
+                        None if sp["b"] is None else sp["b"].detach(), None if lg is None else lg.detach(), sp["logdv"], 0.0, out,
+                        sum_out=sum_out,
                         logdet_dev=logdet_dev)
     return out
 
