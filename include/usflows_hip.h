@@ -116,6 +116,9 @@ int usf_linear_f32(const usf_linear_desc* d, usf_stream_t stream);
  *   W_in  readable as [Hp, Kp] (ldw_in  >= Kp), W_hid[i] as [Hp, Hp] (ldw_hid >= Hp),
  *   W_out readable as [Np, Hp] (ldw_out >= Hp), b_in / b_hid[i] / W_ctx / b_ctx as [Hp], b_out as [Np],
  * all ZERO outside their true extents.  z/out: in place (out == z, ldo == ldz).
+ * Both column segments lie inside the rows: off_pass + n_pass <= ldz and off_trans + n_trans <= ldz (else -2).
+ * The two segments are disjoint: a descriptor whose conditioning and transformed columns overlap is refused (-2).
+ * Nothing but the n_trans transformed columns of the rows [0, M) is written.
  */
 #define USF_MAX_HIDDEN 4
 typedef struct usf_coupling_desc {
@@ -145,11 +148,14 @@ typedef struct usf_coupling_desc {
    * plane q at base + q*plane (elements), rows/ld as in the padding contract above with ld >= the padded K.
    * split_hid / split_out additionally have their K (hidden-unit) axis permuted inside every block of 32:
    * position 8g+j holds unit 4g+j (j<4) or 16+4g+(j-4) (j>=4), the order in which the kernel's accumulators
-   * present the previous layer.  Used when all needed planes are given, hidden width in (128, 256], M >= 1024. */
+   * present the previous layer.  Used when all needed planes are given, hidden width in (128, 256], M >= 1024 and
+   * M * ldz < 2^32 (that kernel forms its row offsets in 32 bits; a larger row buffer is served by the exact-f32 kernel). */
   const void* split_in;  int64_t split_in_ld,  split_in_plane;
   const void* split_hid[USF_MAX_HIDDEN]; int64_t split_hid_ld, split_hid_plane;
   const void* split_out; int64_t split_out_ld, split_out_plane;
-  /* Optional (ABI 32), used by the library's own training path (usflows_hip_internal.h); NULL: off. */
+  /* Optional (ABI 32), used by the library's own training path (usflows_hip_internal.h); NULL: off.  The bf16x3 kernel
+   * writes the whole padded width of the rows [0, M): columns [hidden[l], Hp) of hidden_out[l] receive the padded units'
+   * activations, which are zero (zero weights and biases), columns >= Hp and rows >= M are not touched. */
   float* hidden_out[USF_MAX_HIDDEN]; int64_t ld_hidden_out;
   /* act == USF_ACT_GATE (ABI 32), used by the library's own training path (usflows_hip_internal.h). */
   const float* gate[USF_MAX_HIDDEN]; int64_t ld_gate;

@@ -443,6 +443,16 @@ int coupling_dispatch(const usf_coupling_desc* d, hipStream_t stream, const CplV
     if (v && v->ldw_ctx < d->hidden[0]) { set_error("usf_coupling_additive_vctx_f32: ldw_ctx %lld below the first hidden width", (long long)v->ldw_ctx); return -2; }
     return coupling_tiny_dispatch(d, stream, v);
   }
+  // both column segments inside the rows, and disjoint: the layer conditions on columns it does not write
+  if (d->off_pass < 0 || d->off_trans < 0 || d->off_pass + d->n_pass > d->ldz || d->off_trans + d->n_trans > d->ldz) {
+    set_error("usf_coupling_additive_f32: column segments outside the rows (ldz %lld)", (long long)d->ldz);
+    return -2;
+  }
+  if (d->off_pass < d->off_trans + d->n_trans && d->off_trans < d->off_pass + d->n_pass) {
+    set_error("usf_coupling_additive_f32: the conditioning segment [%lld, %lld) and the transformed segment [%lld, %lld) overlap",
+              (long long)d->off_pass, (long long)(d->off_pass + d->n_pass), (long long)d->off_trans, (long long)(d->off_trans + d->n_trans));
+    return -2;
+  }
   if ((d->n_pass & 3) || (d->off_pass & 3) || (d->off_trans & 3) || (d->ldz & 3) || d->off_trans + ((d->n_trans + 3) / 4) * 4 > d->ldz || (d->ldw_in & 3) || (d->ldw_out & 3) || !aligned16(d->z) ||
       !aligned16(d->W_in) || !aligned16(d->W_out) || !aligned16(d->b_in)) {
     set_error("usf_coupling_additive_f32: n_pass/off_pass/ldz/ldw must be multiples of 4 and pointers 16-byte aligned");
@@ -459,7 +469,7 @@ int coupling_dispatch(const usf_coupling_desc* d, hipStream_t stream, const CplV
     }
   }
   if (coupling_bf16x3_eligible(d)) return coupling_bf16x3_dispatch(d, stream, v);
-  if (d->hidden_out[0] || d->act == USF_ACT_GATE) { set_error("usf_coupling_additive_f32: hidden_out / USF_ACT_GATE are served by the bf16x3 kernel (split planes, hidden width in (128, 256], M >= 1024) and by the tiny-layer kernel (M <= 256, segments <= 64, hidden <= 64) only"); return -2; }
+  if (d->hidden_out[0] || d->act == USF_ACT_GATE) { set_error("usf_coupling_additive_f32: hidden_out / USF_ACT_GATE are served by the bf16x3 kernel (split planes, hidden width in (128, 256], M >= 1024, M * ldz < 2^32) and by the tiny-layer kernel (M <= 256, segments <= 64, hidden <= 64) only"); return -2; }
   CplArgs a;
   a.z = d->z; a.out = d->out; a.ldz = d->ldz;
   a.M = (int)d->M; a.off_pass = (int)d->off_pass; a.n_pass = (int)d->n_pass; a.off_trans = (int)d->off_trans; a.n_trans = (int)d->n_trans; a.n_trans4 = (int)((d->n_trans + 3) / 4 * 4);

@@ -459,7 +459,10 @@ bool coupling_bf16x3_eligible(const usf_coupling_desc* d) {
     if (!d->split_hid[i]) return false;
   int hmax = 0;
   for (int i = 0; i < d->n_hidden; ++i) hmax = d->hidden[i] > hmax ? d->hidden[i] : hmax;
-  return hmax > 128 && hmax <= C3_HMAX && d->M >= 1024;     // instantiated for the 256-wide tile set only
+  if (!(hmax > 128 && hmax <= C3_HMAX && d->M >= 1024)) return false;     // instantiated for the 256-wide tile set only
+  // the kernel forms its row offsets (zoff / ooff: row * ldz + segment offset + column) in 32 bits: every element offset
+  // inside the [M, ldz] row buffer has to fit, i.e. M * ldz < 2^32; larger buffers go to the exact-f32 kernel (64-bit offsets)
+  return d->ldz > 0 && d->M <= 0xffffffffLL / d->ldz;
 }
 
 int coupling_bf16x3_dispatch(const usf_coupling_desc* d, hipStream_t stream, const CplVctx* v) {

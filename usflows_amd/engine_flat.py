@@ -156,10 +156,12 @@ class FlatPlanMixin:
 
     def save_fused_hidden(self, cp, B: int) -> bool:
         """training: the fused bf16x3 coupling kernel stores its hidden activations (usf_coupling_desc::hidden_out) -- where
-        that kernel serves the layer (hidden width in (128, 256], >= 1024 rows), unless USFLOWS_AMD_SAVE_HIDDEN=0"""
+        that kernel serves the layer (hidden width in (128, 256], >= 1024 rows, a row buffer whose element offsets fit 32 bits:
+        coupling_bf16x3_eligible's rule M * ldz < 2^32, restated for the forward launch on the [B, LD] rows and the backward
+        launch on the gradient rows, [B, LD] or [B, LDn]), unless USFLOWS_AMD_SAVE_HIDDEN=0"""
         hm = max(cp["hidden"])
         return (self.gemm_mode == "bf16x3" and config.save_hidden and 128 < hm <= 256
-                and B >= 1024 and self.hmax >= 256 and self.hmax % 4 == 0
+                and B >= 1024 and B * max(self.LD, self.LDn) < (1 << 32) and self.hmax >= 256 and self.hmax % 4 == 0
                 and cp["tr_n"] % 4 == 0 and cp["tr_off"] % 4 == 0)      # (the backward launch reads the transformed half as its input)
 
     def wgrad_from_planes(self, B: int, N: int, K: int) -> bool:
