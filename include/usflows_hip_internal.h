@@ -111,6 +111,33 @@ int usf_radial_logprob_grad_f32(const float* z, int64_t ldz, const float* r, con
                                 void* workspace, int64_t workspace_bytes, usf_stream_t stream);
 
 /*
+ * usf_radial_sample_norm_f32 (an ADDED entry point: every declaration of internal version 4 is unchanged, so the number stays;
+ * a binding that declares it refuses a library without it when it resolves the symbol): RadialDistribution.sample (distributions.py:474-499) in ONE launch -- the
+ * radius r[m] ~ norm_distribution AND z[m, :D] = loc + r[m] * u, u uniform on the unit Lp sphere -- as a pure function of
+ * (seed, offset, m + row_offset, parameters): the same rows for any split of a draw over launches or ranks, no host read-back.
+ *   norm, K, par_a, par_b, logits: exactly as for usf_radial_logprob_f32 (usflows_hip.h): stored parameters, softplus applied
+ *     inside unless USF_NORM_RAW_PARAMS, 1 <= K <= 64, USF_NORM_CHI raw only, par_b NULL for USF_NORM_HALFNORMAL, logits
+ *     required for K > 1.
+ *   r_out [M], optional: receives every row's radius.  z == NULL: the radii only (r_out required; D, loc, p_id ignored).
+ * The radius is computed in fp64 and rounded to fp32 once.  With ph(t) = philox4x32_10(counter m + row_offset, stream
+ * offset ^ 0x85ebca6b ^ (t << 32), key seed) = words w0..w3, u(w) = (w + 1/2) 2^-32 and n = sqrt(-2 ln u(w1)) cos(2 pi u(w2)):
+ *   component k = #{j : C_j <= u(w0 of ph(0)) C_{K-1}} capped at K - 1, C_j = sum_{i <= j} exp(l_i - max l) in index order
+ *   LogNormal  r = exp(mu + sigma n)  [ph(0)]       HalfNormal  r = sigma |n|       Weibull  r = lambda (-ln u(w1))^(1/k)
+ *   Gamma(a, rate b): Marsaglia-Tsang with a' = a < 1 ? a + 1 : a, d = a' - 1/3, c = 1 / sqrt(9 d); attempt t = 0 .. 31 takes
+ *     w1..w3 of ph(t), v = (1 + c n)^3, accepts when v > 0 and ln u(w3) < n^2 / 2 + d - d v + d ln v, then g = d v; the loop
+ *     bound is a compile-time constant and g = d when no attempt accepted (the kernel cannot spin); a < 1: g *=
+ *     u(w0 of ph(0xFFFF))^(1/a);  r = g / b
+ *   Chi(nu, s): that draw with shape nu / 2, r = s sqrt(2 g)
+ *   r is clamped from below to the smallest normal fp32 (as torch's Gamma.rsample).
+ * The direction uses usf_radial_sample_f32's counters, streams and arithmetic unchanged: z is bit for bit what that entry
+ * point writes when handed r_out.  Columns [D, ldz) are not written.  Returns -2 (sizes, ids, K) / -1 (null pointer) with
+ * usf_last_error set before anything is launched.
+ */
+int usf_radial_sample_norm_f32(float* z, int64_t ldz, int64_t M, int64_t D, int32_t p_id, const float* loc,
+                               int32_t norm, int32_t K, const float* par_a, const float* par_b, const float* logits,
+                               float* r_out, uint64_t seed, uint64_t offset, int64_t row_offset, usf_stream_t stream);
+
+/*
  * usf_coupling_planes_ctx (internal version 3): usf_coupling_planes (usflows_hip.h) whose conditioner is a ConditionalDenseNN
  * with context_dim == 1 (networks.py:739-751: layers[1](context) is added to the first layer's pre-activation).  The first
  * layer's accumulators start at

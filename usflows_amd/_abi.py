@@ -271,6 +271,8 @@ INTERNAL_SYMBOLS = {
     "usf_radial_logprob_grad_workspace": (C.c_int64, [C.c_int64, C.c_int64]),
     "usf_radial_logprob_grad_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int32, C.c_int32,
                                               _fp, _fp, _fp, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_void_p]),
+    "usf_radial_sample_norm_f32": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int32, C.c_int32, _fp, _fp, _fp,
+                                             _fp, C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p]),
     "usf_gated_norm_rows_bwd_f32": (C.c_int, [C.POINTER(GatedNormBwdDesc), C.c_void_p]),
     "usf_coupling_planes_ctx": (C.c_int, [C.POINTER(CouplingPlanesDesc), _fp, C.c_int64, _fp, _fp, C.c_void_p]),
     "usf_coupling_additive_vctx_f32": (C.c_int, [C.POINTER(CouplingDesc), _fp, C.c_int64, C.c_int32, _fp, C.c_int64, _fp, C.c_void_p]),

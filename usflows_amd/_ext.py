@@ -359,6 +359,14 @@ def radial_sample(z, ldz, M, D, base, loc, r, seed, offset, row_offset=0):
                                       current_stream(z.device)), tape=False)
 
 
+def radial_sample_norm(z, ldz, M, D, p_id, loc, norm, K, par_a, par_b, logits, r_out, seed, offset, row_offset=0):
+    """usf_radial_sample_norm_f32: radii from the norm distribution and directions on the unit Lp sphere in one launch
+    (include/usflows_hip_internal.h); z None: the radii only, into r_out"""
+    dev = next((t.device for t in (z, r_out) if t is not None), None)
+    _launch("usf_radial_sample_norm_f32", (ptr(z), ldz, M, D, int(p_id), ptr(loc), int(norm), int(K), ptr(par_a), ptr(par_b),
+                                           ptr(logits), ptr(r_out), seed, offset, row_offset, current_stream(dev)), tape=False)
+
+
 def variates_from_bits(bits, u=None, laplace=None, exponential=None):
     """the head kernels' word -> variate maps on caller-supplied int32/uint32 words (include/usflows_hip.h)"""
     _launch("usf_variates_from_bits_f32", (bits.data_ptr(), bits.numel(), ptr(u), ptr(laplace), ptr(exponential),

@@ -199,6 +199,9 @@ int radial_grad(const float* z, int64_t ldz, const float* r, const float* g_lp, 
                 const float* loc, int32_t norm, int32_t K, const float* par_a, const float* par_b, const float* logits, float* g,
                 int64_t ldg, float* d_loc, float* d_a, float* d_b, float* d_logits, void* workspace, int64_t workspace_bytes,
                 hipStream_t stream);
+int radial_sample_norm(float* z, int64_t ldz, int64_t M, int64_t D, int32_t p_id, const float* loc, int32_t norm, int32_t K,
+                       const float* par_a, const float* par_b, const float* logits, float* r_out, uint64_t seed, uint64_t offset,
+                       int64_t row_offset, hipStream_t stream);
 
 }  // namespace usf
 
@@ -583,6 +586,12 @@ int usf_radial_logprob_f32(const float* z, int64_t ldz, int64_t M, int64_t D, in
                            usf_stream_t stream) {
   return usf::radial_logprob(z, ldz, M, D, p_id, loc, norm, K, par_a, par_b, logits, logdv_const, logdet_const, logdet_dev, logp,
                              r_out, sum_out, (hipStream_t)stream);
+}
+int usf_radial_sample_norm_f32(float* z, int64_t ldz, int64_t M, int64_t D, int32_t p_id, const float* loc, int32_t norm, int32_t K,
+                               const float* par_a, const float* par_b, const float* logits, float* r_out, uint64_t seed,
+                               uint64_t offset, int64_t row_offset, usf_stream_t stream) {
+  return usf::radial_sample_norm(z, ldz, M, D, p_id, loc, norm, K, par_a, par_b, logits, r_out, seed, offset, row_offset,
+                                 (hipStream_t)stream);
 }
 int64_t usf_radial_logprob_grad_workspace(int64_t M, int64_t D) { return usf::radial_grad_workspace(M, D); }
 int usf_radial_logprob_grad_f32(const float* z, int64_t ldz, const float* r, const float* g_lp, int64_t M, int64_t D, int32_t p_id,

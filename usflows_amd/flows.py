@@ -330,9 +330,12 @@ class Flow(LayerLoopMixin, FitMixin, torch.nn.Module):
 
     def sample(self, sample_shape: Iterable[int] = None, context: Optional[torch.Tensor] = None,
                seed: Optional[int] = None, row_offset: int = 0) -> torch.Tensor:
-        """x = f(z), z ~ base (flows.py:247-265).  On a ROCm device with a Laplace/Normal base the
-        noise comes from the Philox head kernel (``seed``/``row_offset`` select the substream; the
-        default draws a fresh seed from torch's generator), then one fused forward pass."""
+        """x = f(z), z ~ base (flows.py:247-265).  On a ROCm device with a Laplace/Normal base, or a RadialDistribution
+        base whose norm distribution the device serves (``radial.norm_spec``), the noise comes from ONE Philox head launch:
+        row i of the result is a pure function of (``seed``, ``i + row_offset``), so the same seed gives the same latents
+        and a draw may be split over calls or ranks by ``row_offset`` (the default draws a fresh seed from torch's
+        generator); then one fused forward pass.  A radial base with any other norm distribution takes its radii from
+        that distribution's own ``sample`` (torch's generator): only its directions follow the seed."""
         if sample_shape is None:
             sample_shape = [1]
         dev = self._param_device()
@@ -350,14 +353,21 @@ class Flow(LayerLoopMixin, FitMixin, torch.nn.Module):
                 base = _ext.BASE_LAPLACE if info[0] == "laplace" else _ext.BASE_NORMAL
                 _ext.base_sample(z, eng.D, n, eng.D, base, info[1], info[2], seed, 0, row_offset)
             elif info is not None and info[0] == "radial" and self.base_distribution.n_batch_dims == 0:
-                # RadialDistribution.sample (distributions.py:474-499): radii from the (arbitrary, 1-D) norm
-                # distribution -- O(n) torch work -- directions on the unit Lp sphere from the Philox kernel
+                # RadialDistribution.sample (distributions.py:474-499).  A norm distribution the device serves: radii and
+                # directions from ONE launch, a pure function of (seed, row + row_offset).  Any other (arbitrary, 1-D) norm
+                # distribution: radii from its own sample() -- O(n) torch work on torch's generator -- directions on the unit
+                # Lp sphere from the Philox kernel
                 if seed is None:
                     seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-                r = self.base_distribution.norm_distribution.sample((n,)).reshape(n).to(device=dev, dtype=torch.float32)
-                z = torch.empty(n, eng.D, dtype=torch.float32, device=dev)
-                base = {1.0: _ext.BASE_LPNORM1, 2.0: _ext.BASE_LPNORM2}.get(info[2], _ext.BASE_LPNORMINF)
-                _ext.radial_sample(z, eng.D, n, eng.D, base, info[1], r.contiguous(), seed, 0, row_offset)
+                z = None
+                if config.radial:
+                    from . import radial
+                    z = radial.sample(self.base_distribution, n, seed, 0, row_offset)
+                if z is None:
+                    r = self.base_distribution.norm_distribution.sample((n,)).reshape(n).to(device=dev, dtype=torch.float32)
+                    z = torch.empty(n, eng.D, dtype=torch.float32, device=dev)
+                    base = {1.0: _ext.BASE_LPNORM1, 2.0: _ext.BASE_LPNORM2}.get(info[2], _ext.BASE_LPNORMINF)
+                    _ext.radial_sample(z, eng.D, n, eng.D, base, info[1], r.contiguous(), seed, 0, row_offset)
             else:
                 z = self.base_distribution.sample(shape).to(dev).reshape(n, eng.D).float()
             x = eng.transform(z, "forward", context)
@@ -378,9 +388,10 @@ class Flow(LayerLoopMixin, FitMixin, torch.nn.Module):
 
     def _radial_sample_image(self, shape, dev, seed, row_offset):
         """z ~ RadialDistribution with an image-shaped loc [C, H, W] (the live configurations' base: mnist.yaml:79-92) on
-        the Philox kernel: radii from the norm distribution (O(n) torch work), directions on the unit Lp sphere over the
-        FLATTENED event (distributions.py:474-499: u.reshape(*sample_shape, *loc.shape)) from usf_radial_sample_f32.
-        None: not this kind of base"""
+        the Philox kernels: directions on the unit Lp sphere over the FLATTENED event (distributions.py:474-499:
+        u.reshape(*sample_shape, *loc.shape)); the radii in the same launch where the device serves the norm distribution
+        (``radial.sample``: a pure function of seed and row), else from its own sample() (O(n) torch work on torch's
+        generator) ahead of usf_radial_sample_f32.  None: not this kind of base"""
         b = self.base_distribution
         if not (isinstance(b, RadialDistribution) and b.n_batch_dims == 0 and b.loc.is_cuda and b.loc.dtype == torch.float32
                 and float(b.p) in (1.0, 2.0, float("inf")) and config.radial):
@@ -390,6 +401,10 @@ class Flow(LayerLoopMixin, FitMixin, torch.nn.Module):
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         with torch.no_grad():
+            from . import radial
+            z = radial.sample(b, n, seed, 0, row_offset)
+            if z is not None:
+                return z.reshape(*shape, *b.loc.shape)
             r = b.norm_distribution.sample((n,)).reshape(n).to(device=dev, dtype=torch.float32).contiguous()
             z = torch.empty(n, D, dtype=torch.float32, device=dev)
             if n > 0:

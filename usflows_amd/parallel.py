@@ -154,6 +154,9 @@ def _allreduce_gradients_cat(flow, local_rows: int, group=None, average: bool = 
 
 
 def sample_sharded(flow, n_total: int, seed: int, rank: int, world_size: int) -> torch.Tensor:
-    """this rank's rows of a global draw of ``n_total`` samples (same result for any world size)"""
+    """this rank's rows of a global draw of ``n_total`` samples.  Row i's latent is a pure function of (seed, i) for Laplace /
+    Normal bases and for radial bases whose norm distribution the device serves (``radial.norm_spec``): the same latents
+    for any world size, the samples equal to fp32 rounding (a shard of another size may take other kernels through the
+    layers).  A radial base with any other norm distribution draws its radii from torch's generator: not reproducible."""
     lo, hi = shard_rows(n_total, rank, world_size)
     return flow.sample([hi - lo], seed=seed, row_offset=lo)

@@ -349,3 +349,59 @@ def log_prob_from_radius(base, r: torch.Tensor):
         return None
     _ext.load()
     return RadialFinish.apply(r, sp["a"], sp["b"], sp["logits"], sp["p_id"], sp["norm"], sp["K"], sp["D"], sp["logdv"])
+
+
+# ---- sampling: radii and directions in one launch (usf_radial_sample_norm_f32) -------------------------------------------------
+def sample(base, n: int, seed: int, offset: int = 0, row_offset: int = 0, want_r: bool = False):
+    """``n`` rows z [n, D] ~ ``base`` (a ``RadialDistribution`` on a GPU; D = the flattened event) from ONE launch: row i is a
+    pure function of (seed, offset, i + row_offset, the parameters) -- the same rows for any split of a draw over calls or
+    ranks, no host read-back, no use of torch's generator.  ``want_r``: (z, r [n]), the radii drawn.  None when
+    ``radial_spec`` has no device form of this base (the caller keeps the distribution object's own ``sample``)."""
+    loc = getattr(base, "loc", None)
+    if not (torch.is_tensor(loc) and loc.is_cuda):
+        return None
+    with torch.no_grad():
+        sp = radial_spec(base, loc.device)
+        if sp is None:
+            return None
+        _ext.load()
+        n, d = int(n), sp["D"]
+        z = torch.empty(n, d, dtype=torch.float32, device=loc.device)
+        r = torch.empty(n, dtype=torch.float32, device=loc.device) if want_r else None
+        if n > 0:
+            b, lg = sp["b"], sp["logits"]
+            _ext.radial_sample_norm(z, d, n, d, sp["p_id"], loc.detach().reshape(-1), sp["norm"], sp["K"], sp["a"].detach(),
+                                    None if b is None else b.detach(), None if lg is None else lg.detach(), r, int(seed), int(offset),
+                                    int(row_offset))
+    return (z, r) if want_r else z
+
+
+def _norm_device(nd):
+    """the device a norm distribution's parameters live on (None: it holds no tensor)"""
+    if isinstance(nd, torch.nn.Module):
+        for t in list(nd.parameters()) + list(nd.buffers()):
+            return t.device
+    for t in vars(nd).values():
+        if torch.is_tensor(t):
+            return t.device
+    return None
+
+
+def sample_radii(norm_distribution, n: int, seed: int, offset: int = 0, row_offset: int = 0, device=None):
+    """``n`` radii r [n] ~ ``norm_distribution`` from the same launch without a direction (z == NULL): exactly the radii
+    ``sample`` draws for these arguments.  ``device``: where the parameters live (default: taken from them).  None when
+    ``norm_spec`` has no device form of this distribution."""
+    device = torch.device(device) if device is not None else _norm_device(norm_distribution)
+    if device is None or device.type != "cuda":
+        return None
+    with torch.no_grad():
+        ns = norm_spec(norm_distribution, device)
+        if ns is None:
+            return None
+        _ext.load()
+        norm, K, a, b, lg = ns
+        r = torch.empty(int(n), dtype=torch.float32, device=device)
+        if n > 0:
+            _ext.radial_sample_norm(None, 0, int(n), 0, 0, None, norm, K, a.detach(), None if b is None else b.detach(),
+                                    None if lg is None else lg.detach(), r, int(seed), int(offset), int(row_offset))
+    return r
