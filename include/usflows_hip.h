@@ -368,8 +368,10 @@ int usf_conv2d_same_ctx_f32(const float* x, float* y, int64_t B, int64_t cin, in
  * its output stream:  y = res_x + res_sign * (res_mul * conv(in_act(x) * in_mul)),  res_x [B, cout, H, W] (the coupling's
  * input), res_mul [cout * H * W] = 1 - mask -- the arithmetic of usf_conv2d_same_f32 followed by usf_masked_residual_f32,
  * without the conditioner's output tensor ever reaching HBM.  Returns 0 when done, 1 when this shape is not served by the
- * fused form (3 x 3 kernel, 16 / 32 input channels, 16 / 32 / 64 output channels, H W <= 64, 16-byte aligned tensors):
- * the caller then runs the two entry points one after the other; < 0: error. */
+ * fused form (served: 3 x 3 kernel, 16 / 32 / 48 input channels, 16 / 32 / 48 / 64 output channels, H W <= 64, every tensor
+ * 16-byte aligned; the groups of the fused form hold at most 8192 outputs, so a launch may run with fewer samples per group
+ * than the plain convolution of the same shape -- the sums per output element are the same): the caller then runs the two
+ * entry points one after the other; < 0: error. */
 int usf_conv2d_same_res_f32(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
                             const void* w_planes, const float* bias, const float* in_mul, int32_t in_act, float in_slope,
                             const float* res_x, const float* res_mul, float res_sign, usf_stream_t stream);

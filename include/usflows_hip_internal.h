@@ -16,7 +16,7 @@
 extern "C" {
 #endif
 
-#define USF_INTERNAL_VERSION 4
+#define USF_INTERNAL_VERSION 5
 
 /* USF_INTERNAL_VERSION of the header the library was built from (host only, launches nothing). */
 int usf_internal_version(void);
@@ -71,7 +71,7 @@ int usf_internal_version(void);
  *
  * usf_sizeof_desc(kind) also reports sizeof(usf_mt_chunk|usf_grad_job|usf_psum_job) for kind 8|11|12 and
  * sizeof(usf_gated_norm_bwd_desc|usf_wgrad_job|usf_wreduce_job|usf_wplanes_job) for kind 13|14|15|16 and
- * sizeof(usf_adam_chunk|usf_grad_chunk) for kind 17|18.
+ * sizeof(usf_adam_chunk|usf_grad_chunk|usf_conv_variant_query|usf_conv_variant) for kind 17|18|19|20.
  */
 
 /*
@@ -310,10 +310,51 @@ int usf_gated_tail_bwd_f32(const float* h, const float* x, const float* dy, floa
  * gate_mul [cout * H * W] or NULL = the forward layer's input mask, gate_add [B, cout, H, W] or NULL = the gradient that
  * reaches the same tensor along another branch (the forward input forks: GatedConv's skip connection, networks.py:108-122).
  * The arithmetic of usf_conv2d_same_f32 followed by usf_act_grad_f32 and the mask product / the sum, in one pass.  Returns 0
- * when done, 1 when the shape is not served by this form (as usf_conv2d_same_res_f32), < 0 on error. */
+ * when done, 1 when the shape is not served by this form, < 0 on error.  Served: what usf_conv2d_same_res_f32 serves (3 x 3,
+ * 16 / 32 / 48 -> 16 / 32 / 48 / 64 channels, H W <= 64, every tensor 16-byte aligned); under the tuning knob conv_wsp=0 (the
+ * register-weight kernel) no 48 channels and no gate_add form.  usf_conv2d_same_variant answers for a given call. */
 int usf_conv2d_same_gate_f32(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
                              const void* w_planes, const float* gate_h, float gate_slope, const float* gate_mul,
                              const float* gate_add, usf_stream_t stream);
+
+/*
+ * usf_conv2d_same_variant (internal version 5): which kernel a call of the "same" convolution's entry points launches, and
+ * how -- answered by the planning functions the entry points themselves launch from (host only, nothing is launched, no
+ * tensor pointer exists).  Three kernels serve the five entry points:
+ *   1  conv2d_same_bf16x3_kernel<CTX>            every shape usf_conv2d_same_f32 accepts, gated mode, 4-byte tensor accesses
+ *   2  conv2d_same_wreg_kernel<NB, CP, NCT, CTX> 3 x 3, 16 / 32 -> 16 / 32 / 64 channels, H W <= 64; only under the tuning
+ *                                                knob conv_wsp=0; no gate-add form, residual forms up to 8192 outputs per group
+ *   3  conv2d_same_wsp_kernel<NB, CP, NCT, CTX>  3 x 3, 16 / 32 / 48 -> 16 / 32 / 48 / 64 channels, H W <= 64
+ * Kernels 2 and 3 want (cin H W) and (cout H W) multiples of 4 and every tensor 16-byte aligned; a plain / ctx call they do
+ * not serve runs on kernel 1, a res / gate call they do not serve is answered with return code 1 (kernel 0 here).
+ * Query: entry (USF_CONV_ENTRY_*; GATED: usf_conv2d_same_f32 with gate_x, cout = the packed row count), B, cin, cout, H, W,
+ * ks, aligned (1: every tensor pointer is 16-byte aligned), cus (0: ask the device; > 0: plan for that many compute units --
+ * works without a GPU).  The tuning knobs in force (conv_wreg, conv_wsp, conv_small_s) are honoured as a launch honours them.
+ * Answer: kernel (0: not served / refused); S samples per group, groups = ceil(B / S), grid blocks, lds_bytes; for kernels 2
+ * and 3 the instantiation (NB k-blocks, CP padded input channels, NCT output tiles) and the largest n each magic-number
+ * division umulhi(n, m) is applied to (max_mHW / mW / mSE / mSO; -1: that division is not made); for kernel 1 the patch shape
+ * (PC, PR) in 16-row tiles of a full group and of the last group (they differ when the last group is ragged); CTX: the
+ * context instantiation.  Returns 0, -1 (null pointer) or -2 (bad entry).
+ */
+#define USF_CONV_ENTRY_PLAIN 0
+#define USF_CONV_ENTRY_CTX 1
+#define USF_CONV_ENTRY_RES 2
+#define USF_CONV_ENTRY_GATE_MUL 3
+#define USF_CONV_ENTRY_GATE_ADD 4
+#define USF_CONV_ENTRY_GATED 5
+typedef struct usf_conv_variant_query {
+  int32_t entry, aligned;
+  int64_t B, cin, cout, H, W, ks;
+  int32_t cus, reserved;
+} usf_conv_variant_query;
+typedef struct usf_conv_variant {
+  int32_t kernel, S;
+  int64_t grid, groups, lds_bytes;
+  int32_t NB, CP, NCT, CTX;
+  int32_t PC_full, PR_full, PC_last, PR_last;
+  int32_t max_mHW, max_mW, max_mSE, max_mSO;
+} usf_conv_variant;
+int usf_conv2d_same_variant(const usf_conv_variant_query* q, usf_conv_variant* out);
 
 /* which instantiation of usf_gemm_planes_bf16x3 serves the descriptor (nothing is launched): 5000 + 10 TN + (1: fp32 output, 0: planes output),
  * TN = column-block width in 32-feature blocks (4 or 5, whichever pads the output less); 0 for empty extents */

@@ -724,7 +724,10 @@ def test_conv2d_with_masked_residual_equals_the_two_passes(B, cin, cout, H, W):
     rx48 = torch.randn(B, 48, H, W, generator=g).to("cuda:0")
     om48 = (torch.rand(48 * H * W, generator=g) > 0.5).float().to("cuda:0")
     fused = _ext.conv2d_same_res(x, p48, 48, 3, rx48, om48, -1.0)
-    if fused is not None:
+    served = _ext.conv2d_same_variant("res", B, cin, 48, H, W, 3)["kernel"]       # (the launch path's own planner, for this device)
+    assert served == 3                                    # these shapes: the wave-specialised kernel, on any number of compute units
+    assert (fused is not None) == (served != 0)
+    if served:
         assert torch.equal(fused, _ext.masked_residual(rx48, _ext.conv2d_same(x, p48, 48, 3), om48, -1.0))
     # a 1 x 1 kernel: not served by the fused form
     w1 = torch.randn(cout, cin, 1, 1, generator=g).to("cuda:0")

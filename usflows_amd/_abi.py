@@ -4,7 +4,7 @@ loads the library or launches anything; ``_ext.py`` does, and re-exports every n
 import ctypes as C
 
 USF_ABI_VERSION = 36          # include/usflows_hip.h
-USF_INTERNAL_VERSION = 4      # include/usflows_hip_internal.h
+USF_INTERNAL_VERSION = 5      # include/usflows_hip_internal.h
 USF_MAX_HIDDEN = 4
 
 ACT_NONE, ACT_LEAKY_RELU, ACT_GATE = 0, 1, 2
@@ -109,6 +109,23 @@ class GradChunk(C.Structure):
     _fields_ = [("g", _fp), ("n", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ConvVariantQuery(C.Structure):
+    """usf_conv_variant_query: one call of the "same" convolution's entry points, as usf_conv2d_same_variant is asked about it"""
+    _fields_ = [("entry", C.c_int32), ("aligned", C.c_int32), ("B", C.c_int64), ("cin", C.c_int64), ("cout", C.c_int64),
+                ("H", C.c_int64), ("W", C.c_int64), ("ks", C.c_int64), ("cus", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ConvVariant(C.Structure):
+    """usf_conv_variant: the kernel, group size, grid and instantiation / patch shapes such a call launches"""
+    _fields_ = [("kernel", C.c_int32), ("S", C.c_int32), ("grid", C.c_int64), ("groups", C.c_int64), ("lds_bytes", C.c_int64),
+                ("NB", C.c_int32), ("CP", C.c_int32), ("NCT", C.c_int32), ("CTX", C.c_int32),
+                ("PC_full", C.c_int32), ("PR_full", C.c_int32), ("PC_last", C.c_int32), ("PR_last", C.c_int32),
+                ("max_mHW", C.c_int32), ("max_mW", C.c_int32), ("max_mSE", C.c_int32), ("max_mSO", C.c_int32)]
+
+
+CONV_ENTRIES = {"plain": 0, "ctx": 1, "res": 2, "gate_mul": 3, "gate_add": 4, "gated": 5}   # USF_CONV_ENTRY_*
+
+
 class GatedNormDesc(C.Structure):
     """usf_gated_norm_desc: row pass of the vector ConvNet conditioner (gate, layer norm, activation)"""
     _fields_ = [("skip", _fp), ("ld_skip", C.c_int64), ("vg", _fp), ("ld_vg", C.c_int64), ("gate_off", C.c_int64),
@@ -195,7 +212,8 @@ class GradJob(C.Structure):
 # usf_sizeof_desc kind -> the struct whose size it reports: every Structure above (load() compares each one with C)
 SIZEOF_KINDS = {OP_LINEAR: LinearDesc, OP_COUPLING: CouplingDesc, 0: Op, 3: LuPrepDesc, 4: PackJob, OP_PACK_PLANES: PackPlanesDesc,
                 OP_GEMM_PLANES: GemmPlanesDesc, OP_COUPLING_PLANES: CouplingPlanesDesc, 8: MtChunk, OP_GATED_NORM: GatedNormDesc,
-                OP_CALL: CallDesc, 11: GradJob, 12: PsumJob, 13: GatedNormBwdDesc, 14: WgradJob, 15: WReduceJob, 16: WPlanesJob, 17: AdamChunk, 18: GradChunk}
+                OP_CALL: CallDesc, 11: GradJob, 12: PsumJob, 13: GatedNormBwdDesc, 14: WgradJob, 15: WReduceJob, 16: WPlanesJob, 17: AdamChunk, 18: GradChunk,
+                19: ConvVariantQuery, 20: ConvVariant}
 
 
 # every symbol include/usflows_hip.h declares (the stable public ABI): (restype, argtypes)
@@ -279,6 +297,7 @@ INTERNAL_SYMBOLS = {
     "usf_coupling_additive_vctx_variant": (C.c_int, [C.POINTER(CouplingDesc), C.c_int32]),
     "usf_conv_ctx_wgrad_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_void_p]),
     "usf_conv2d_same_gate_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [C.c_void_p, _fp, C.c_float, _fp, _fp, C.c_void_p]),
+    "usf_conv2d_same_variant": (C.c_int, [C.POINTER(ConvVariantQuery), C.POINTER(ConvVariant)]),
     "usf_conv_wgrad_workspace": (C.c_int64, [C.c_int64] * 6),
     "usf_conv_wgrad_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [_fp, _fp, C.c_int32, C.c_float, _fp, _fp, _fp, C.c_int64,
                                      C.c_void_p]),

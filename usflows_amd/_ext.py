@@ -23,7 +23,7 @@ from ._abi import (  # noqa: E402,F401  -- the declarations, re-exported: caller
     BASE_LPNORM1, BASE_LPNORM2, BASE_LPNORMINF, BASE_ROWSUM, NORM_LOGNORMAL, NORM_GAMMA, NORM_RAW_PARAMS, NORM_WEIBULL, NORM_HALFNORMAL, NORM_CHI, RADIAL_MAX_K, OP_LINEAR,
     OP_COUPLING, OP_PACK_PLANES, OP_GEMM_PLANES, OP_COUPLING_PLANES, OP_GATED_NORM, OP_CALL, PLANES_BF16X3, PLANES_F16X2, CALL_FNS,
     FN_COUPLING_PLANES_CTX, FN_COUPLING_VCTX, VCTX_MAX,
-    _fp, LinearDesc, CouplingDesc, PackPlanesDesc, GemmPlanesDesc, CouplingPlanesDesc, MtChunk, AdamChunk, GradChunk, GatedNormDesc, GatedNormBwdDesc,
+    _fp, LinearDesc, CouplingDesc, PackPlanesDesc, GemmPlanesDesc, CouplingPlanesDesc, MtChunk, AdamChunk, GradChunk, ConvVariantQuery, ConvVariant, CONV_ENTRIES, GatedNormDesc, GatedNormBwdDesc,
     CallDesc, _OpUnion, Op, LuPrepDesc, PackJob, PsumJob, WgradJob, WReduceJob, WPlanesJob, GradJob, SIZEOF_KINDS, PUBLIC_SYMBOLS,
     INTERNAL_SYMBOLS, SYMBOLS)
 
@@ -593,6 +593,16 @@ def conv2d_same_gate(x, planes, cout, ks, gate_h, gate_slope, gate_mul=None, gat
                                               float(gate_slope), ptr(gate_mul), ptr(gate_add), current_stream(x.device)),
                  tape=False, unserved_ok=True)
     return None if rc else y
+
+
+def conv2d_same_variant(entry, B, cin, cout, H, W, ks=3, aligned=True, cus=0) -> dict:
+    """usf_conv2d_same_variant: which kernel an entry point of the "same" convolution ("plain", "ctx", "res", "gate_mul",
+    "gate_add", "gated") launches for these sizes and how, as a dict of the answer's fields; cus > 0 plans for that many compute
+    units (no GPU needed), 0 asks the device"""
+    q = ConvVariantQuery(CONV_ENTRIES[entry], int(bool(aligned)), int(B), int(cin), int(cout), int(H), int(W), int(ks), int(cus), 0)
+    out = ConvVariant()
+    check(load().usf_conv2d_same_variant(C.byref(q), C.byref(out)), "usf_conv2d_same_variant")
+    return {name: int(getattr(out, name)) for name, _ in ConvVariant._fields_}
 
 
 def pointwise_conv_supported(cin: int, cout: int, gated: bool = False) -> bool:

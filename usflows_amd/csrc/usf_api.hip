@@ -114,6 +114,7 @@ int conv2d_same(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, 
                 const void* wplanes, const float* bias, const float* in_mul, int32_t in_act, float in_slope,
                 int32_t out_act, float out_slope, const float* gate_x, int64_t gate_channels, hipStream_t stream,
                 const float* ctx = nullptr, int64_t ctx_stride = 0, const float* w_ctx = nullptr);
+int conv2d_same_variant(const usf_conv_variant_query* q, usf_conv_variant* out);
 int conv_ctx_wgrad(const float* dy, const float* ctx, int64_t ctx_stride, int64_t B, int64_t cout, int64_t H, int64_t W, int64_t ks,
                    float* dw_ctx, hipStream_t stream);
 int conv2d_same_gate(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
@@ -237,6 +238,8 @@ int usf_sizeof_desc(int32_t kind) {
     case 16: return (int)sizeof(usf_wplanes_job);
     case 17: return (int)sizeof(usf_adam_chunk);
     case 18: return (int)sizeof(usf_grad_chunk);
+    case 19: return (int)sizeof(usf_conv_variant_query);
+    case 20: return (int)sizeof(usf_conv_variant);
     default: return -1;
   }
 }
@@ -472,6 +475,7 @@ int usf_gated_tail_bwd_f32(const float* h, const float* x, const float* dy, floa
                              ln_eps, dparams, workspace, workspace_floats, job, (hipStream_t)stream);
 }
 int64_t usf_conv2d_weight_elems(int64_t cin, int64_t cout, int64_t ks) { return usf::conv2d_weight_elems(cin, cout, ks); }
+int usf_conv2d_same_variant(const usf_conv_variant_query* q, usf_conv_variant* out) { return usf::conv2d_same_variant(q, out); }
 int usf_conv2d_same_fits(int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks) { return usf::conv2d_same_fits(cin, cout, H, W, ks); }
 int usf_conv2d_same_f32(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
                         const void* w_planes, const float* bias, const float* in_mul, int32_t in_act, float in_slope,

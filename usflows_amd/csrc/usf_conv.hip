@@ -20,6 +20,7 @@
 // Row strides of both LDS images are an odd number of 16-byte units: the 16 lanes of a fragment read hit 16 different
 // bank groups.
 #include "usf_common.h"
+#include "usf_conv_plan.h"
 #include <type_traits>
 
 namespace usf {
@@ -264,10 +265,10 @@ __global__ __launch_bounds__(512, 2) void conv2d_same_bf16x3_kernel(const ConvAr
     };
     typedef std::integral_constant<int, 1> I1;
     typedef std::integral_constant<int, 2> I2;
-    const int c16 = a.coutp / 16, r32 = (R + 31) / 32;
-    if (((c16 + 1) / 2) * r32 >= 7 || (a.gateC > 0 && (c16 / 2) * r32 >= 4)) patches(I2(), I2());
-    else if (a.gateC > 0) patches(I2(), I1());                       // (value, gate) tile pairs stay together
-    else if (c16 * r32 >= 7) patches(I1(), I2());
+    const int shape = conv_patch_shape(a.coutp, R, a.gateC);         // (usf_conv_plan.h: the probe reports the same rule)
+    if (shape == 0x22) patches(I2(), I2());
+    else if (shape == 0x21) patches(I2(), I1());                     // (value, gate) tile pairs stay together
+    else if (shape == 0x12) patches(I1(), I2());
     else patches(I1(), I1());
     __syncthreads();                                                 // the image is rewritten by the next group
   }
@@ -308,6 +309,73 @@ int conv2d_same_fits(int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks
   return 0;
 }
 
+// The first kernel's launch for B samples of a shape conv2d_same accepts: as many samples per group as fit 158 KB of LDS and
+// the staging registers (at most 8; at least one has to fit: else -3 with p->lds = one sample's bytes), clipped to B; one
+// block per group up to the device's compute units (cus == 0: ask the device).
+int conv_first_plan(int64_t B, int cin, int cout, int H, int W, int ks, int cus, ConvPlan* p) {
+  int S = 8;
+  int64_t lds = 0;
+  for (; S >= 1; --S) {
+    lds = conv_lds_bytes(cin, cout, H, W, ks, S, &p->xs16, &p->ws16, &p->cp, &p->kp, &p->coutp);
+    if (lds <= 158 * 1024 && conv_stage_iters(cin, H * W, S) <= 16) break;
+  }
+  p->lds = lds;
+  p->S = S < 1 ? 0 : S;
+  p->groups = 0; p->grid = 0;
+  if (S < 1) return -3;
+  if (S > B) {
+    S = (int)B;
+    lds = conv_lds_bytes(cin, cout, H, W, ks, S, &p->xs16, &p->ws16, &p->cp, &p->kp, &p->coutp);
+  }
+  p->S = S; p->lds = lds;
+  if (cus <= 0) cus = device_cu_count();
+  p->groups = (B + S - 1) / S;
+  p->grid = (unsigned)(p->groups < cus ? p->groups : cus);
+  return 0;
+}
+
+// usf_conv2d_same_variant: the plans above, asked instead of launched (no pointer is looked at, nothing is launched)
+int conv2d_same_variant(const usf_conv_variant_query* q, usf_conv_variant* o) {
+  if (!q || !o) { set_error("usf_conv2d_same_variant: null pointer"); return -1; }
+  *o = usf_conv_variant();
+  o->max_mHW = o->max_mW = o->max_mSE = o->max_mSO = -1;
+  const int64_t B = q->B, cin = q->cin, cout = q->cout, H = q->H, W = q->W, ks = q->ks;
+  const int e = q->entry;
+  if (e < USF_CONV_ENTRY_PLAIN || e > USF_CONV_ENTRY_GATED) { set_error("usf_conv2d_same_variant: bad entry"); return -2; }
+  if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0 || B > 0x7fffffff) return 0;
+  const bool fused = e == USF_CONV_ENTRY_RES || e == USF_CONV_ENTRY_GATE_MUL || e == USF_CONV_ENTRY_GATE_ADD;
+  const bool first_ok = !(cin > 64 || cout > 64 || H * W > 256 || (ks != 1 && ks != 3));   // conv2d_same's size rule
+  if (fused ? ks != 3 : !first_ok) return 0;
+  if (e == USF_CONV_ENTRY_GATED && cout % 32 != 0) return 0;
+  const int cus = q->cus > 0 ? q->cus : device_cu_count();
+  if (ks == 3 && e != USF_CONV_ENTRY_GATED) {
+    ConvWQuery wq;
+    wq.B = B; wq.cin = cin; wq.cout = cout; wq.H = H; wq.W = W;
+    wq.aligned = q->aligned != 0;
+    wq.has_res = fused; wq.res_mul = fused; wq.res_alias = false;
+    wq.res_mode = e == USF_CONV_ENTRY_GATE_MUL ? 1 : (e == USF_CONV_ENTRY_GATE_ADD ? 2 : 0);
+    wq.cus = cus;
+    ConvWPlan wp;
+    conv_wreg_launch_plan(wq, &wp);
+    if (wp.kernel) {
+      o->kernel = wp.kernel; o->S = wp.S; o->grid = wp.grid; o->groups = wp.groups; o->lds_bytes = wp.lds;
+      o->NB = wp.NB; o->CP = wp.CP; o->NCT = wp.NCT; o->CTX = e == USF_CONV_ENTRY_CTX;
+      o->max_mHW = wp.max_mHW; o->max_mW = wp.max_mW; o->max_mSE = wp.max_mSE; o->max_mSO = wp.max_mSO;
+      return 0;
+    }
+  }
+  if (fused) return 0;                                     // the fused forms live on the second / third kernel only
+  ConvPlan p;
+  if (conv_first_plan(B, (int)cin, (int)cout, (int)H, (int)W, (int)ks, cus, &p) != 0) return 0;
+  o->kernel = 1; o->S = p.S; o->grid = p.grid; o->groups = p.groups; o->lds_bytes = p.lds;
+  o->CTX = e == USF_CONV_ENTRY_CTX;
+  const int gateC = e == USF_CONV_ENTRY_GATED ? 1 : 0, HW = (int)(H * W);
+  const int full = conv_patch_shape(p.coutp, p.S * HW, gateC);
+  const int last = conv_patch_shape(p.coutp, (int)(B - (p.groups - 1) * p.S) * HW, gateC);
+  o->PC_full = full >> 4; o->PR_full = full & 15; o->PC_last = last >> 4; o->PR_last = last & 15;
+  return 0;
+}
+
 int conv2d_same(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
                 const void* wplanes, const float* bias, const float* in_mul, int32_t in_act, float in_slope,
                 int32_t out_act, float out_slope, const float* gate_x, int64_t gate_channels, hipStream_t stream,
@@ -344,19 +412,14 @@ int conv2d_same(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, 
   a.dbg = (int)tuning("conv_dbg", 0);
   a.gate_x = gate_x; a.gateC = (int)gate_channels;
   a.ctx = ctx; a.ctx_stride = (int)ctx_stride; a.w_ctx = w_ctx;
-  // samples per group: as many as fit 158 KB of LDS (at most 8; at least one has to fit)
-  int S = 8;
-  int64_t lds = 0;
-  for (; S >= 1; --S) {
-    lds = conv_lds_bytes(a.cin, a.cout, a.H, a.W, a.ks, S, &a.xs16, &a.ws16, &a.cp, &a.kp, &a.coutp);
-    if (lds <= 158 * 1024 && conv_stage_iters(a.cin, a.H * a.W, S) <= 16) break;
+  ConvPlan pl;
+  if (conv_first_plan(B, a.cin, a.cout, a.H, a.W, a.ks, 0, &pl) != 0) {
+    set_error("usf_conv2d_same_f32: one sample does not fit the LDS / staging registers (%lld bytes)", (long long)pl.lds);
+    return -3;
   }
-  if (S < 1) { set_error("usf_conv2d_same_f32: one sample does not fit the LDS / staging registers (%lld bytes)", (long long)lds); return -3; }
-  if (S > B) {
-    S = (int)B;
-    lds = conv_lds_bytes(a.cin, a.cout, a.H, a.W, a.ks, S, &a.xs16, &a.ws16, &a.cp, &a.kp, &a.coutp);
-  }
-  a.S = S;
+  const int64_t lds = pl.lds;
+  a.xs16 = pl.xs16; a.ws16 = pl.ws16; a.cp = pl.cp; a.kp = pl.kp; a.coutp = pl.coutp;
+  a.S = pl.S;
   static bool attr_done_dev[2][USF_MAX_DEVICES] = {{false}};   // (the attribute belongs to the device and the instantiation)
   bool& attr_done = attr_done_dev[ctx ? 1 : 0][current_device_slot()];
   const void* kfn = ctx ? reinterpret_cast<const void*>(&conv2d_same_bf16x3_kernel<true>)
@@ -368,9 +431,7 @@ int conv2d_same(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, 
     }
     attr_done = true;
   }
-  const int cus = device_cu_count();
-  const int64_t ngroups = (B + S - 1) / S;
-  const unsigned grid = (unsigned)(ngroups < cus ? ngroups : cus);
+  const unsigned grid = pl.grid;
   if (ctx) hipLaunchKernelGGL(conv2d_same_bf16x3_kernel<true>, dim3(grid), dim3(512), (size_t)lds, stream, a);
   else hipLaunchKernelGGL(conv2d_same_bf16x3_kernel<false>, dim3(grid), dim3(512), (size_t)lds, stream, a);
   return check_launch(ctx ? "usf_conv2d_same_ctx_f32" : "usf_conv2d_same_f32");

@@ -16,13 +16,24 @@
 //     outputs to HBM, splits and stores the next group's image -- two barriers per group; the two waves of a SIMD run
 //     the same program, the hardware interleaves one wave's vector / memory work with the other's MFMAs.
 // Arithmetic: unchanged (six v_mfma_f32_16x16x32_bf16 per fp32-equivalent product, fp32 accumulation, K order
-// tap-major / channel-minor, smallest terms first).  Served: 3 x 3 kernels, 16 / 32 input channels (k-block counts
-// 5 / 9; 48 channels = 14 k-blocks = 168 weight registers do not fit beside the rest), 16 / 32 / 64 output channels
-// (1 / 2 / 4 tiles: 8 / 4 / 2 waves each), H W <= 64 with (channels x H W) a multiple of 4, no gate; everything else
-// stays on the first kernel.
+// tap-major / channel-minor, smallest terms first).
+//
+// This file holds TWO kernels; which limit is whose:
+//   * conv2d_same_wreg_kernel (the register-weight kernel described above; launched only under the tuning knob conv_wsp=0 --
+//     with default knobs conv_wsp_plan serves every shape conv_wreg_plan does): 3 x 3 kernels, 16 / 32 input channels (k-block
+//     counts 5 / 9; 48 channels = 14 k-blocks = 168 weight registers do not fit beside the rest), 16 / 32 / 64 output channels
+//     (1 / 2 / 4 tiles: 8 / 4 / 2 waves each), at most 4 row tiles per wave and 2 staging units per thread and group; the
+//     residual and gate-mul forms, no gate-add form (res_mode 2);
+//   * conv2d_same_wsp_kernel (the wave-specialised kernel, further down; the one the product runs): 16 / 32 / 48 input channels
+//     (14 k-blocks fit: a multiplying wave holds nothing but weights and fragments), 16 / 32 / 48 / 64 output channels (48: the
+//     four-tile instance with one multiplying wave idle), at most 16 row tiles and 1024 staging units per group, fused forms up
+//     to 8192 outputs per group; all three fused forms;
+//   * both: H W <= 64 with (channels x H W) a multiple of 4, every tensor 16-byte aligned, no gated mode; everything else stays
+//     on the first kernel.  conv_wreg_launch_plan below is the one place that decides (usf_conv2d_same_variant reports it).
 #include <stdlib.h>
 
 #include "usf_common.h"
+#include "usf_conv_plan.h"
 
 namespace usf {
 
@@ -51,7 +62,10 @@ struct ConvWArgs {
   const float* w_ctx;          // [cout][9] weights of the context channel
 };
 
-__device__ __forceinline__ int cw_div(int n, unsigned m) { return (int)__umulhi((unsigned)n, m); }
+// n / d from the magic number m = floor(2^32 / d) + 1 (exact for n < 2^16).  d == 1 has no 32-bit magic: 2^32 + 1 wraps to 1,
+// and umulhi(n, 1) is 0 -- every 1 x 1 picture (d = H W) and every picture one pixel wide (d = W) took sample and row 0 for
+// all its rows.  m == 1 can only be that wrap, so it stands for n / 1.
+__device__ __forceinline__ int cw_div(int n, unsigned m) { return m == 1u ? n : (int)__umulhi((unsigned)n, m); }
 
 __device__ __forceinline__ void cw_split(float x, __bf16& h, __bf16& m, __bf16& l) {
   h = (__bf16)x;
@@ -631,41 +645,85 @@ int conv2d_same_wreg_fits(int64_t cin, int64_t cout, int64_t H, int64_t W) {
   return conv_wreg_plan((int)cin, (int)cout, (int)H, (int)W, &cgs, &ib, &lds);
 }
 
-// returns 1 when the launch was made, 0 when the shape is not served (the caller uses the first kernel), < 0 on error
-int conv2d_same_wreg(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, const void* wplanes,
-                     const float* bias, const float* in_mul, int32_t in_act, float in_slope, int32_t out_act, float out_slope,
-                     const float* res_x, const float* res_mul, float res_sign, int res_mode, hipStream_t stream,
-                     const float* ctx, int64_t ctx_stride, const float* w_ctx) {
-  if (!tuning("conv_wreg", 1)) return 0;                   // tuning aid: 0 = first kernel only
-  ConvWArgs a;
+// The plan of a call on the second / third kernel: which of the two, samples per group, grid, LDS layout, instantiation and
+// the reach of the magic-number divisions.  p->kernel == 0: not served here.  conv2d_same_wreg launches from it and
+// usf_conv2d_same_variant answers from it.
+void conv_wreg_launch_plan(const ConvWQuery& q, ConvWPlan* p) {
+  *p = ConvWPlan();
+  p->max_mHW = p->max_mW = p->max_mSE = p->max_mSO = -1;
+  if (!tuning("conv_wreg", 1)) return;                     // tuning aid: 0 = first kernel only
+  const int64_t B = q.B, cin = q.cin, cout = q.cout, H = q.H, W = q.W;
   int64_t lds = 0;
   const int wsp = (int)tuning("conv_wsp", 1);              // tuning aid: 0 = the unspecialised kernel
   int S = 0;
   bool specialised = false;
   if (wsp && cin <= 64 && cout <= 64 && H * W <= 64) {
-    S = conv_wsp_plan((int)cin, (int)cout, (int)H, (int)W, res_x != nullptr, &a.cgs, &a.img_bytes, &lds, B, device_cu_count());
+    S = conv_wsp_plan((int)cin, (int)cout, (int)H, (int)W, q.has_res, &p->cgs, &p->img_bytes, &lds, B, q.cus);
     specialised = S > 0;
   }
-  if (!specialised && cin == 48) return 0;
+  if (!specialised && cin == 48) return;
   if (!specialised)
-    S = conv2d_same_wreg_fits(cin, cout, H, W) ? conv_wreg_plan((int)cin, (int)cout, (int)H, (int)W, &a.cgs, &a.img_bytes, &lds) : 0;
-  if (S == 0 || !aligned16(x) || !aligned16(y) || (in_mul && !aligned16(in_mul)) ||
-      (res_x && ((!res_mul && !res_mode) || !aligned16(res_x) || (res_mul && !aligned16(res_mul)) || res_x == y))) return 0;
-  if (!specialised && res_x && ((int64_t)S * cout * H * W / 4 > 4 * 512 || res_mode == 2)) return 0;
+    S = conv2d_same_wreg_fits(cin, cout, H, W) ? conv_wreg_plan((int)cin, (int)cout, (int)H, (int)W, &p->cgs, &p->img_bytes, &lds) : 0;
+  if (S == 0 || !q.aligned || (q.has_res && ((!q.res_mul && !q.res_mode) || q.res_alias))) return;
+  if (!specialised && q.has_res && ((int64_t)S * cout * H * W / 4 > 4 * 512 || q.res_mode == 2)) return;
+  p->kernel = specialised ? 3 : 2;
+  p->S = S;
+  p->lds = lds;
+  p->mSO = (unsigned)(0x100000000ULL / (uint64_t)(cout * H * W)) + 1u;
+  p->mHW = (unsigned)(0x100000000ULL / (uint64_t)(H * W)) + 1u; p->mW = (unsigned)(0x100000000ULL / (uint64_t)W) + 1u;
+  p->mSE = (unsigned)(0x100000000ULL / (uint64_t)(cin * H * W)) + 1u;
+  p->groups = (B + S - 1) / S;
+  p->grid = (unsigned)(p->groups < q.cus ? p->groups : q.cus);
+  const int nct = (int)((cout + 15) / 16);
+  p->NCT = nct == 1 ? 1 : (nct == 2 ? 2 : 4);
+  p->CP = (int)cin;
+  p->NB = (int)((9 * cin + 31) / 32);
+  // the reach of the kernels' umulhi divisions (their staging loops divide every unit index of a thread, live or not)
+  const int HW = (int)(H * W);
+  int units;                                               // staging unit indices a thread may divide by H W
+  if (specialised) {
+    const int nsv = 512 - 64 * (p->NCT == 1 ? 2 : 4);
+    units = nsv * ((1024 + nsv - 1) / nsv);
+  } else {
+    units = 2 * 512;
+    p->max_mSE = (int)(((S - 1) * cin + (cin - 8)) * HW + HW - 1);   // channel 0 of the last live unit inside the group's chunk
+  }
+  p->max_mHW = units - 1 > S * HW - 1 ? units - 1 : S * HW - 1;
+  p->max_mW = HW - 1;
+  if (q.has_res && q.res_mul && q.res_mode != 2) p->max_mSO = (int)(S * cout * HW - 4);
+}
+
+// returns 1 when the launch was made, 0 when the shape is not served (the caller uses the first kernel), < 0 on error
+int conv2d_same_wreg(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, const void* wplanes,
+                     const float* bias, const float* in_mul, int32_t in_act, float in_slope, int32_t out_act, float out_slope,
+                     const float* res_x, const float* res_mul, float res_sign, int res_mode, hipStream_t stream,
+                     const float* ctx, int64_t ctx_stride, const float* w_ctx) {
+  if (!tuning("conv_wreg", 1)) return 0;                   // (before the device is asked for its size)
+  ConvWQuery q;
+  q.B = B; q.cin = cin; q.cout = cout; q.H = H; q.W = W;
+  q.aligned = aligned16(x) && aligned16(y) && (!in_mul || aligned16(in_mul)) &&
+              (!res_x || (aligned16(res_x) && (!res_mul || aligned16(res_mul))));
+  q.has_res = res_x != nullptr; q.res_mul = res_mul != nullptr; q.res_mode = res_mode; q.res_alias = res_x && res_x == y;
+  q.cus = device_cu_count();
+  ConvWPlan pl;
+  conv_wreg_launch_plan(q, &pl);
+  if (pl.kernel == 0) return 0;
+  const bool specialised = pl.kernel == 3;
+  const int64_t lds = pl.lds;
+  ConvWArgs a;
+  a.cgs = pl.cgs; a.img_bytes = pl.img_bytes;
   a.res_x = res_x; a.res_mul = res_mul; a.res_sign = res_sign; a.res_mode = res_mode;
-  a.mSO = (unsigned)(0x100000000ULL / (uint64_t)(cout * H * W)) + 1u;
+  a.mSO = pl.mSO;
   a.x = x; a.y = y; a.wp = reinterpret_cast<const __bf16*>(wplanes); a.bias = bias; a.in_mul = in_mul;
   a.B = (int)B; a.cin = (int)cin; a.cout = (int)cout; a.H = (int)H; a.W = (int)W;
   a.coutp = (int)((cout + 15) / 16 * 16); a.kp = (int)((9 * cin + 31) / 32 * 32);
   a.dbg = (int)tuning("convw_dbg", 0);
-  a.S = S; a.in_act = in_act; a.out_act = out_act; a.in_slope = in_slope; a.out_slope = out_slope;
-  a.mHW = (unsigned)(0x100000000ULL / (uint64_t)(H * W)) + 1u; a.mW = (unsigned)(0x100000000ULL / (uint64_t)W) + 1u;
-  a.mSE = (unsigned)(0x100000000ULL / (uint64_t)(cin * H * W)) + 1u;
+  a.S = pl.S; a.in_act = in_act; a.out_act = out_act; a.in_slope = in_slope; a.out_slope = out_slope;
+  a.mHW = pl.mHW; a.mW = pl.mW;
+  a.mSE = pl.mSE;
   a.ctx = ctx; a.ctx_stride = (int)ctx_stride; a.w_ctx = w_ctx;
   if (ctx && res_x) { set_error("usf_conv2d_same_ctx_f32: the context channel has no residual / gate form"); return -2; }
-  const int cus = device_cu_count();
-  const int64_t ngroups = (B + S - 1) / S;
-  const unsigned grid = (unsigned)(ngroups < cus ? ngroups : cus);
+  const unsigned grid = pl.grid;
   const int nct = a.coutp / 16;
 #define USF_CW(NB_, CP_, NCT_, CTX_)                                                                                    \
   do {                                                                                                              \
