@@ -21,6 +21,34 @@ namespace usf {
 typedef __bf16 cp_bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 cp_f16x8 __attribute__((ext_vector_type(8)));
 #define USF_CP_F16_GUARD 65000.0f
+// build switch of the vector-instruction diet (profiles/coupling_valu_diet.md; it changes no stored bit).  Splits that convert
+// two neighbouring slots per instruction were measured there too and did not clear; the code is gone.
+#ifndef USF_CP_ADDR32
+#define USF_CP_ADDR32 1                 // global addresses: 32-bit per-thread offsets on scalar bases
+#endif
+
+// A global access at a wave-uniform address plus a 32-bit per-thread byte offset: the instruction takes the uniform part as
+// its scalar base and the offset as its one address register -- when the offset's zero-extension is selected in the block of
+// the access.  The offsets are loop invariants, so their extensions would be hoisted into 64-bit register pairs and added
+// to the uniform part lane by lane, load by load; cp_pin() redefines an offset in place (no instruction), which keeps it
+// 32 bits wide up to the accesses behind the pin.
+__device__ __forceinline__ void cp_pin(unsigned& off) { asm("" : "+v"(off)); }
+template <class V> __device__ __forceinline__ V cp_load(const void* uniform, unsigned off) {
+  return *reinterpret_cast<const V*>(reinterpret_cast<const char*>(uniform) + off);
+}
+template <class V> __device__ __forceinline__ void cp_store(void* uniform, unsigned off, const V v) {
+  *reinterpret_cast<V*>(reinterpret_cast<char*>(uniform) + off) = v;
+}
+
+// max(x, sx) with sx = slope * x as ONE v_max_f32.  fmaxf() compiles to two here: in IEEE mode the compiler first
+// canonicalises an operand it cannot prove quiet (an MFMA result) with a v_max_f32 x, x of its own, which the instruction does
+// anyway.  sx is the product of x, so the multiply -- an instruction the compiler sees, with the wait states a read of a
+// fresh MFMA result needs -- always stands in front of this one.
+__device__ __forceinline__ float max_with_product(float x, float sx) {
+  float r;
+  asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(sx));
+  return r;
+}
 
 template <int NPL> struct CPlanes;
 template <> struct CPlanes<3> {
@@ -76,6 +104,7 @@ struct CplPArgs {
   const char* Whid[2]; int64_t ld_hid, pl_hid; const float* b_hid[2];
   const char* Wout; int64_t ld_out, pl_out; const float* b_out;
   float sign, slope; int act;
+  int act_max;                           // leaky ReLU as max(x, slope x): set by the host for 0 <= slope <= 1 (knob coupling_act_max)
   int32_t* range_flag;
   int descend;                           // knob coupling_descend: blocks take the panels from the last one down
   unsigned long long* dbg;               // tuning builds (-DUSF_STAMP) only
@@ -122,8 +151,15 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  const int wave = tid >> 6;
+  // A32: every global address is a scalar base (kernel argument + wave, stage, block and plane terms, advanced in scalar
+  // registers or sitting in the instruction's immediate) plus one of five 32-bit per-thread offsets computed once
+  // (loff, goff, koff_in, koff_hid, noff), as gemm_planes_kernel addresses its A operand; the host keeps every buffer
+  // below 4 GiB.  Without it each load rebuilds a 64-bit address per lane from the stage / block index.
+  constexpr bool A32 = USF_CP_ADDR32 != 0;
+  const int wave = A32 ? __builtin_amdgcn_readfirstlane(tid >> 6) : (tid >> 6);
   const int lj = lane & 15, lg = lane >> 4;
+  unsigned loff = (unsigned)lane * 16u;                     // the lane's 16 bytes of a chunk line
+  unsigned goff = (unsigned)lg * 16u;                       // ... of a 16-float bias slice
   // this wave's 16 rows.  Descending (the default): the GEMM in front of the layer finishes with the highest rows and the one
   // behind it starts with the lowest, so the layer reads what was written last and leaves behind what is read next
   // (profiles/dead_tiles_and_pack.md; blocks are independent: the results are the same bit for bit)
@@ -135,6 +171,11 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   constexpr unsigned CHB = NPL * 1024u;
   const size_t zbase = ((size_t)panc * p.z_nkb) * CHB + (size_t)lane * 16;
+  char* const zrow = p.z + ((size_t)panc * p.z_nkb) * CHB;         // A32: the wave's panel, a scalar
+  // A32: a thread's part of a weight stage's addresses (bytes).  k-slab: row tid / 4, 8-element group tid % 4; n-tile: row
+  // tid / NC, chunk tid % NC; the thread's further rows lie NT / 4 resp. NT / NC rows on: a scalar term
+  auto k_off = [&](int64_t ld) { return 2u * ((unsigned)(tid >> 2) * (unsigned)ld + 8u * (unsigned)(tid & 3)); };
+  auto n_off = [&](int64_t ld) { return 2u * ((unsigned)(tid / NC) * (unsigned)ld + 8u * (unsigned)(tid % NC)); };
 
   // ---- weight stages (images as in usf_coupling_bf16x3.hip; offsets in bytes, 2-byte elements) ----
   int kdst[NPP];
@@ -146,12 +187,17 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
     kdst[i] = 4 * (c * HP + (r ^ (2 * c)));
     krow[i] = (unsigned)r;
   }
-  auto issue_k = [&](const char* W, int64_t ld, int64_t pl, int k0, f32x4 (&st)[NST]) {
+  auto issue_k = [&](const char* W, int64_t ld, int64_t pl, int k0, unsigned& off, f32x4 (&st)[NST]) {
+    if constexpr (A32) cp_pin(off);
 #pragma unroll
     for (int q = 0; q < NPL; ++q)
 #pragma unroll
-      for (int i = 0; i < NPP; ++i)
-        st[q * NPP + i] = *reinterpret_cast<const f32x4*>(W + 2 * (q * pl + (int64_t)krow[i] * ld + k0 + 8 * ((tid + NT * i) & 3)));
+      for (int i = 0; i < NPP; ++i) {
+        if constexpr (A32)
+          st[q * NPP + i] = cp_load<f32x4>(W + 2 * (q * pl + (int64_t)((NT / 4) * i) * ld + k0), off);
+        else
+          st[q * NPP + i] = *reinterpret_cast<const f32x4*>(W + 2 * (q * pl + (int64_t)krow[i] * ld + k0 + 8 * ((tid + NT * i) & 3)));
+      }
   };
   auto store_k = [&](int buf, const f32x4 (&st)[NST]) {
 #pragma unroll
@@ -160,13 +206,18 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
       for (int i = 0; i < NPP; ++i) *reinterpret_cast<f32x4*>(&lds[buf][q * 16 * HP + kdst[i]]) = st[q * NPP + i];
   };
   auto n_rc = [&](int i, int& r, int& c) { const int idx = tid + NT * i; r = idx / NC; c = idx % NC; };
-  auto issue_n = [&](const char* W, int64_t ld, int64_t pl, int n0, f32x4 (&st)[NST]) {
+  auto issue_n = [&](const char* W, int64_t ld, int64_t pl, int n0, unsigned& off, f32x4 (&st)[NST]) {
+    if constexpr (A32) cp_pin(off);
 #pragma unroll
     for (int q = 0; q < NPL; ++q)
 #pragma unroll
       for (int i = 0; i < NPP; ++i) {
-        int r, c; n_rc(i, r, c);
-        st[q * NPP + i] = *reinterpret_cast<const f32x4*>(W + 2 * (q * pl + (int64_t)(n0 + r) * ld + 8 * c));
+        if constexpr (A32) {
+          st[q * NPP + i] = cp_load<f32x4>(W + 2 * (q * pl + (int64_t)(n0 + (NT / NC) * i) * ld), off);
+        } else {
+          int r, c; n_rc(i, r, c);
+          st[q * NPP + i] = *reinterpret_cast<const f32x4*>(W + 2 * (q * pl + (int64_t)(n0 + r) * ld + 8 * c));
+        }
       }
   };
   auto store_n = [&](int buf, const f32x4 (&st)[NST]) {
@@ -180,9 +231,14 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
   };
 
   // accumulators start at the layer bias
+  // the lane's four entries of tile t of a [256] fp32 vector
+  auto bias4 = [&](const float* b, int t) {
+    if constexpr (A32) { if (t == 0) cp_pin(goff); return cp_load<f32x4>(b + t * 16, goff); }
+    else return *reinterpret_cast<const f32x4*>(b + t * 16 + 4 * lg);
+  };
   f32x4 X1[T], X2[T];
 #pragma unroll
-  for (int t = 0; t < T; ++t) X1[t] = *reinterpret_cast<const f32x4*>(p.b_in + t * 16 + 4 * lg);
+  for (int t = 0; t < T; ++t) X1[t] = bias4(p.b_in, t);
   if (CTX) {
     // lane (lj, lg) holds hidden units 16 t + 4 lg + e of row 16 panel + lj; rows beyond M read the last row's context
     const int crow = min(16 * panc + lj, p.M - 1);
@@ -198,9 +254,12 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
 
   // conditioning features: the B operand straight from the planes
   auto load_z = [&](int kb, vec8 (&dst)[NPL]) {
+    if constexpr (A32) cp_pin(loff);
 #pragma unroll
-    for (int q = 0; q < NPL; ++q)
-      dst[q] = *reinterpret_cast<const vec8*>(p.z + zbase + (size_t)(p.kb_p0 + kb) * CHB + q * 1024);
+    for (int q = 0; q < NPL; ++q) {
+      if constexpr (A32) dst[q] = cp_load<vec8>(zrow + ((size_t)(p.kb_p0 + kb) * CHB + q * 1024), loff);
+      else dst[q] = *reinterpret_cast<const vec8*>(p.z + zbase + (size_t)(p.kb_p0 + kb) * CHB + q * 1024);
+    }
   };
 
   // one 32-k step over all hidden tiles: X[ht] += W(ht) . B; W fragments from a k-slab
@@ -241,7 +300,8 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
   int g = 0;
   f32x4 st[NST];
   vec8 zp[NPL], zn[NPL];
-  issue_k(p.Win, p.ld_in, p.pl_in, 0, st);
+  unsigned koff_in = k_off(p.ld_in), koff_hid = k_off(p.ld_hid), noff = n_off(p.ld_out);
+  issue_k(p.Win, p.ld_in, p.pl_in, 0, koff_in, st);
   load_z(0, zp);
   store_k(0, st);
   __syncthreads();
@@ -249,7 +309,7 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
   // ================= phase 1: X1[h][row] += W_in[h][k] * z[row][k] over the conditioning blocks ============
   for (int s = 0; s + 1 < p.nk_p; ++s, ++g) {
     const int buf = g & 1;
-    issue_k(p.Win, p.ld_in, p.pl_in, (s + 1) * 32, st);
+    issue_k(p.Win, p.ld_in, p.pl_in, (s + 1) * 32, koff_in, st);
     load_z(s + 1, zn);
     mfma_slab(buf, X1, zp);
     CP_PIN_SLAB(NST + NPL, 0);
@@ -261,7 +321,7 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
   }
   {
     const int buf = g & 1;
-    if (NH >= 2) issue_k(p.Whid[0], p.ld_hid, p.pl_hid, 0, st); else issue_n(p.Wout, p.ld_out, p.pl_out, 0, st);
+    if (NH >= 2) issue_k(p.Whid[0], p.ld_hid, p.pl_hid, 0, koff_hid, st); else issue_n(p.Wout, p.ld_out, p.pl_out, 0, noff, st);
     mfma_slab(buf, X1, zp);
     CP_PIN_SLAB(NST, 0);
     __builtin_amdgcn_sched_barrier(0);
@@ -270,17 +330,33 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
     ++g;
   }
   const size_t hbase = (size_t)panc * 8 * CHB + (size_t)lane * 16;      // this lane's line in block 0 of a hidden planes buffer
+  const size_t hrow = (size_t)panc * 8 * CHB;                           // A32: the wave's panel of it, a scalar
   auto activate = [&](f32x4 (&X)[T], int l) {
     if (MODE == 2) {
       // lane (j, g)'s line of block ks holds slots 8 g .. 8 g + 7 = registers 0..3 of tiles 2 ks and 2 ks + 1
+      if constexpr (A32) cp_pin(loff);
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
-        const vec8 hv = *reinterpret_cast<const vec8*>(p.gate[l] + hbase + (size_t)ks * CHB);
+        const vec8 hv = A32 ? cp_load<vec8>(p.gate[l] + (hrow + (size_t)ks * CHB), loff)
+                            : *reinterpret_cast<const vec8*>(p.gate[l] + hbase + (size_t)ks * CHB);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           X[2 * ks][t] = gate_apply(X[2 * ks][t], (float)hv[t], p.slope);
           X[2 * ks + 1][t] = gate_apply(X[2 * ks + 1][t], (float)hv[4 + t], p.slope);
         }
+      }
+      return;
+    }
+    if (p.act_max) {
+      // leaky ReLU with 0 <= slope <= 1 (not -0) as max(x, slope x): two instructions per value where the select takes
+      // four.  Bit for bit the select's value for finite x: x > 0: slope x <= x (the rounded product of a factor <= 1
+      // cannot pass x) and max returns x, as the select does; x < 0: slope x >= x and max returns slope x (equal bits where
+      // they tie); x = +-0: slope x is x itself, sign included.  One block-uniform branch per layer.
+#pragma unroll
+      for (int ht = 0; ht < T; ++ht) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) X[ht][t] = max_with_product(X[ht][t], X[ht][t] * p.slope);
+        guard(X[ht]);
       }
       return;
     }
@@ -293,8 +369,12 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
   };
   auto save_hidden = [&](int l, int ks, const vec8 (&x)[NPL]) {
     if (MODE != 0 && live) {
+      if constexpr (A32) cp_pin(loff);
 #pragma unroll
-      for (int q = 0; q < NPL; ++q) *reinterpret_cast<vec8*>(p.hout[l] + hbase + (size_t)ks * CHB + q * 1024) = x[q];
+      for (int q = 0; q < NPL; ++q) {
+        if constexpr (A32) cp_store<vec8>(p.hout[l] + (hrow + (size_t)ks * CHB + q * 1024), loff, x[q]);
+        else *reinterpret_cast<vec8*>(p.hout[l] + hbase + (size_t)ks * CHB + q * 1024) = x[q];
+      }
     }
   };
   activate(X1, 0);
@@ -310,9 +390,9 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
       const int buf = g & 1;
       const bool last = (ks + 1 == KS);
       const bool next_is_hidden = (l + 2 < NH);
-      if (!last) issue_k(p.Whid[l], p.ld_hid, p.pl_hid, (ks + 1) * 32, st);
-      else if (next_is_hidden) issue_k(p.Whid[l + 1], p.ld_hid, p.pl_hid, 0, st);
-      else issue_n(p.Wout, p.ld_out, p.pl_out, 0, st);
+      if (!last) issue_k(p.Whid[l], p.ld_hid, p.pl_hid, (ks + 1) * 32, koff_hid, st);
+      else if (next_is_hidden) issue_k(p.Whid[l + 1], p.ld_hid, p.pl_hid, 0, koff_hid, st);
+      else issue_n(p.Wout, p.ld_out, p.pl_out, 0, noff, st);
       mfma_slab(buf, Xout, xc);
       if (!last) PT::split(Xin[2 * ks + 2], Xin[2 * ks + 3], xn);
       CP_PIN_SLAB(NST, (NPL == 3) ? 5 : 3);
@@ -329,12 +409,12 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
   };
   if (NH >= 2) {
 #pragma unroll
-    for (int t = 0; t < T; ++t) X2[t] = *reinterpret_cast<const f32x4*>(p.b_hid[0] + t * 16 + 4 * lg);
+    for (int t = 0; t < T; ++t) X2[t] = bias4(p.b_hid[0], t);
     hidden_layer(X1, X2, 0);
   }
   if (NH >= 3) {
 #pragma unroll
-    for (int t = 0; t < T; ++t) X1[t] = *reinterpret_cast<const f32x4*>(p.b_hid[1] + t * 16 + 4 * lg);
+    for (int t = 0; t < T; ++t) X1[t] = bias4(p.b_hid[1], t);
     hidden_layer(X2, X1, 1);
   }
 
@@ -351,11 +431,17 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
     vec8 res[NPL];
     f32x4 bo[2];
     auto issue_res = [&](int nt) {
+      if constexpr (A32) { cp_pin(loff); cp_pin(goff); }
 #pragma unroll
-      for (int q = 0; q < NPL; ++q)
-        res[q] = *reinterpret_cast<const vec8*>(p.z + zbase + (size_t)(p.kb_t0 + nt) * CHB + q * 1024);
+      for (int q = 0; q < NPL; ++q) {
+        if constexpr (A32) res[q] = cp_load<vec8>(zrow + ((size_t)(p.kb_t0 + nt) * CHB + q * 1024), loff);
+        else res[q] = *reinterpret_cast<const vec8*>(p.z + zbase + (size_t)(p.kb_t0 + nt) * CHB + q * 1024);
+      }
 #pragma unroll
-      for (int u = 0; u < 2; ++u) bo[u] = *reinterpret_cast<const f32x4*>(p.b_out + nt * 32 + 16 * u + 4 * lg);
+      for (int u = 0; u < 2; ++u) {
+        if constexpr (A32) bo[u] = cp_load<f32x4>(p.b_out + nt * 32 + 16 * u, goff);
+        else bo[u] = *reinterpret_cast<const f32x4*>(p.b_out + nt * 32 + 16 * u + 4 * lg);
+      }
     };
     // lane-local epilogue: the two tiles are the lane's 8 slots of its chunk line of block kb_t0 + nt
     auto epilogue = [&](int nt, const auto& ac, const auto& rs) {
@@ -373,16 +459,19 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
       vec8 o[NPL];
       PT::split(v[0], v[1], o);
       if (live_z) {
+        if constexpr (A32) cp_pin(loff);
 #pragma unroll
-        for (int q = 0; q < NPL; ++q)
-          *reinterpret_cast<vec8*>(p.z + zbase + (size_t)(p.kb_t0 + nt) * CHB + q * 1024) = o[q];
+        for (int q = 0; q < NPL; ++q) {
+          if constexpr (A32) cp_store<vec8>(zrow + ((size_t)(p.kb_t0 + nt) * CHB + q * 1024), loff, o[q]);
+          else *reinterpret_cast<vec8*>(p.z + zbase + (size_t)(p.kb_t0 + nt) * CHB + q * 1024) = o[q];
+        }
       }
     };
     issue_res(0);
     // one output block: its MFMAs, then its epilogue
     auto block = [&](int nt) {
       const int buf = g & 1;
-      issue_n(p.Wout, p.ld_out, p.pl_out, min(nt + 1, p.nk_t - 1) * 32, st);
+      issue_n(p.Wout, p.ld_out, p.pl_out, min(nt + 1, p.nk_t - 1) * 32, noff, st);
       f32x4 acc[2] = {bo[0], bo[1]};                         // the output bias is the accumulators' starting value
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
@@ -463,6 +552,22 @@ int coupling_planes_ctx(const usf_coupling_planes_desc* d, const float* ctx, int
   const int64_t npl = d->format == USF_PLANES_F16X2 ? 2 : 3;
   const int64_t npanels = (d->M + 15) / 16;
   if (2 * npl * d->w_in_plane >= (1LL << 40)) { set_error("usf_coupling_planes: operand too large"); return -3; }
+  // the kernel adds 32-bit per-thread offsets to scalar bases: every buffer it addresses stays below 4 GiB (the largest plan,
+  // cfg4, builds 0.6 GB).  Checked from the geometry alone, in front of any launch.
+  {
+    const int64_t lim = 1LL << 32, chb = npl * 1024;
+    const bool z_big = d->z_nkb >= lim / chb || npanels * d->z_nkb * chb >= lim;
+    const bool h_big = (d->hidden_out[0] || d->hidden_out[1]) && npanels * 8 * chb >= lim;    // hidden_out / gate: 8 blocks per panel
+    auto w_big = [&](int64_t ld, int64_t plane, int64_t rows) {
+      return ld < 0 || plane < 0 || ld >= lim / (2 * rows) || plane >= lim / (2 * npl);
+    };
+    if (z_big || h_big || w_big(d->ldw_in, d->w_in_plane, 256) || (d->n_hidden > 1 && w_big(d->ldw_hid, d->w_hid_plane, 256)) ||
+        w_big(d->ldw_out, d->w_out_plane, 32 * d->nk_t)) {
+      set_error("usf_coupling_planes: a buffer of 4 GiB or more (z: %lld panels x %lld blocks x %lld bytes; weights: ld %lld / %lld / %lld)",
+                (long long)npanels, (long long)d->z_nkb, (long long)chb, (long long)d->ldw_in, (long long)d->ldw_hid, (long long)d->ldw_out);
+      return -3;
+    }
+  }
   CplPArgs a;
   a.z = reinterpret_cast<char*>(d->z); a.z_nkb = (int)d->z_nkb; a.npanels = (int)npanels; a.M = (int)d->M;
   a.kb_p0 = (int)d->kb_p0; a.nk_p = (int)d->nk_p; a.kb_t0 = (int)d->kb_t0; a.nk_t = (int)d->nk_t;
@@ -475,6 +580,10 @@ int coupling_planes_ctx(const usf_coupling_planes_desc* d, const float* ctx, int
   a.ld_hid = d->ldw_hid; a.pl_hid = d->w_hid_plane;
   a.Wout = reinterpret_cast<const char*>(d->W_out); a.ld_out = d->ldw_out; a.pl_out = d->w_out_plane; a.b_out = d->b_out;
   a.sign = d->sign; a.slope = d->slope; a.act = d->act; a.range_flag = d->range_flag;
+  // the max form of the activation (see activate): leaky ReLU, slope in [0, 1] and not -0 (max(+0, +0 * -0) would be +0 where
+  // the select gives -0).  Knob coupling_act_max = 0: always the select (A/B aid)
+  a.act_max = (d->act == USF_ACT_LEAKY_RELU && d->slope >= 0.0f && d->slope <= 1.0f && !__builtin_signbit(d->slope) &&
+               tuning("coupling_act_max", 1) != 0) ? 1 : 0;
   a.descend = (int)tuning("coupling_descend", 1);           // A/B aid: 0 = ascending
   a.ctx = ctx; a.ctx_stride = (int)ctx_stride; a.w_ctx = w_ctx; a.b_ctx = b_ctx;
   a.dbg = nullptr;
