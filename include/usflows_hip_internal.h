@@ -16,7 +16,7 @@
 extern "C" {
 #endif
 
-#define USF_INTERNAL_VERSION 5
+#define USF_INTERNAL_VERSION 6
 
 /* USF_INTERNAL_VERSION of the header the library was built from (host only, launches nothing). */
 int usf_internal_version(void);
@@ -71,7 +71,8 @@ int usf_internal_version(void);
  *
  * usf_sizeof_desc(kind) also reports sizeof(usf_mt_chunk|usf_grad_job|usf_psum_job) for kind 8|11|12 and
  * sizeof(usf_gated_norm_bwd_desc|usf_wgrad_job|usf_wreduce_job|usf_wplanes_job) for kind 13|14|15|16 and
- * sizeof(usf_adam_chunk|usf_grad_chunk|usf_conv_variant_query|usf_conv_variant) for kind 17|18|19|20.
+ * sizeof(usf_adam_chunk|usf_grad_chunk|usf_conv_variant_query|usf_conv_variant) for kind 17|18|19|20 and
+ * sizeof(usf_conv_wgrad_query|usf_conv_wgrad_info|usf_ln_bwd_info) for kind 21|22|23.
  */
 
 /*
@@ -220,9 +221,10 @@ int usf_conv_ctx_wgrad_f32(const float* dy, const float* ctx, int64_t ctx_stride
  *     db[co]             = sum_{b, p} dy[b, co, p]                                             (db may be NULL)
  *   with xin = in_act(x - pre_sub[ci]) * in_mul -- the input transforms of usf_conv2d_same_f32 (in_act, in_mul) and of
  *   usf_channel_affine_f32 (pre_sub), each optional -- and zeros outside the image.  Exact fp32 products and sums on
- *   v_mfma_f32_16x16x4_f32.  Served: cin, cout multiples of 16 up to 64 (kernel 3: cin * cout <= 1536), H * W <= 64, W >= 2, 16-byte
+ *   v_mfma_f32_16x16x4_f32.  Served: cin, cout multiples of 16 up to 64 (kernel 3: (cin / 16) * (cout / 16) <= 6 and neither of them 64), H * W <= 64, W >= 2, 16-byte
  *   aligned tensors; returns 1 (nothing written) for other shapes, 0 when done, < 0 on error.  workspace: at least
- *   usf_conv_wgrad_workspace(...) floats (0 = shape not served).  The DATA gradient of these layers is the forward entry point
+ *   usf_conv_wgrad_workspace(...) floats (0 = shape served neither with nor without in_mul; 64 -> 64 channels at kernel 1 and
+ *   57 .. 64 pixels are served without in_mul only).  The DATA gradient of these layers is the forward entry point
  *   on the flipped, transposed weight (usf_conv2d_same_f32 / usf_pointwise_conv_f32 / usf_channel_affine_f32).
  * usf_layernorm_channels_bwd_f32: backward of usf_layernorm_channels_f32 (same x, gamma, eps, act, slope):
  *     dx [B, C, P]; dgamma_dbeta [2 C] = (sum dy * xhat, sum dy); workspace >= usf_layernorm_channels_bwd_workspace(B, C, P) floats.
@@ -276,6 +278,41 @@ int usf_layernorm_channels_bwd_f32(const float* x, const float* dy, float* dx, i
                                    float eps, int32_t act, float slope, float* dgamma_dbeta, float* workspace,
                                    int64_t workspace_floats, usf_stream_t stream);
 int usf_gated_residual_bwd_f32(const float* dy, const float* vg, float* dvg, int64_t B, int64_t CP, usf_stream_t stream);
+
+/*
+ * usf_conv_wgrad_variant (internal version 6): which kernel a call of usf_conv_wgrad_f32 (or its deferred / plan forms)
+ * launches and how -- answered by the planning function the entry points themselves launch from (host only, nothing is
+ * launched, no tensor pointer exists).
+ * Query: B, cin, cout, H, W, ks, masked (1: the call passes in_mul); cus and blocks_per_cu: the device's compute units and the
+ * occupancy answer for the kernel instance (resident blocks per compute unit) -- 0 asks the device, as a launch does; > 0
+ * plans for the stated value (works without a GPU).  The tuning knobs in force are honoured as a launch honours them:
+ * conv_wgrad_rsplit (0: one wave per sample) and conv_wgrad_blocks (> 0: caps the grid; default 0 = the occupancy cap alone --
+ * a test aid: with it a batch of a few dozen samples gives every wave several samples).
+ * Answer: kernel 0 not served (the call returns 1), 1 the LDS-staged kernel conv_wgrad_kernel<CIT, COT, T>, 2 the direct 1 x 1
+ * kernel conv_wgrad_k1_kernel<CIT, COT>; rsplit waves per sample, grid blocks, lds_bytes; the staging geometry (row stride S,
+ * first pixel at base, first position read q0, channel stride CS, nch position chunks, nacc floats per partial slot,
+ * tab_floats of tables in front of the waves' images); the sum over the slots = 4 * blocks partial slots in `rounds` (1 or
+ * 2) rounds, the first of two with rows_used rows of `per` slots; max_samples_per_wave = ceil(B / (slots / rsplit));
+ * blocks_per_cu / cus: the values the plan was made with.  Returns 0 or -1 (null pointer).
+ * usf_layernorm_channels_bwd_variant: the same for usf_layernorm_channels_bwd_f32: kernel 1 = one thread per pixel
+ * (layernorm_channels_bwd_kernel<width, false>, width = CMAX 16 / 32 / 64), 2 = two lanes per pixel
+ * (layernorm_channels_bwd2_kernel<width>, width = CPT = C / 2 for C = 16, 32, 48, 64); 0: the sizes are refused.
+ */
+typedef struct usf_conv_wgrad_query {
+  int64_t B, cin, cout, H, W, ks;
+  int32_t masked, cus, blocks_per_cu, reserved;
+} usf_conv_wgrad_query;
+typedef struct usf_conv_wgrad_info {
+  int32_t kernel, CIT, COT, T, rsplit, blocks, lds_bytes;
+  int32_t S, base, q0, CS, nch, nacc, tab_floats;
+  int32_t slots, rounds, per, rows_used, max_samples_per_wave;
+  int32_t blocks_per_cu, cus, reserved;
+} usf_conv_wgrad_info;
+int usf_conv_wgrad_variant(const usf_conv_wgrad_query* q, usf_conv_wgrad_info* out);
+typedef struct usf_ln_bwd_info {
+  int32_t kernel, width, blocks, slots, rounds, per, rows_used, reserved;
+} usf_ln_bwd_info;
+int usf_layernorm_channels_bwd_variant(int64_t B, int64_t C, int64_t P, usf_ln_bwd_info* out);
 
 /* usf_conv2d_weight_planes_f32(transposed = 2) for MANY weights in one launch.  jobs / block_job are DEVICE arrays (as for
  * usf_partial_sum_jobs_f32): job j splits the fp32 weight w [cout, cin, ks, ks] into its planes followed by the planes of its

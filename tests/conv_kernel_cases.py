@@ -28,6 +28,26 @@ GUARD = 64                         # sentinel floats in front of and behind y
 SENTINEL_BITS = 0x65A5A5A5         # 9.78e22: no result of the table comes near it
 
 
+# the library's default of every tuning knob the case tables set (tests/test_image_grad_kernels_cpu.py holds them to the sources)
+KNOB_DEFAULTS = {"conv_wsp": 1, "conv_wreg": 1, "conv_small_s": 1, "conv_wgrad_rsplit": 1, "conv_wgrad_blocks": 0}
+
+
+class knobs:
+    """library tuning knobs for the duration of a block; the previous values afterwards (a knob nobody has set reads as its default)"""
+
+    def __init__(self, lib, kv):
+        self.lib, self.kv, self.old = lib, kv, {}
+
+    def __enter__(self):
+        for k, v in self.kv.items():
+            self.old[k] = self.lib.usf_get_tuning(k.encode(), KNOB_DEFAULTS[k])
+            assert self.lib.usf_set_tuning(k.encode(), int(v)) == 0, k
+
+    def __exit__(self, *exc):
+        for k, v in self.old.items():
+            assert self.lib.usf_set_tuning(k.encode(), int(v)) == 0, k
+
+
 def sentinel():
     return torch.tensor([SENTINEL_BITS], dtype=torch.int32).view(torch.float32).item()
 

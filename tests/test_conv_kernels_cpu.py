@@ -25,20 +25,7 @@ def lib():
     return _ext.load()
 
 
-class knobs:
-    """library tuning knobs for the duration of a block; the previous values afterwards"""
-
-    def __init__(self, lib, kv):
-        self.lib, self.kv, self.old = lib, kv, {}
-
-    def __enter__(self):
-        for k, v in self.kv.items():
-            self.old[k] = self.lib.usf_get_tuning(k.encode(), 1)
-            _ext.check(self.lib.usf_set_tuning(k.encode(), int(v)), "usf_set_tuning")
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            _ext.check(self.lib.usf_set_tuning(k.encode(), int(v)), "usf_set_tuning")
+knobs = K.knobs
 
 
 def _probe(lib):

@@ -22,22 +22,9 @@ def _ext():
     return _ext
 
 
-class knobs:
-    """library tuning knobs for the duration of a block; the previous values afterwards"""
-
-    def __init__(self, kv):
-        self.kv, self.old = kv, {}
-
-    def __enter__(self):
-        ext = _ext()
-        for k, v in self.kv.items():
-            self.old[k] = ext.load().usf_get_tuning(k.encode(), 1)
-            ext.check(ext.load().usf_set_tuning(k.encode(), int(v)), "usf_set_tuning")
-
-    def __exit__(self, *exc):
-        ext = _ext()
-        for k, v in self.old.items():
-            ext.check(ext.load().usf_set_tuning(k.encode(), int(v)), "usf_set_tuning")
+def knobs(kv):
+    """conv_kernel_cases.knobs on the loaded library"""
+    return K.knobs(_ext().load(), kv)
 
 
 def _rows_nan(t, roll=0, lead=0):

@@ -195,8 +195,8 @@ def test_abi_of_the_new_entry_points():
     hdr = open(os.path.join(ROOT, "include", "usflows_hip_internal.h")).read()
     pub = open(os.path.join(ROOT, "include", "usflows_hip.h")).read()
     lib = _ext.load()
-    assert int(re.search(r"^#define USF_INTERNAL_VERSION (\d+)", hdr, flags=re.M).group(1)) == _ext.USF_INTERNAL_VERSION == 5
-    assert lib.usf_internal_version() == 5
+    assert int(re.search(r"^#define USF_INTERNAL_VERSION (\d+)", hdr, flags=re.M).group(1)) == _ext.USF_INTERNAL_VERSION == 6
+    assert lib.usf_internal_version() == 6
     assert int(re.search(r"^#define USF_ABI_VERSION (\d+)", pub, flags=re.M).group(1)) == _ext.USF_ABI_VERSION == lib.usf_abi_version() == 36
     for name in ("usf_coupling_additive_vctx_f32", "usf_coupling_additive_vctx_variant"):
         assert re.search(rf"\b{name}\s*\(", hdr) and name in _ext.INTERNAL_SYMBOLS and name not in pub and hasattr(lib, name)

@@ -4,7 +4,7 @@ loads the library or launches anything; ``_ext.py`` does, and re-exports every n
 import ctypes as C
 
 USF_ABI_VERSION = 36          # include/usflows_hip.h
-USF_INTERNAL_VERSION = 5      # include/usflows_hip_internal.h
+USF_INTERNAL_VERSION = 6      # include/usflows_hip_internal.h
 USF_MAX_HIDDEN = 4
 
 ACT_NONE, ACT_LEAKY_RELU, ACT_GATE = 0, 1, 2
@@ -123,6 +123,24 @@ class ConvVariant(C.Structure):
                 ("max_mHW", C.c_int32), ("max_mW", C.c_int32), ("max_mSE", C.c_int32), ("max_mSO", C.c_int32)]
 
 
+class ConvWgradQuery(C.Structure):
+    """usf_conv_wgrad_query: one call of usf_conv_wgrad_f32, as usf_conv_wgrad_variant is asked about it"""
+    _fields_ = [("B", C.c_int64), ("cin", C.c_int64), ("cout", C.c_int64), ("H", C.c_int64), ("W", C.c_int64), ("ks", C.c_int64),
+                ("masked", C.c_int32), ("cus", C.c_int32), ("blocks_per_cu", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ConvWgradInfo(C.Structure):
+    """usf_conv_wgrad_info: the kernel, instantiation, grid, staging geometry and reduction such a call launches"""
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "CIT", "COT", "T", "rsplit", "blocks", "lds_bytes", "S", "base", "q0", "CS", "nch",
+                                         "nacc", "tab_floats", "slots", "rounds", "per", "rows_used", "max_samples_per_wave",
+                                         "blocks_per_cu", "cus", "reserved")]
+
+
+class LnBwdInfo(C.Structure):
+    """usf_ln_bwd_info: the kernel, its width (CMAX or CPT), grid and reduction usf_layernorm_channels_bwd_f32 launches"""
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "width", "blocks", "slots", "rounds", "per", "rows_used", "reserved")]
+
+
 CONV_ENTRIES = {"plain": 0, "ctx": 1, "res": 2, "gate_mul": 3, "gate_add": 4, "gated": 5}   # USF_CONV_ENTRY_*
 
 
@@ -213,7 +231,7 @@ class GradJob(C.Structure):
 SIZEOF_KINDS = {OP_LINEAR: LinearDesc, OP_COUPLING: CouplingDesc, 0: Op, 3: LuPrepDesc, 4: PackJob, OP_PACK_PLANES: PackPlanesDesc,
                 OP_GEMM_PLANES: GemmPlanesDesc, OP_COUPLING_PLANES: CouplingPlanesDesc, 8: MtChunk, OP_GATED_NORM: GatedNormDesc,
                 OP_CALL: CallDesc, 11: GradJob, 12: PsumJob, 13: GatedNormBwdDesc, 14: WgradJob, 15: WReduceJob, 16: WPlanesJob, 17: AdamChunk, 18: GradChunk,
-                19: ConvVariantQuery, 20: ConvVariant}
+                19: ConvVariantQuery, 20: ConvVariant, 21: ConvWgradQuery, 22: ConvWgradInfo, 23: LnBwdInfo}
 
 
 # every symbol include/usflows_hip.h declares (the stable public ABI): (restype, argtypes)
@@ -298,6 +316,8 @@ INTERNAL_SYMBOLS = {
     "usf_conv_ctx_wgrad_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_void_p]),
     "usf_conv2d_same_gate_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [C.c_void_p, _fp, C.c_float, _fp, _fp, C.c_void_p]),
     "usf_conv2d_same_variant": (C.c_int, [C.POINTER(ConvVariantQuery), C.POINTER(ConvVariant)]),
+    "usf_conv_wgrad_variant": (C.c_int, [C.POINTER(ConvWgradQuery), C.POINTER(ConvWgradInfo)]),
+    "usf_layernorm_channels_bwd_variant": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(LnBwdInfo)]),
     "usf_conv_wgrad_workspace": (C.c_int64, [C.c_int64] * 6),
     "usf_conv_wgrad_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [_fp, _fp, C.c_int32, C.c_float, _fp, _fp, _fp, C.c_int64,
                                      C.c_void_p]),

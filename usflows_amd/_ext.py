@@ -8,6 +8,7 @@ for gfx950.  There is NO fallback: if the library is missing or a call fails, a
 from __future__ import annotations
 
 import ctypes as C
+import gc
 import math
 import os
 import struct
@@ -23,7 +24,7 @@ from ._abi import (  # noqa: E402,F401  -- the declarations, re-exported: caller
     BASE_LPNORM1, BASE_LPNORM2, BASE_LPNORMINF, BASE_ROWSUM, NORM_LOGNORMAL, NORM_GAMMA, NORM_RAW_PARAMS, NORM_WEIBULL, NORM_HALFNORMAL, NORM_CHI, RADIAL_MAX_K, OP_LINEAR,
     OP_COUPLING, OP_PACK_PLANES, OP_GEMM_PLANES, OP_COUPLING_PLANES, OP_GATED_NORM, OP_CALL, PLANES_BF16X3, PLANES_F16X2, CALL_FNS,
     FN_COUPLING_PLANES_CTX, FN_COUPLING_VCTX, VCTX_MAX,
-    _fp, LinearDesc, CouplingDesc, PackPlanesDesc, GemmPlanesDesc, CouplingPlanesDesc, MtChunk, AdamChunk, GradChunk, ConvVariantQuery, ConvVariant, CONV_ENTRIES, GatedNormDesc, GatedNormBwdDesc,
+    _fp, LinearDesc, CouplingDesc, PackPlanesDesc, GemmPlanesDesc, CouplingPlanesDesc, MtChunk, AdamChunk, GradChunk, ConvVariantQuery, ConvVariant, ConvWgradQuery, ConvWgradInfo, LnBwdInfo, CONV_ENTRIES, GatedNormDesc, GatedNormBwdDesc,
     CallDesc, _OpUnion, Op, LuPrepDesc, PackJob, PsumJob, WgradJob, WReduceJob, WPlanesJob, GradJob, SIZEOF_KINDS, PUBLIC_SYMBOLS,
     INTERNAL_SYMBOLS, SYMBOLS)
 
@@ -605,6 +606,23 @@ def conv2d_same_variant(entry, B, cin, cout, H, W, ks=3, aligned=True, cus=0) ->
     return {name: int(getattr(out, name)) for name, _ in ConvVariant._fields_}
 
 
+def conv_wgrad_variant(B, cin, cout, H, W, ks=3, masked=False, cus=0, blocks_per_cu=0) -> dict:
+    """usf_conv_wgrad_variant: which kernel usf_conv_wgrad_f32 launches for these sizes and how, as a dict of the answer's fields
+    (kernel 0: not served); cus / blocks_per_cu > 0 plan for that device answer (no GPU needed), 0 asks the device"""
+    q = ConvWgradQuery(int(B), int(cin), int(cout), int(H), int(W), int(ks), int(bool(masked)), int(cus), int(blocks_per_cu), 0)
+    out = ConvWgradInfo()
+    check(load().usf_conv_wgrad_variant(C.byref(q), C.byref(out)), "usf_conv_wgrad_variant")
+    return {name: int(getattr(out, name)) for name, _ in ConvWgradInfo._fields_ if name != "reserved"}
+
+
+def layernorm_channels_bwd_variant(B, C_, P) -> dict:
+    """usf_layernorm_channels_bwd_variant: the kernel (1 / 2), its width (CMAX / CPT), grid and reduction rounds of
+    usf_layernorm_channels_bwd_f32 for these sizes (kernel 0: refused)"""
+    out = LnBwdInfo()
+    check(load().usf_layernorm_channels_bwd_variant(int(B), int(C_), int(P), C.byref(out)), "usf_layernorm_channels_bwd_variant")
+    return {name: int(getattr(out, name)) for name, _ in LnBwdInfo._fields_ if name != "reserved"}
+
+
 def pointwise_conv_supported(cin: int, cout: int, gated: bool = False) -> bool:
     return bool(load().usf_pointwise_conv_supported(int(cin), int(cout), int(bool(gated))))
 
@@ -717,6 +735,30 @@ class deferred_sums_scope:
     def __exit__(self, *exc):
         with _psum.lock:
             _psum.scope -= 1
+        return False
+
+
+class capture_without_gc:
+    """``with capture_without_gc(), torch.cuda.graph(g): ...`` -- a stream capture during which Python's cyclic garbage collector
+    does not run.  A dead flow is cyclic garbage (its LU layers' gradient hooks refer back to the module) and owns the
+    ``torch.cuda.CUDAGraph`` objects of its replayed steps; only a collection destroys them.  On ROCm the destructor of a
+    CUDAGraph synchronises the device, which a capture in progress forbids: the error is thrown inside the destructor and the
+    process aborts.  torch.cuda.graph no longer collects before it captures (it did up to torch 2.9), so whether a collection
+    falls into a capture depended on how many objects the process had allocated before.  The garbage is collected HERE, before the
+    capture begins (which also returns its device memory), and the collector is switched back on behind the capture.
+    gc.disable() holds for the whole process, not for this thread: while one thread captures, no thread collects (what the guard
+    is for: the autograd engine's worker threads run inside the capture too); two threads that capture at once may switch it
+    back on while the slower one still captures -- Flow.fit's captures are serialised by capture_tables' lock."""
+
+    def __enter__(self):
+        self.was = gc.isenabled()
+        gc.collect()
+        gc.disable()
+        return self
+
+    def __exit__(self, *exc):
+        if self.was:
+            gc.enable()
         return False
 
 

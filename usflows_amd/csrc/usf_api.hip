@@ -154,6 +154,8 @@ int layernorm_channels_bwd(const float* x, const float* dy, float* dx, int64_t B
                            int32_t act, float slope, float* dgamma, float* dbeta, float* workspace, int64_t workspace_floats,
                            hipStream_t stream);
 int gated_residual_bwd(const float* dy, const float* vg, float* dvg, int64_t B, int64_t CP, hipStream_t stream);
+int conv_wgrad_variant(const usf_conv_wgrad_query* q, usf_conv_wgrad_info* out);
+int layernorm_channels_bwd_variant(int64_t B, int64_t C, int64_t P, usf_ln_bwd_info* out);
 int conv2d_weight_planes(const float* w, void* planes, int64_t cin, int64_t cout, int64_t ks, int32_t transposed, hipStream_t stream);
 int sophiag_step(const usf_mt_chunk* chunks, int64_t n_chunks, float decay, float beta1, float one_minus_beta1, float rho_bs,
                  float neg_lr, int32_t maximize, hipStream_t stream);
@@ -240,6 +242,9 @@ int usf_sizeof_desc(int32_t kind) {
     case 18: return (int)sizeof(usf_grad_chunk);
     case 19: return (int)sizeof(usf_conv_variant_query);
     case 20: return (int)sizeof(usf_conv_variant);
+    case 21: return (int)sizeof(usf_conv_wgrad_query);
+    case 22: return (int)sizeof(usf_conv_wgrad_info);
+    case 23: return (int)sizeof(usf_ln_bwd_info);
     default: return -1;
   }
 }
@@ -451,6 +456,10 @@ int usf_layernorm_channels_bwd_f32(const float* x, const float* dy, float* dx, i
 int usf_conv2d_weight_planes_f32(const float* w, void* planes, int64_t cin, int64_t cout, int64_t ks, int32_t transposed,
                                  usf_stream_t stream) {
   return usf::conv2d_weight_planes(w, planes, cin, cout, ks, transposed, (hipStream_t)stream);
+}
+int usf_conv_wgrad_variant(const usf_conv_wgrad_query* q, usf_conv_wgrad_info* out) { return usf::conv_wgrad_variant(q, out); }
+int usf_layernorm_channels_bwd_variant(int64_t B, int64_t C, int64_t P, usf_ln_bwd_info* out) {
+  return usf::layernorm_channels_bwd_variant(B, C, P, out);
 }
 int usf_gated_residual_bwd_f32(const float* dy, const float* vg, float* dvg, int64_t B, int64_t CP, usf_stream_t stream) {
   return usf::gated_residual_bwd(dy, vg, dvg, B, CP, (hipStream_t)stream);

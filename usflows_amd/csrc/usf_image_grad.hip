@@ -384,14 +384,24 @@ __global__ __launch_bounds__(256) void partial_sum_jobs_kernel(const usf_psum_jo
 
 constexpr int kReduceRows = 64;        // scratch rows of the two-round sum (workspace: kReduceRows * n floats behind the slots)
 
+// the rounds of the sum of `nparts` slots: 1 up to 64 slots; else 2: a first round of `used` rows (<= kReduceRows) of `per` slots
+// each, the last row possibly shorter.  Every caller below -- and the probes -- take the geometry from here.
+static int reduce_rounds(int nparts, int& per, int& used) {
+  per = nparts;
+  used = 1;
+  if (nparts <= 64) return 1;
+  const int rows = nparts / 16 < kReduceRows ? (nparts + 15) / 16 : kReduceRows;
+  per = (nparts + rows - 1) / rows;
+  used = (nparts + per - 1) / per;
+  return 2;
+}
+
 // sum of `nparts` slots of n floats: one round up to 64 slots, else a first round into <= 64 rows of scratch
 static int reduce_partials(const float* part, int nparts, int n, float* scratch, float* out, float* out2, int mode, int cin, int cout,
                            int CIT, int T, int ntile, hipStream_t stream, const char* what) {
   const unsigned gx = (unsigned)((n + 63) / 64);
-  if (nparts > 64) {
-    const int rows = nparts / 16 < kReduceRows ? (nparts + 15) / 16 : kReduceRows;
-    const int per = (nparts + rows - 1) / rows;
-    const int used = (nparts + per - 1) / per;
+  int per, used;
+  if (reduce_rounds(nparts, per, used) == 2) {
     hipLaunchKernelGGL(partial_sum_kernel, dim3(gx, (unsigned)used), dim3(256), 0, stream, part, nparts, per, n, scratch,
                        (float*)nullptr, 0, 0, 0, 0, 0, 0);
     part = scratch;
@@ -409,10 +419,8 @@ int sum_slots(const float* part, int nparts, int n, float* scratch, float* out, 
   if (!job) return reduce_partials(part, nparts, n, scratch, out, nullptr, 0, 0, 0, 0, 0, 0, stream, what);
   job[0] = usf_psum_job{};
   job[1] = usf_psum_job{};
-  if (nparts > 64) {
-    const int rows = nparts / 16 < kReduceRows ? (nparts + 15) / 16 : kReduceRows;
-    const int per = (nparts + rows - 1) / rows;
-    const int used = (nparts + per - 1) / per;
+  int per, used;
+  if (reduce_rounds(nparts, per, used) == 2) {
     usf_psum_job& a0 = job[0];
     a0.part = part; a0.out = scratch; a0.nparts = nparts; a0.n = n; a0.per = per; a0.rows = used;
     a0.vec4 = (n % 4 == 0 && aligned16(part) && aligned16(scratch)) ? 1 : 0;
@@ -471,11 +479,24 @@ int wgrad_blocks_per_cu(int CIT, int COT, int T, int lds_bytes) {
   return nb;
 }
 
+// is there an instance of the LDS-staged kernel for these tiles?  (16 -> 64 and 64 -> 16 channels at kernel 3 pass the register
+// rule below, CIT * COT = 4, and have none)
+bool wgrad_has_instance(int CIT, int COT, int T) {
+#define USF_WG_HAS(CIT_, COT_, T_) if (CIT == CIT_ && COT == COT_ && T == T_) return true;
+  USF_WG_INSTANCES(USF_WG_HAS)
+#undef USF_WG_HAS
+  return false;
+}
+
 struct WgPlan {
   int CIT, COT, T, S, base, CS, nch, q0, nacc, lds_bytes, blocks, tab_floats, rsplit;
   bool direct;               // kernel 1 without an input mask: conv_wgrad_k1_kernel
+  int per_cu, cus;           // the occupancy answer (before the cap of 4 / 8) and the compute units the plan was made for
 };
-bool wgrad_plan(int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks, bool masked, WgPlan& pl) {
+// cus / blocks_per_cu: the device's compute units and the occupancy answer for the instance; <= 0: ask the device (what every
+// launch does -- usf_conv_wgrad_variant may state them instead, so the plan can be asked without a GPU)
+bool wgrad_plan(int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks, bool masked, int cus, int blocks_per_cu,
+                WgPlan& pl) {
   if (B <= 0 || cin <= 0 || cout <= 0 || (cin & 15) || (cout & 15) || H <= 0 || W < 2 || H * W > 64 || (ks != 1 && ks != 3))
     return false;                                                // (W >= 2: the index tables divide by W and H * W with 32-bit magic numbers)
   pl.CIT = (int)(cin / 16);
@@ -506,41 +527,76 @@ bool wgrad_plan(int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int6
   pl.nacc = pl.COT * pl.CIT * pl.T * 256 + pl.COT * 16;
   pl.direct = (ks == 1 && !masked && H * W > 48);
   pl.rsplit = 1;
+  const int64_t blocks_knob = tuning("conv_wgrad_blocks", 0);    // tuning aid: > 0 caps the grid (0: the occupancy cap alone)
   if (pl.direct) {
     pl.lds_bytes = 0;
-    int per_cu = wgrad_k1_blocks_per_cu(pl.CIT, pl.COT);
+    pl.tab_floats = 0;
+    int per_cu = blocks_per_cu > 0 ? blocks_per_cu : wgrad_k1_blocks_per_cu(pl.CIT, pl.COT);
+    pl.per_cu = per_cu;
     if (per_cu > 8) per_cu = 8;
     int64_t blocks = (B + 3) / 4;
-    const int64_t cap = (int64_t)device_cu_count() * per_cu;
-    pl.blocks = (int)(blocks > cap ? cap : blocks);
+    pl.cus = cus > 0 ? cus : device_cu_count();
+    const int64_t cap = (int64_t)pl.cus * per_cu;
+    if (blocks > cap) blocks = cap;
+    if (blocks_knob > 0 && blocks > blocks_knob) blocks = blocks_knob;
+    pl.blocks = (int)blocks;
     return true;
   }
   pl.tab_floats = (pl.CIT * 1024 + pl.COT * 1024) / 2 + pl.CIT * 1024 + (int)cin;      // index tables (u16), mask, pre_sub
   pl.tab_floats = (pl.tab_floats + 3) & ~3;
   pl.lds_bytes = (pl.tab_floats + 4 * ((int)(cin + cout) * pl.CS + 4)) * 4;
   if (pl.lds_bytes > 160 * 1024) return false;
-  int per_cu = wgrad_blocks_per_cu(pl.CIT, pl.COT, pl.T, pl.lds_bytes);
+  if (!wgrad_has_instance(pl.CIT, pl.COT, pl.T)) return false;   // (the occupancy query below says the same: 0)
+  int per_cu = blocks_per_cu > 0 ? blocks_per_cu : wgrad_blocks_per_cu(pl.CIT, pl.COT, pl.T, pl.lds_bytes);
   if (per_cu <= 0) return false;
+  pl.per_cu = per_cu;
   if (per_cu > 4) per_cu = 4;                                    // (more partial slots than that buy nothing)
-  const int64_t cap = (int64_t)device_cu_count() * per_cu;
+  pl.cus = cus > 0 ? cus : device_cu_count();
+  const int64_t cap = (int64_t)pl.cus * per_cu;
   // few samples: 2 or 4 waves per sample (position chunks dealt over them) while that still fits one round of blocks
   const int rs_on = (int)tuning("conv_wgrad_rsplit", 1);   // tuning aid: 0 = one wave per sample
   if (rs_on && pl.T == 9) {
-    if (B <= 64 && B <= cap && pl.nch >= 8) pl.rsplit = 4;          // (<= 256 partial slots: still one reduction round)
+    if (B <= 64 && B <= cap && pl.nch >= 8) pl.rsplit = 4;          // (<= 256 partial slots; above 64 of them the sum takes two rounds)
     else if (B <= 128 && B <= 2 * cap && pl.nch >= 4) pl.rsplit = 2;
   }
   int64_t blocks = (B * pl.rsplit + 3) / 4;
   if (blocks > cap) blocks = cap;
+  if (blocks_knob > 0 && blocks > blocks_knob) blocks = blocks_knob;
   pl.blocks = (int)blocks;
   return true;
 }
 }  // namespace
 
+// usf_conv_wgrad_variant: the plan above, asked instead of launched
+int conv_wgrad_variant(const usf_conv_wgrad_query* q, usf_conv_wgrad_info* o) {
+  if (!q || !o) { set_error("usf_conv_wgrad_variant: null pointer"); return -1; }
+  *o = usf_conv_wgrad_info();
+  WgPlan pl;
+  if (!wgrad_plan(q->B, q->cin, q->cout, q->H, q->W, q->ks, q->masked != 0, q->cus, q->blocks_per_cu, pl)) return 0;
+  o->kernel = pl.direct ? 2 : 1;
+  o->CIT = pl.CIT; o->COT = pl.COT; o->T = pl.T; o->rsplit = pl.rsplit; o->blocks = pl.blocks; o->lds_bytes = pl.lds_bytes;
+  o->S = pl.S; o->base = pl.base; o->q0 = pl.q0; o->CS = pl.CS; o->nch = pl.nch; o->nacc = pl.nacc; o->tab_floats = pl.tab_floats;
+  o->slots = pl.blocks * 4;
+  int per, used;
+  o->rounds = reduce_rounds(o->slots, per, used);
+  o->per = per;
+  o->rows_used = used;
+  const int64_t in_flight = (int64_t)pl.blocks * 4 / pl.rsplit;       // samples the grid takes per round of its waves
+  o->max_samples_per_wave = (int32_t)((q->B + in_flight - 1) / in_flight);
+  o->blocks_per_cu = pl.per_cu;
+  o->cus = pl.cus;
+  return 0;
+}
+
 int64_t conv_wgrad_workspace(int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks) {
   // (the masked form of kernel 1 needs at least the slots of the direct form: both sized here)
+  // A form that is not served needs nothing: 64 + 64 channels at 57 .. 64 pixels run on the direct kernel while their masked
+  // form exceeds the LDS -- answering 0 for both made every unmasked call there fail with "workspace too small".
   WgPlan pl, pm;
-  if (!wgrad_plan(B, cin, cout, H, W, ks, false, pl) || !wgrad_plan(B, cin, cout, H, W, ks, true, pm)) return 0;
-  return ((int64_t)(pl.blocks > pm.blocks ? pl.blocks : pm.blocks) * 4 + kReduceRows) * pl.nacc;
+  const bool ok = wgrad_plan(B, cin, cout, H, W, ks, false, 0, 0, pl), okm = wgrad_plan(B, cin, cout, H, W, ks, true, 0, 0, pm);
+  if (!ok && !okm) return 0;
+  const int blocks = (ok ? pl.blocks : 0) > (okm ? pm.blocks : 0) ? pl.blocks : pm.blocks;
+  return ((int64_t)blocks * 4 + kReduceRows) * (ok ? pl.nacc : pm.nacc);
 }
 
 int conv_wgrad(const float* x, const float* dy, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
@@ -550,7 +606,7 @@ int conv_wgrad(const float* x, const float* dy, int64_t B, int64_t cin, int64_t 
   if (job) job[0].nparts = job[1].nparts = 0;
   if (wjob) wjob->blocks = 0;
   if (B < 0) { set_error("usf_conv_wgrad_f32: bad sizes"); return -2; }
-  if (B == 0 || !wgrad_plan(B, cin, cout, H, W, ks, in_mul != nullptr, pl)) {
+  if (B == 0 || !wgrad_plan(B, cin, cout, H, W, ks, in_mul != nullptr, 0, 0, pl)) {
     if (B == 0) { set_error("usf_conv_wgrad_f32: empty batch"); return -2; }
     return 1;                                                     // shape not served
   }
@@ -602,10 +658,8 @@ int conv_wgrad(const float* x, const float* dy, int64_t B, int64_t cin, int64_t 
     const float* src = workspace;
     float* scratch = workspace + (int64_t)pl.blocks * 4 * pl.nacc;
     job[0].nparts = 0;
-    if (nparts > 64) {
-      const int rows = nparts / 16 < kReduceRows ? (nparts + 15) / 16 : kReduceRows;
-      const int per = (nparts + rows - 1) / rows;
-      const int used = (nparts + per - 1) / per;
+    int per, used;
+    if (reduce_rounds(nparts, per, used) == 2) {
       usf_psum_job& a0 = job[0];
       a0.part = workspace; a0.out = scratch; a0.out2 = nullptr; a0.nparts = nparts; a0.n = pl.nacc; a0.mode = 0; a0.cin = a0.cout = 0;
       a0.CIT = a0.T = a0.ntile = 0; a0.first_block = 0; a0.per = per; a0.rows = used;
@@ -828,33 +882,58 @@ __global__ __launch_bounds__(256) void layernorm_channels_bwd2_kernel(const floa
   }
 }
 
-int64_t layernorm_channels_bwd_workspace(int64_t B, int64_t C, int64_t P) {
-  if (B <= 0 || C <= 0 || C > 64 || P <= 0) return 0;
+// which kernel serves C channels and on how many blocks: the launch below and usf_layernorm_channels_bwd_variant read it here
+struct LnBwdPlan { int kernel, width, blocks; };     // kernel 1: one thread per pixel, width = CMAX; 2: two lanes per pixel, width = CPT
+static bool ln_bwd_plan(int64_t B, int64_t C, int64_t P, LnBwdPlan& pl) {
+  if (B <= 0 || C <= 0 || C > 64 || P <= 0) return false;
   int64_t blocks = (B * P + 255) / 256;
   if (blocks > 2048) blocks = 2048;
-  return (blocks * 4 + kReduceRows) * 2 * C;
+  pl.blocks = (int)blocks;
+  if (C % 16 == 0) { pl.kernel = 2; pl.width = (int)(C / 2); }
+  else { pl.kernel = 1; pl.width = C < 16 ? 16 : (C < 32 ? 32 : 64); }
+  return true;
+}
+
+int64_t layernorm_channels_bwd_workspace(int64_t B, int64_t C, int64_t P) {
+  LnBwdPlan pl;
+  if (!ln_bwd_plan(B, C, P, pl)) return 0;
+  return ((int64_t)pl.blocks * 4 + kReduceRows) * 2 * C;
+}
+
+int layernorm_channels_bwd_variant(int64_t B, int64_t C, int64_t P, usf_ln_bwd_info* o) {
+  if (!o) { set_error("usf_layernorm_channels_bwd_variant: null pointer"); return -1; }
+  *o = usf_ln_bwd_info();
+  LnBwdPlan pl;
+  if (!ln_bwd_plan(B, C, P, pl)) return 0;
+  o->kernel = pl.kernel; o->width = pl.width; o->blocks = pl.blocks; o->slots = pl.blocks * 4;
+  int per, used;
+  o->rounds = reduce_rounds(o->slots, per, used);
+  o->per = per;
+  o->rows_used = used;
+  return 0;
 }
 
 int layernorm_channels_bwd(const float* x, const float* dy, float* dx, int64_t B, int64_t C, int64_t P, const float* gamma, float eps,
                            int32_t act, float slope, float* dgamma, float* dbeta, float* workspace, int64_t workspace_floats,
                            hipStream_t stream) {
-  if (B <= 0 || C <= 0 || P <= 0 || C > 64) { set_error("usf_layernorm_channels_bwd_f32: bad sizes (C must be 1..64, B > 0)"); return -2; }
+  LnBwdPlan pl;
+  if (!ln_bwd_plan(B, C, P, pl)) { set_error("usf_layernorm_channels_bwd_f32: bad sizes (C must be 1..64, B > 0)"); return -2; }
   if (!x || !dy || !dx || !gamma || !dgamma || !dbeta || !workspace) { set_error("usf_layernorm_channels_bwd_f32: null pointer"); return -1; }
   if (dgamma + C != dbeta) { set_error("usf_layernorm_channels_bwd_f32: dbeta must follow dgamma (one [2 C] buffer)"); return -2; }
   if (act != USF_ACT_NONE && act != USF_ACT_LEAKY_RELU) { set_error("usf_layernorm_channels_bwd_f32: bad act"); return -2; }
   const int64_t need = layernorm_channels_bwd_workspace(B, C, P);
   if (workspace_floats < need) { set_error("usf_layernorm_channels_bwd_f32: workspace too small"); return -2; }
   const int64_t BP = B * P;
-  const int blocks = (int)(need / (2 * C) - kReduceRows) / 4;
+  const int blocks = pl.blocks;
   const dim3 g((unsigned)blocks), b(256);
 #define USF_LNB(CM_, FULL_) hipLaunchKernelGGL((layernorm_channels_bwd_kernel<CM_, FULL_>), g, b, 0, stream, x, dy, dx, BP, (int)C, P, gamma, eps, act, slope, workspace)
 #define USF_LNB2(CPT_) hipLaunchKernelGGL((layernorm_channels_bwd2_kernel<CPT_>), g, b, 0, stream, x, dy, dx, BP, P, gamma, eps, act, slope, workspace)
-  if (C == 16) USF_LNB2(8);
-  else if (C == 32) USF_LNB2(16);
-  else if (C == 48) USF_LNB2(24);
-  else if (C == 64) USF_LNB2(32);
-  else if (C < 16) USF_LNB(16, false);
-  else if (C < 32) USF_LNB(32, false);
+  if (pl.kernel == 2 && pl.width == 8) USF_LNB2(8);
+  else if (pl.kernel == 2 && pl.width == 16) USF_LNB2(16);
+  else if (pl.kernel == 2 && pl.width == 24) USF_LNB2(24);
+  else if (pl.kernel == 2) USF_LNB2(32);
+  else if (pl.width == 16) USF_LNB(16, false);
+  else if (pl.width == 32) USF_LNB(32, false);
   else USF_LNB(64, false);
 #undef USF_LNB
 #undef USF_LNB2

@@ -913,7 +913,7 @@ class FlowEngine(FlatPlanMixin, PlanesPlanMixin):
             else:
                 torch.cuda.synchronize(x.device)
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
+                with _ext.capture_without_gc(), torch.cuda.graph(g):
                     self._execute_plain(plan, xs, os_, None)
                 plan["graph"] = g
                 g.replay()

@@ -341,7 +341,7 @@ class FitMixin:
                     o.defer_uploads(True)
                 tables = _ext.capture_tables(sample.device)          # (job tables of launches inside the capture: _ext.conv_wgrad)
                 try:
-                    with tables, (torch.cuda.graph(graph, stream=cur) if on_own else torch.cuda.graph(graph)):
+                    with _ext.capture_without_gc(), tables, (torch.cuda.graph(graph, stream=cur) if on_own else torch.cuda.graph(graph)):
                         sl = body()
                 finally:
                     for o in owners:

@@ -36,8 +36,15 @@ def _gate_inplace(d: torch.Tensor, h: torch.Tensor, act) -> None:
     _ext.act_grad(d, h, M=B, H=n, ldd=n, ldh=n, act=act[0], slope=act[1])
 
 
-def conv_shape_ok(conv, B: int, H: int, W: int) -> bool:
-    """forward, data gradient (the transposed shape) and weight gradient of this nn.Conv2d at [B, cin, H, W] are all served"""
+def wgrad_served(B: int, cin: int, cout: int, H: int, W: int, ks: int, masked: bool) -> bool:
+    """does usf_conv_wgrad_f32 serve this call -- with an input mask (in_mul) or without?  The two forms differ: 64 -> 64
+    channels at kernel 1 and 57 .. 64 pixels run without a mask only (usf_conv_wgrad_workspace > 0 says that ONE form is served)"""
+    return _ext.conv_wgrad_variant(max(B, 1), cin, cout, H, W, ks, masked)["kernel"] != 0
+
+
+def conv_shape_ok(conv, B: int, H: int, W: int, masked: bool = False) -> bool:
+    """forward, data gradient (the transposed shape) and weight gradient of this nn.Conv2d at [B, cin, H, W] are all served;
+    masked: the layer may be handed an input mask (the first convolution of a coupling's conditioner)"""
     if not isinstance(conv, torch.nn.Conv2d):
         return False
     k = conv.kernel_size
@@ -50,7 +57,7 @@ def conv_shape_ok(conv, B: int, H: int, W: int) -> bool:
     lib = _ext.load()
     cin, cout = conv.in_channels, conv.out_channels
     return (lib.usf_conv2d_same_fits(cin, cout, H, W, k[0]) >= 2 and lib.usf_conv2d_same_fits(cout, cin, H, W, k[0]) >= 2
-            and lib.usf_conv_wgrad_workspace(max(B, 1), cin, cout, H, W, k[0]) > 0)
+            and wgrad_served(B, cin, cout, H, W, k[0], masked))
 
 
 def _weight_planes(w, want_transposed: bool, param=None):
@@ -358,7 +365,7 @@ def conv_ctx_shape_ok(conv, B: int, H: int, W: int) -> bool:
     lib = _ext.load()
     C, cout = conv.in_channels - 1, conv.out_channels
     return (lib.usf_conv2d_same_fits(C, cout, H, W, k[0]) >= 2 and lib.usf_conv2d_same_fits(cout, C, H, W, k[0]) >= 2
-            and lib.usf_conv_wgrad_workspace(max(B, 1), C, cout, H, W, k[0]) > 0)
+            and wgrad_served(B, C, cout, H, W, k[0], True))            # (the first convolution: it may be handed the coupling's mask)
 
 
 class Pointwise(torch.autograd.Function):

@@ -483,7 +483,7 @@ class LayerLoopMixin:
                             self._layer_loop_log_prob(static_x, static_c)
                     torch.cuda.current_stream(x.device).wait_stream(side)
                     g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
+                    with _ext.capture_without_gc(), torch.cuda.graph(g):
                         static_out = self._layer_loop_log_prob(static_x, static_c)
                 hit = cache[key] = (ver, g, static_x, static_out, static_c)
                 if len(cache) > 8:

@@ -201,7 +201,7 @@ class _ConvStack(nn.Module):
             m = mods[k]
             nxt = mods[k + 1] if k + 1 < len(mods) else None
             if isinstance(m, nn.Conv2d):
-                if m.in_channels != C or not it.conv_shape_ok(m, B, H, W):
+                if m.in_channels != C or not it.conv_shape_ok(m, B, H, W, masked=(k == 0)):   # (the first one may get the coupling's mask)
                     return False
                 C = m.out_channels
                 after = mods[k + 2] if k + 2 < len(mods) else None
