@@ -163,6 +163,42 @@ int usf_coupling_planes_ctx(const usf_coupling_planes_desc* d, const float* ctx,
                             const float* b_ctx, usf_stream_t stream);
 
 /*
+ * usf_gemm_planes_side / usf_coupling_planes_side (ADDED entry points: every declaration of internal version 6 is unchanged, so
+ * the number stays; a binding that declares them refuses a library without them when it resolves the symbols).
+ * The transformed half of an affine layer's output has one reader in an inference plan: the output phase of the fused coupling
+ * behind it, which wants it as fp32 (the residual of fma(sign, acc, residual)).  The pair hands it over as fp32 beside the planes:
+ *   side buffer: ceil(M / 16) panels x side_kbn blocks x 2 KiB, 16-byte aligned, below 4 GiB (32-bit offsets).  Chunk (panel p,
+ *     block j) lies at (p * side_kbn + j) * 2048; lane L = 16 g + j' holds 32 bytes at L * 32: the fp32 values of the 8 slots
+ *     that lane holds in a planes chunk (usflows_hip.h), in slot order.
+ *   usf_gemm_planes_side: usf_gemm_planes_bf16x3 with planes output and no residual, whose output blocks [side_kb0, side_kb0 +
+ *     side_kbn) (counted from c_kb0, inside [0, c_kbn)) go to the side buffer (block side_kb0 + j to chunk j) and NOT to
+ *     C_planes -- except the blocks of [both_kb0, both_kb0 + both_kbn), a sub-range of the side range (both_kbn == 0: none),
+ *     which are written both ways: the block that holds conditioning and transformed features.  The other blocks are written
+ *     as planes, as always.  USF_PLANES_BF16X3: the side value is the accumulator -- the float whose exact three-way split the
+ *     planes would hold (exact for every value whose last bit is worth 2^-133 or more; an accumulator of -0, whose planes sum
+ *     to +0, arrives as -0).  USF_PLANES_F16X2: the side value is
+ *     the sum of the two fp16 planes the value would have been stored as, and the range guard looks at it as always.
+ *   usf_coupling_planes_side: usf_coupling_planes (inference: no context, no hidden_out, no USF_ACT_GATE) whose output phase
+ *     reads the residual of transformed block nt from chunk nt of the side buffer (side_nkb must equal nk_t) instead of
+ *     rebuilding it from z's planes.  It reads the conditioning blocks of z and writes its transformed blocks as always -- the
+ *     same bytes as usf_coupling_planes on a z whose transformed blocks hold the planes of the side values; what those blocks
+ *     held before is not read.
+ * Returns -1 (null pointer), -2 (alignment, block ranges, a descriptor the side form does not serve), -3 (a side buffer of
+ * 4 GiB or more) with usf_last_error set before anything is launched.
+ *
+ * Inside an op list the public usf_op union does not grow: a USF_OP_CALL op with fn == USF_FN_GEMM_PLANES_SIDE and n_args == 5
+ * carries (side, side_kb0, side_kbn, both_kb0, both_kbn) and applies to the USF_OP_GEMM_PLANES op that must follow it directly;
+ * one with fn == USF_FN_COUPLING_PLANES_SIDE and n_args == 2 carries (side, side_nkb) and applies to the USF_OP_COUPLING_PLANES
+ * op that must follow it directly.  Each pair is ONE launch.  A list that ends behind a prefix op, or whose next op is of
+ * another kind, is rejected.
+ */
+#define USF_FN_GEMM_PLANES_SIDE 66
+#define USF_FN_COUPLING_PLANES_SIDE 67
+int usf_gemm_planes_side(const usf_gemm_planes_desc* d, void* side, int64_t side_kb0, int64_t side_kbn, int64_t both_kb0,
+                         int64_t both_kbn, usf_stream_t stream);
+int usf_coupling_planes_side(const usf_coupling_planes_desc* d, const void* side, int64_t side_nkb, usf_stream_t stream);
+
+/*
  * usf_coupling_additive_vctx_f32 (internal version 4): usf_coupling_additive_f32 (usflows_hip.h) whose conditioner is a
  * ConditionalDenseNN with 1 <= context_dim <= USF_VCTX_MAX (networks.py:681-751: h = layers[0](x) + layers[1](context)).
  * The first hidden layer's pre-activation becomes

@@ -160,6 +160,8 @@ def op_record(op, names, _ext):
             a = [names.of_ptr(a[0]), a[1], a[2], names.of_ptr(a[3]), a[4], names.of_ptr(a[5])]
         elif _ext.is_ctx_prefix(op):               # ctx, ctx_stride, w_ctx, b_ctx
             a = [names.of_ptr(a[0]), a[1], names.of_ptr(a[2]), names.of_ptr(a[3])]
+        elif _ext.is_side_prefix(op):              # side, then block numbers
+            a = [names.of_ptr(a[0])] + a[1:]
         return f"call fn={d.fn} n_args={d.n_args} a={a}"
     parts = [f"{name}={_field(getattr(d, name), t, names, _ext)}" for name, t in d._fields_]
     return member + " " + " ".join(parts)

@@ -21,7 +21,9 @@ CALL_FNS = {"usf_scale_f32": 1, "usf_channel_affine_f32": 2, "usf_layernorm_chan
 
 FN_COUPLING_PLANES_CTX = 64   # internal USF_OP_CALL id: the context arguments of the USF_OP_COUPLING_PLANES op behind it
 FN_COUPLING_VCTX = 65         # internal USF_OP_CALL id: the vector context of the USF_OP_COUPLING op behind it
-VCTX_MAX = 32                 # USF_VCTX_MAX: widest context usf_coupling_additive_vctx_f32 takes
+FN_GEMM_PLANES_SIDE = 66      # internal USF_OP_CALL id: the fp32 side output of the USF_OP_GEMM_PLANES op behind it
+FN_COUPLING_PLANES_SIDE = 67  # internal USF_OP_CALL id: the fp32 residual buffer of the USF_OP_COUPLING_PLANES op behind it
+VCTX_MAX = 32                # USF_VCTX_MAX: widest context usf_coupling_additive_vctx_f32 takes
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -311,6 +313,8 @@ INTERNAL_SYMBOLS = {
                                              _fp, C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p]),
     "usf_gated_norm_rows_bwd_f32": (C.c_int, [C.POINTER(GatedNormBwdDesc), C.c_void_p]),
     "usf_coupling_planes_ctx": (C.c_int, [C.POINTER(CouplingPlanesDesc), _fp, C.c_int64, _fp, _fp, C.c_void_p]),
+    "usf_gemm_planes_side": (C.c_int, [C.POINTER(GemmPlanesDesc), _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    "usf_coupling_planes_side": (C.c_int, [C.POINTER(CouplingPlanesDesc), _fp, C.c_int64, C.c_void_p]),
     "usf_coupling_additive_vctx_f32": (C.c_int, [C.POINTER(CouplingDesc), _fp, C.c_int64, C.c_int32, _fp, C.c_int64, _fp, C.c_void_p]),
     "usf_coupling_additive_vctx_variant": (C.c_int, [C.POINTER(CouplingDesc), C.c_int32]),
     "usf_conv_ctx_wgrad_f32": (C.c_int, [_fp, _fp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _fp, C.c_void_p]),

@@ -23,7 +23,7 @@ from ._abi import (  # noqa: E402,F401  -- the declarations, re-exported: caller
     USF_ABI_VERSION, USF_INTERNAL_VERSION, USF_MAX_HIDDEN, ACT_NONE, ACT_LEAKY_RELU, ACT_GATE, BASE_LAPLACE, BASE_NORMAL,
     BASE_LPNORM1, BASE_LPNORM2, BASE_LPNORMINF, BASE_ROWSUM, NORM_LOGNORMAL, NORM_GAMMA, NORM_RAW_PARAMS, NORM_WEIBULL, NORM_HALFNORMAL, NORM_CHI, RADIAL_MAX_K, OP_LINEAR,
     OP_COUPLING, OP_PACK_PLANES, OP_GEMM_PLANES, OP_COUPLING_PLANES, OP_GATED_NORM, OP_CALL, PLANES_BF16X3, PLANES_F16X2, CALL_FNS,
-    FN_COUPLING_PLANES_CTX, FN_COUPLING_VCTX, VCTX_MAX,
+    FN_COUPLING_PLANES_CTX, FN_COUPLING_VCTX, FN_GEMM_PLANES_SIDE, FN_COUPLING_PLANES_SIDE, VCTX_MAX,
     _fp, LinearDesc, CouplingDesc, PackPlanesDesc, GemmPlanesDesc, CouplingPlanesDesc, MtChunk, AdamChunk, GradChunk, ConvVariantQuery, ConvVariant, ConvWgradQuery, ConvWgradInfo, LnBwdInfo, CONV_ENTRIES, GatedNormDesc, GatedNormBwdDesc,
     CallDesc, _OpUnion, Op, LuPrepDesc, PackJob, PsumJob, WgradJob, WReduceJob, WPlanesJob, GradJob, SIZEOF_KINDS, PUBLIC_SYMBOLS,
     INTERNAL_SYMBOLS, SYMBOLS)
@@ -1147,6 +1147,42 @@ def coupling_vctx_prefix(ctx, ld_ctx, ctx_dim, w_ctx_t, ldw_ctx, b_ctx) -> "Op":
 def is_ctx_prefix(op) -> bool:
     """a USF_OP_CALL op that only carries the context arguments of the op behind it (the pair is one launch)"""
     return op.kind == OP_CALL and op.u.call.fn in (FN_COUPLING_PLANES_CTX, FN_COUPLING_VCTX)
+
+
+def gemm_planes_side_op(op, side, side_kb0, side_kbn, both_kb0, both_kbn, device):
+    """usf_gemm_planes_side: the Op's usf_gemm_planes_bf16x3 launch with the output blocks [side_kb0, side_kb0 + side_kbn) as fp32
+    in ``side`` (those of [both_kb0, both_kb0 + both_kbn) as planes too)"""
+    _launch("usf_gemm_planes_side", (C.byref(op.u.gemm_planes), ptr(side), int(side_kb0), int(side_kbn), int(both_kb0), int(both_kbn),
+                                     current_stream(device)), (op, side))
+
+
+def coupling_planes_side_op(op, side, side_nkb, device):
+    """usf_coupling_planes_side: the Op's usf_coupling_planes launch with the residual read as fp32 from ``side``"""
+    _launch("usf_coupling_planes_side", (C.byref(op.u.coupling_planes), ptr(side), int(side_nkb), current_stream(device)), (op, side))
+
+
+def _side_prefix(fn: int, words) -> "Op":
+    op = Op()
+    op.kind = OP_CALL
+    op.u.call.fn, op.u.call.n_args = fn, len(words)
+    for j, w in enumerate(words):
+        op.u.call.a[j] = w
+    return op
+
+
+def gemm_planes_side_prefix(side, side_kb0, side_kbn, both_kb0, both_kbn) -> "Op":
+    """the USF_OP_CALL op (USF_FN_GEMM_PLANES_SIDE) that hands the USF_OP_GEMM_PLANES op behind it its fp32 side output"""
+    return _side_prefix(FN_GEMM_PLANES_SIDE, (side.data_ptr(), int(side_kb0), int(side_kbn), int(both_kb0), int(both_kbn)))
+
+
+def coupling_planes_side_prefix(side, side_nkb) -> "Op":
+    """the USF_OP_CALL op (USF_FN_COUPLING_PLANES_SIDE) that hands the USF_OP_COUPLING_PLANES op behind it its fp32 residual buffer"""
+    return _side_prefix(FN_COUPLING_PLANES_SIDE, (side.data_ptr(), int(side_nkb)))
+
+
+def is_side_prefix(op) -> bool:
+    """a USF_OP_CALL op that only carries the fp32 side buffer of the planes op behind it (the pair is one launch)"""
+    return op.kind == OP_CALL and op.u.call.fn in (FN_GEMM_PLANES_SIDE, FN_COUPLING_PLANES_SIDE)
 
 
 def run_ops(ops_array, n, device=None):

@@ -40,6 +40,7 @@ class Config:
     # ---- tuning knobs (Python side); every one documented where it is used --------------------------------------------------
     _KNOBS = dict(
         planes_min_rows=8192,      # engine: smallest batch of a planes plan
+        planes_side_f32=True,      # planes inference plans: the transformed half travels from an affine GEMM to the fused coupling behind it as fp32
         base_in_epilogue=True,     # planes plans of Flow.log_prob: Laplace / Normal base density reduced by the last GEMM's epilogue
         tiny_coupling=True,        # launch-bound batches, tiny conditioners (the live flat configuration): a coupling layer as ONE launch each way
         engine_graph=False,        # engine: replay small inference batches as a hipGraph (measured no faster than usf_run_ops)

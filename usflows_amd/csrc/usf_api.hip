@@ -90,6 +90,9 @@ int gemm_planes_variant(const usf_gemm_planes_desc* d);
 int coupling_planes(const usf_coupling_planes_desc* d, hipStream_t stream);
 int coupling_planes_ctx(const usf_coupling_planes_desc* d, const float* ctx, int64_t ctx_stride, const float* w_ctx, const float* b_ctx,
                         hipStream_t stream);
+int gemm_planes_side(const usf_gemm_planes_desc* d, void* side, int64_t side_kb0, int64_t side_kbn, int64_t both_kb0, int64_t both_kbn,
+                     hipStream_t stream);
+int coupling_planes_side(const usf_coupling_planes_desc* d, const void* side, int64_t side_nkb, hipStream_t stream);
 int lu_prepare(const usf_lu_prep_desc* d, hipStream_t stream);
 int gemm_f64(const double* A, int64_t lda, int64_t sA, int transA, const double* B, int64_t ldb, int64_t sB, int transB,
              double* C, int64_t ldc, int64_t sC, int64_t M, int64_t N, int64_t K, int64_t batch, double alpha,
@@ -268,6 +271,15 @@ int usf_coupling_planes(const usf_coupling_planes_desc* d, usf_stream_t stream) 
 int usf_coupling_planes_ctx(const usf_coupling_planes_desc* d, const float* ctx, int64_t ctx_stride, const float* w_ctx, const float* b_ctx,
                             usf_stream_t stream) {
   return usf::coupling_planes_ctx(d, ctx, ctx_stride, w_ctx, b_ctx, (hipStream_t)stream);
+}
+int usf_gemm_planes_side(const usf_gemm_planes_desc* d, void* side, int64_t side_kb0, int64_t side_kbn, int64_t both_kb0,
+                         int64_t both_kbn, usf_stream_t stream) {
+  if (!side) { usf::set_error("usf_gemm_planes_side: null side buffer"); return -1; }
+  return usf::gemm_planes_side(d, side, side_kb0, side_kbn, both_kb0, both_kbn, (hipStream_t)stream);
+}
+int usf_coupling_planes_side(const usf_coupling_planes_desc* d, const void* side, int64_t side_nkb, usf_stream_t stream) {
+  if (!side) { usf::set_error("usf_coupling_planes_side: null side buffer"); return -1; }
+  return usf::coupling_planes_side(d, side, side_nkb, (hipStream_t)stream);
 }
 int usf_gemm_planes_variant(const usf_gemm_planes_desc* d) { return usf::gemm_planes_variant(d); }
 int usf_coupling_variant(const usf_coupling_desc* d) { return usf::coupling_variant(d); }
@@ -706,6 +718,26 @@ int usf_run_ops(const usf_op* ops, int32_t n_ops, usf_stream_t stream) {
                                   reinterpret_cast<const float*>((uintptr_t)c->a[3]), (int64_t)c->a[4],
                                   reinterpret_cast<const float*>((uintptr_t)c->a[5])};
           rc = usf::coupling_dispatch(&ops[i + 1].u.coupling, (hipStream_t)stream, &v);
+          ++i;
+          break;
+        }
+        if (ops[i].u.call.fn == USF_FN_GEMM_PLANES_SIDE || ops[i].u.call.fn == USF_FN_COUPLING_PLANES_SIDE) {
+          // the fp32 side buffer of the planes op that follows (usflows_hip_internal.h): one launch for the pair
+          const usf_call_desc* c = &ops[i].u.call;
+          const bool gemm = c->fn == USF_FN_GEMM_PLANES_SIDE;
+          if (c->n_args != (gemm ? 5 : 2) || i + 1 >= n_ops || ops[i + 1].kind != (gemm ? USF_OP_GEMM_PLANES : USF_OP_COUPLING_PLANES)) {
+            usf::set_error("usf_run_ops: op %d (%s) needs %d arguments and a %s op behind it", i,
+                           gemm ? "USF_FN_GEMM_PLANES_SIDE" : "USF_FN_COUPLING_PLANES_SIDE", gemm ? 5 : 2,
+                           gemm ? "USF_OP_GEMM_PLANES" : "USF_OP_COUPLING_PLANES");
+            return -2;
+          }
+          void* side = reinterpret_cast<void*>((uintptr_t)c->a[0]);
+          if (!side) { usf::set_error("usf_run_ops: op %d carries a null side buffer", i); return -1; }
+          if (gemm)
+            rc = usf::gemm_planes_side(&ops[i + 1].u.gemm_planes, side, (int64_t)c->a[1], (int64_t)c->a[2], (int64_t)c->a[3],
+                                       (int64_t)c->a[4], (hipStream_t)stream);
+          else
+            rc = usf::coupling_planes_side(&ops[i + 1].u.coupling_planes, side, (int64_t)c->a[1], (hipStream_t)stream);
           ++i;
           break;
         }

@@ -14,6 +14,8 @@
 //   * NPL = 3: bf16, six MFMAs per product; NPL = 2: fp16, three (range guard as in usf_planes.hip).
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "usf_common.h"
 
 namespace usf {
@@ -114,6 +116,8 @@ struct CplPArgs {
   char* hout[2]; const char* gate[2];
   // context term of the first layer (CTX instantiations only; usf_coupling_planes_ctx): ctx[row * ctx_stride], w_ctx / b_ctx [256]
   const float* ctx; int ctx_stride; const float* w_ctx; const float* b_ctx;
+  // fp32 residual of the transformed blocks (SIDE instantiations only; usf_coupling_planes_side): nk_t chunks of 2 KiB per panel
+  const char* side;
 };
 
 #ifdef USF_STAMP
@@ -130,8 +134,14 @@ struct CplPArgs {
 // CTX (MODE 0 / 1): ConditionalDenseNN's context layer (networks.py:739-751, context_dim 1) -- the first layer's accumulators
 // start at b_in[h] + b_ctx[h] + ctx[row] * w_ctx[h] instead of b_in[h]: a rank-1 term, no MFMA, no LDS, nothing in the K loops.
 // The CTX = false instantiations are the instruction streams they were without the flag.
-template <int NPL, int NH, int MODE = 0, bool CTX = false>
+// SIDE (MODE 0, no context; usf_coupling_planes_side): the residual of the output phase arrives as the fp32 values the GEMM in
+// front of the layer kept beside its planes (usf_gemm_planes_side: the lane's 8 slots of a block as 32 bytes at lane * 32 of a
+// 2-KiB chunk) -- two 16-byte loads per block instead of NPL, no widenings and no adds to rebuild the value.  The transformed
+// blocks of z are written as before and are not read.  The SIDE = false instantiations are the instruction streams they were
+// (opcode by opcode; the two <2, 1, 0> forms gained one s_waitcnt: profiles/planes_side_f32.md).
+template <int NPL, int NH, int MODE = 0, bool CTX = false, bool SIDE = false>
 __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs p) {
+  static_assert(!SIDE || (MODE == 0 && !CTX), "the fp32 residual serves the plain inference launch");
   typedef CPlanes<NPL> PT;
   typedef typename PT::vec vec8;
   constexpr int T = 16;                     // hidden tiles (padded hidden width 256)
@@ -428,14 +438,23 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) { PT::split(X[2 * ks], X[2 * ks + 1], xp[ks]); save_hidden(NH - 1, ks, xp[ks]); }
     // residual of output block nt (the lane's own chunk line) and its slice of the output bias, one block ahead
-    vec8 res[NPL];
+    // (SIDE: the residual itself, the lane's two tiles as fp32 from the side buffer's chunk of block nt)
+    typename std::conditional<SIDE, f32x4, vec8>::type res[SIDE ? 2 : NPL];
     f32x4 bo[2];
+    unsigned soff = (unsigned)lane * 32u;                     // SIDE: the lane's 32 bytes of a side chunk
+    const char* const srow = SIDE ? p.side + ((size_t)panc * p.nk_t) * 2048u : nullptr;       // the wave's panel of it, a scalar
     auto issue_res = [&](int nt) {
       if constexpr (A32) { cp_pin(loff); cp_pin(goff); }
+      if constexpr (SIDE) {
+        if constexpr (A32) cp_pin(soff);
 #pragma unroll
-      for (int q = 0; q < NPL; ++q) {
-        if constexpr (A32) res[q] = cp_load<vec8>(zrow + ((size_t)(p.kb_t0 + nt) * CHB + q * 1024), loff);
-        else res[q] = *reinterpret_cast<const vec8*>(p.z + zbase + (size_t)(p.kb_t0 + nt) * CHB + q * 1024);
+        for (int u = 0; u < 2; ++u) res[u] = cp_load<f32x4>(srow + ((size_t)nt * 2048u + 16 * u), soff);
+      } else {
+#pragma unroll
+        for (int q = 0; q < NPL; ++q) {
+          if constexpr (A32) res[q] = cp_load<vec8>(zrow + ((size_t)(p.kb_t0 + nt) * CHB + q * 1024), loff);
+          else res[q] = *reinterpret_cast<const vec8*>(p.z + zbase + (size_t)(p.kb_t0 + nt) * CHB + q * 1024);
+        }
       }
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
@@ -450,8 +469,13 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
       for (int u = 0; u < 2; ++u) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          float r = (float)rs[0][4 * u + e] + (float)rs[1][4 * u + e];
-          if (NPL == 3) r = r + (float)rs[NPL - 1][4 * u + e];
+          float r;
+          if constexpr (SIDE) {
+            r = rs[u][e];                                        // the float the planes' sum below would have rebuilt
+          } else {
+            r = (float)rs[0][4 * u + e] + (float)rs[1][4 * u + e];
+            if (NPL == 3) r = r + (float)rs[NPL - 1][4 * u + e];
+          }
           v[u][e] = __builtin_fmaf(p.sign, ac[u][e], r);       // (sign = +-1: the product is exact, one rounding either way)
         }
         guard(v[u]);
@@ -490,7 +514,7 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
       for (int i = 0; i < 2 * KS; ++i) {
         __builtin_amdgcn_sched_group_barrier(0x008, NPR, 0);
         if (i + AHEAD < 2 * KS) __builtin_amdgcn_sched_group_barrier(0x100, NPL, 0);
-        if (i < NST + NPL + 2) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+        if (i < NST + (SIDE ? 2 : NPL) + 2) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
       store_n(buf ^ 1, st);
@@ -522,8 +546,8 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
 unsigned long long* g_cdbg = nullptr;
 #endif
 
-int coupling_planes_ctx(const usf_coupling_planes_desc* d, const float* ctx, int64_t ctx_stride, const float* w_ctx,
-                        const float* b_ctx, hipStream_t stream) {
+static int coupling_planes_launch(const usf_coupling_planes_desc* d, const float* ctx, int64_t ctx_stride, const float* w_ctx,
+                                  const float* b_ctx, const void* side, int64_t side_nkb, hipStream_t stream) {
   if (!d) { set_error("usf_coupling_planes: null descriptor"); return -1; }
   if (ctx) {
     if (d->act == USF_ACT_GATE) { set_error("usf_coupling_planes_ctx: USF_ACT_GATE takes no context (the context enters no data gradient)"); return -2; }
@@ -568,7 +592,21 @@ int coupling_planes_ctx(const usf_coupling_planes_desc* d, const float* ctx, int
       return -3;
     }
   }
+  if (side) {
+    // the fp32 residual (usflows_hip_internal.h): the plain inference launch only, one 2-KiB chunk per panel and transformed block
+    if (ctx || d->hidden_out[0] || d->hidden_out[1] || d->act == USF_ACT_GATE) {
+      set_error("usf_coupling_planes_side: the fp32 residual serves the inference launch without a context (no hidden_out, no USF_ACT_GATE)");
+      return -2;
+    }
+    if (!aligned16(side)) { set_error("usf_coupling_planes_side: side must be 16-byte aligned"); return -2; }
+    if (side_nkb != d->nk_t) {
+      set_error("usf_coupling_planes_side: the side buffer holds %lld blocks per panel, the layer transforms %lld", (long long)side_nkb, (long long)d->nk_t);
+      return -2;
+    }
+    if (npanels * d->nk_t * 2048 >= (1LL << 32)) { set_error("usf_coupling_planes_side: side buffer of 4 GiB or more"); return -3; }
+  }
   CplPArgs a;
+  a.side = reinterpret_cast<const char*>(side);
   a.z = reinterpret_cast<char*>(d->z); a.z_nkb = (int)d->z_nkb; a.npanels = (int)npanels; a.M = (int)d->M;
   a.kb_p0 = (int)d->kb_p0; a.nk_p = (int)d->nk_p; a.kb_t0 = (int)d->kb_t0; a.nk_t = (int)d->nk_t;
   a.Win = reinterpret_cast<const char*>(d->W_in); a.ld_in = d->ldw_in; a.pl_in = d->w_in_plane; a.b_in = d->b_in;
@@ -620,7 +658,14 @@ int coupling_planes_ctx(const usf_coupling_planes_desc* d, const float* ctx, int
   const dim3 block(512);
 #define USF_CPL(NPL_, NH_) hipLaunchKernelGGL((coupling_planes_kernel<NPL_, NH_>), grid, block, 0, stream, a)
 #define USF_CPLC(NPL_, NH_) hipLaunchKernelGGL((coupling_planes_kernel<NPL_, NH_, 0, true>), grid, block, 0, stream, a)
-  if (ctx) {
+#define USF_CPLS(NPL_, NH_) hipLaunchKernelGGL((coupling_planes_kernel<NPL_, NH_, 0, false, true>), grid, block, 0, stream, a)
+  if (side) {
+    if (npl == 2) {
+      switch (d->n_hidden) { case 1: USF_CPLS(2, 1); break; case 2: USF_CPLS(2, 2); break; default: USF_CPLS(2, 3); break; }
+    } else {
+      switch (d->n_hidden) { case 1: USF_CPLS(3, 1); break; case 2: USF_CPLS(3, 2); break; default: USF_CPLS(3, 3); break; }
+    }
+  } else if (ctx) {
     if (npl == 2) {
       switch (d->n_hidden) { case 1: USF_CPLC(2, 1); break; case 2: USF_CPLC(2, 2); break; default: USF_CPLC(2, 3); break; }
     } else {
@@ -631,9 +676,19 @@ int coupling_planes_ctx(const usf_coupling_planes_desc* d, const float* ctx, int
   } else {
     switch (d->n_hidden) { case 1: USF_CPL(3, 1); break; case 2: USF_CPL(3, 2); break; default: USF_CPL(3, 3); break; }
   }
+#undef USF_CPLS
 #undef USF_CPLC
 #undef USF_CPL
   return check_launch("usf_coupling_planes");
+}
+
+int coupling_planes_ctx(const usf_coupling_planes_desc* d, const float* ctx, int64_t ctx_stride, const float* w_ctx,
+                        const float* b_ctx, hipStream_t stream) {
+  return coupling_planes_launch(d, ctx, ctx_stride, w_ctx, b_ctx, nullptr, 0, stream);
+}
+
+int coupling_planes_side(const usf_coupling_planes_desc* d, const void* side, int64_t side_nkb, hipStream_t stream) {
+  return coupling_planes_launch(d, nullptr, 0, nullptr, nullptr, side, side_nkb, stream);
 }
 
 int coupling_planes(const usf_coupling_planes_desc* d, hipStream_t stream) { return coupling_planes_ctx(d, nullptr, 0, nullptr, nullptr, stream); }

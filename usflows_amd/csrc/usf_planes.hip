@@ -274,12 +274,21 @@ struct PlArgs {
   int skip_dead;                        // knob planes_skip_dead: the last column block looks for an all-zero last feature tile
   // base density in the fp32-output epilogue (b_part == nullptr: off): tables loc | 1 / scale | constant, stride b_stride
   const float* b_tab; float* b_part; int b_stride; int b_base;
+  // fp32 side output (SIDE instantiations only; usf_gemm_planes_side): the output blocks [s_kb0, s_kb0 + s_kbn) go to S as
+  // fp32 chunks, those of them in [s_both0, s_both0 + s_bothn) also to the planes
+  char* S; int s_kb0, s_kbn, s_both0, s_bothn;
   unsigned long long* clk;              // usf_set_clock_buffer: [shader cycles, 100 MHz ticks] summed over the blocks' lifetimes
   unsigned long long* dbg;
   unsigned long long* span;             // tuning builds only: [first wave start, last wave end] in s_memrealtime ticks
 };
 
-template <int NPL, int TN, bool F32OUT>
+// SIDE (planes output only; usf_gemm_planes_side in usflows_hip_internal.h): the output blocks of a range leave as the fp32
+// accumulators themselves -- 2 KiB per (panel, block), the lane's 8 slots as 32 bytes at lane * 32, in the planes' slot order --
+// for the one reader that wants them back as fp32, the fused coupling's residual.  No split and no plane stores for them,
+// except for the blocks of the sub-range that the coupling's first layer also reads as planes.  The SIDE = false
+// instantiations keep their instruction streams (the planes-output forms gained two s_mov_b32 with the longer argument
+// block, nothing else: profiles/planes_side_f32.md) and their register counts.
+template <int NPL, int TN, bool F32OUT, bool SIDE = false>
 __global__ __launch_bounds__(512, 2) void gemm_planes_kernel(const PlArgs p) {
   typedef Planes<NPL> PT;
   typedef typename PT::vec vec8;
@@ -626,6 +635,9 @@ __global__ __launch_bounds__(512, 2) void gemm_planes_kernel(const PlArgs p) {
 #pragma unroll
     for (int t = 0; t < TN; ++t) {
       const int kbo = bn * TN + t;
+      // (block-uniform: one test per 32-column block)
+      const bool to_side = SIDE && (unsigned)(kbo - p.s_kb0) < (unsigned)p.s_kbn;
+      const bool to_planes = !to_side || (unsigned)(kbo - p.s_both0) < (unsigned)p.s_bothn;
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
         if (kbo < p.c_kbn && pw[b] < p.npanels) {
@@ -633,6 +645,30 @@ __global__ __launch_bounds__(512, 2) void gemm_planes_kernel(const PlArgs p) {
           float x[8];
 #pragma unroll
           for (int u = 0; u < 8; ++u) x[u] = acc[2 * t + (u >> 2)][b][u & 3];
+          if constexpr (SIDE) {
+            if (to_side) {
+              // a 32-bit offset on the scalar base, as the A operand is addressed (the host keeps the buffer below 4 GiB)
+              const unsigned soff = ((unsigned)pw[b] * (unsigned)p.s_kbn + (unsigned)(kbo - p.s_kb0)) * 2048u + (unsigned)lane * 32u;
+              f32x4 s0 = {x[0], x[1], x[2], x[3]}, s1 = {x[4], x[5], x[6], x[7]};
+              if constexpr (NPL == 2) {
+                // fp16 planes hold 22 bits: the reader gets the value its planes would have given it, not the accumulator
+                bool sb = false;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) sb = sb || (16 * pw[b] + lj < p.M && !(fabsf(x[u]) < USF_F16_GUARD));
+                bad = bad || sb;
+                vec8 so[NPL];
+                PT::split(x, so);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                  s0[u] = (float)so[0][u] + (float)so[1][u];
+                  s1[u] = (float)so[0][4 + u] + (float)so[1][4 + u];
+                }
+              }
+              *reinterpret_cast<f32x4*>(p.S + soff) = s0;
+              *reinterpret_cast<f32x4*>(p.S + (soff + 16u)) = s1;
+            }
+            if (!to_planes) continue;
+          }
           if (p.R) {
             vec8 r[NPL];
 #pragma unroll
@@ -696,6 +732,7 @@ unsigned long long* g_pspan = nullptr;
 
 template <int NPL, int TN>
 static int launch_planes(PlArgs a, bool f32out, hipStream_t stream) {
+  const bool side = a.S != nullptr;
   constexpr int BN = TN * 32;
   a.nbm = (a.npanels + 15) / 16;
   a.nbn = f32out ? (a.N + BN - 1) / BN : (a.c_kbn + TN - 1) / TN;
@@ -707,6 +744,7 @@ static int launch_planes(PlArgs a, bool f32out, hipStream_t stream) {
   cus = (cus / 8) * 8 > 0 ? (cus / 8) * 8 : 8;
   if (persist && grid > cus) grid = cus;
   if (f32out) hipLaunchKernelGGL((gemm_planes_kernel<NPL, TN, true>), dim3((unsigned)grid), dim3(512), 0, stream, a);
+  else if (side) hipLaunchKernelGGL((gemm_planes_kernel<NPL, TN, false, true>), dim3((unsigned)grid), dim3(512), 0, stream, a);
   else hipLaunchKernelGGL((gemm_planes_kernel<NPL, TN, false>), dim3((unsigned)grid), dim3(512), 0, stream, a);
   return check_launch("usf_gemm_planes");
 }
@@ -726,7 +764,8 @@ int gemm_planes_variant(const usf_gemm_planes_desc* d) {
   return 5000 + 10 * gemm_planes_tn(nblk) + (f32out ? 1 : 0);
 }
 
-int gemm_planes(const usf_gemm_planes_desc* d, hipStream_t stream) {
+int gemm_planes_side(const usf_gemm_planes_desc* d, void* side, int64_t side_kb0, int64_t side_kbn, int64_t both_kb0,
+                     int64_t both_kbn, hipStream_t stream) {
   if (!d) { set_error("usf_gemm_planes_bf16x3: null descriptor"); return -1; }
   if (d->M < 0 || d->M > 0x7fffffff || d->nk <= 0 || d->a_nkb <= 0 || d->a_kb0 < 0 || d->a_kb0 + d->nk > d->a_nkb ||
       d->w_rows < 4 || d->w_rows > 0x7fffffff) {
@@ -764,6 +803,21 @@ int gemm_planes(const usf_gemm_planes_desc* d, hipStream_t stream) {
   a.skip_dead = (int)tuning("planes_skip_dead", 1);         // A/B aid: 0 = every tile runs the full K loop
   a.b_tab = d->base_tab; a.b_part = d->base_part; a.b_stride = (int)d->base_tab_stride; a.b_base = d->base;
   a.dbg = nullptr; a.span = nullptr;
+  a.S = nullptr; a.s_kb0 = a.s_kbn = a.s_both0 = a.s_bothn = 0;
+  if (side) {
+    // the fp32 side output (usflows_hip_internal.h), checked in front of any launch
+    if (f32out || d->residual) { set_error("usf_gemm_planes_side: the side output needs planes output and no residual"); return -2; }
+    if (!aligned16(side)) { set_error("usf_gemm_planes_side: side must be 16-byte aligned"); return -2; }
+    if (side_kbn <= 0 || side_kb0 < 0 || side_kb0 + side_kbn > d->c_kbn || both_kbn < 0 ||
+        (both_kbn > 0 && (both_kb0 < side_kb0 || both_kb0 + both_kbn > side_kb0 + side_kbn))) {
+      set_error("usf_gemm_planes_side: bad block ranges (side %lld + %lld of c_kbn=%lld, both %lld + %lld)", (long long)side_kb0,
+                (long long)side_kbn, (long long)d->c_kbn, (long long)both_kb0, (long long)both_kbn);
+      return -2;
+    }
+    if (npanels * side_kbn * 2048 >= (1LL << 32)) { set_error("usf_gemm_planes_side: side buffer larger than the kernel's 32-bit offsets"); return -3; }
+    a.S = reinterpret_cast<char*>(side); a.s_kb0 = (int)side_kb0; a.s_kbn = (int)side_kbn;
+    a.s_both0 = (int)both_kb0; a.s_bothn = (int)both_kbn;
+  }
   a.clk = clock_buffer();
 #ifdef USF_STAMP
   a.dbg = g_pdbg; a.span = g_pspan;
@@ -801,5 +855,7 @@ int gemm_planes(const usf_gemm_planes_desc* d, hipStream_t stream) {
   if (npl == 2) return tn == 4 ? launch_planes<2, 4>(a, f32out, stream) : launch_planes<2, 5>(a, f32out, stream);
   return tn == 4 ? launch_planes<3, 4>(a, f32out, stream) : launch_planes<3, 5>(a, f32out, stream);
 }
+
+int gemm_planes(const usf_gemm_planes_desc* d, hipStream_t stream) { return gemm_planes_side(d, nullptr, 0, 0, 0, 0, stream); }
 
 }  // namespace usf

@@ -323,6 +323,12 @@ class FlowEngine(FlatPlanMixin, PlanesPlanMixin):
         self.use_planes = config.planes
         self.planes_min_rows = int(config.planes_min_rows)
         self.planes_min_rows_bf16x3 = 24576
+        # inference plans: an affine layer hands the transformed half of its output to the fused coupling behind it as fp32
+        # beside the planes (usf_gemm_planes_side / usf_coupling_planes_side).  Knob planes_side_f32 = 0 builds the
+        # launch list without it (the A/B arm).  From planes_side_min_rows rows: the smallest batch at which a planes plan is
+        # chosen automatically -- below it (forced plans) the list stays the plain one, which is all that was measured there
+        self.planes_side_f32 = bool(config.planes_side_f32)
+        self.planes_side_min_rows = 8192
         # training on the planes pipeline (round 5): the forward keeps every layer's planes buffer and the conditioners' hidden
         # activations as planes, the backward runs on usf_gemm_planes_bf16x3 / usf_coupling_planes (gate mode) /
         # usf_wgrad_blocked_f32.  USFLOWS_AMD_TRAIN_PLANES=0 keeps the fp32-row path of rounds 3 / 4.
@@ -840,7 +846,8 @@ class FlowEngine(FlatPlanMixin, PlanesPlanMixin):
         key = (direction, B, str(device), has_ctx, final, self.use_fused_coupling, self.gemm_mode, self.fused_min_rows,
                config.tiny_coupling, config.get_lib("coupling_tiny", 1), train, self.use_planes, self.planes_min_rows, self._planes_fmt(), self.planes_min_rows_bf16x3,
                (not train) and self._merge_on(direction), train and self.use_train_planes, train and self.train_planes_min_rows,
-               has_ctx and (self.train_ctx_planes_min_rows if train else self.ctx_planes_min_rows), has_ctx and self.ctx_dim)
+               has_ctx and (self.train_ctx_planes_min_rows if train else self.ctx_planes_min_rows), has_ctx and self.ctx_dim,
+               (not train) and self.planes_side_f32 and B >= self.planes_side_min_rows)
         plan = self._plans.get(key)
         if plan is None:
             plan = self._build_plan(direction, B, device, has_ctx, final, train)
@@ -965,10 +972,13 @@ class FlowEngine(FlatPlanMixin, PlanesPlanMixin):
                 while j < end:
                     op = arr[j]
                     n_run = 2 if _ext.is_ctx_prefix(op) else 1       # (a context prefix and its coupling op are ONE launch)
-                    if n_run == 2 and arr[j + 1].kind == _ext.OP_COUPLING:
+                    side = _ext.is_side_prefix(op)                   # (so are a side-buffer prefix and its planes op, under that op's tag)
+                    if side:
+                        n_run, op = 2, arr[j + 1]
+                    if n_run == 2 and not side and arr[j + 1].kind == _ext.OP_COUPLING:
                         c_ = arr[j + 1].u.coupling
                         tag = ("coupling_vctx", c_.M, c_.n_trans, c_.n_pass)
-                    elif n_run == 2:
+                    elif n_run == 2 and not side:
                         c_ = arr[j + 1].u.coupling_planes
                         tag = ("coupling_planes_ctx", c_.M, 32 * c_.nk_t, 32 * c_.nk_p)
                     elif op.kind == _ext.OP_LINEAR:

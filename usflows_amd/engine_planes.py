@@ -279,6 +279,7 @@ class _PlanesPlan:
         self.meta: List[dict] = []
         self.patch_in, self.patch_out = [], []
         self.head_scale, self.bias_in_head, self.out_buf = None, False, None
+        self.side_for = None            # (coupling step, nk_t) whose residual the last affine GEMM left as fp32 (_side_output)
 
     def planes_buf(self, name: str, blocks: int) -> torch.Tensor:
         ws, n = self.ws, (-(-self.B // 16)) * blocks * 3072            # (sized for either format)
@@ -358,10 +359,48 @@ class _PlanesPlan:
                 self.n_z += 1
             kw.update(C_planes=self.other.data_ptr(), c_nkb=nkb, c_kb0=0, c_kbn=nkb)
             self.z, self.z_name, self.other, self.other_name = self.other, self.other_name, self.z, self.z_name
+            self._side_output(k + taken)
         if self.train:
             self.meta[-1]["out_buf"] = self.out_buf[0] if is_last else self.z_name
         self.ops.append(self.gemm_op(W, **kw))
         return taken
+
+    def side_range(self, k: int):
+        """the fp32 side output of the affine GEMM in front of primitive k: None, or (coupling step, kb_t0, nk_t, both_kb0,
+        both_kbn) when that primitive is a coupling of this plan that runs as ONE fused launch without a context -- the only
+        reader of the transformed blocks [kb_t0, kb_t0 + nk_t) of the GEMM's output then wants them as fp32 (its residual).  The
+        blocks of that range which also hold conditioning features (both) are written as planes as well: the coupling's first
+        layer reads them.  Inference plans from planes_side_min_rows rows, knob planes_side_f32."""
+        e = self.eng
+        if self.train or not e.planes_side_f32 or self.B < e.planes_side_min_rows or k >= len(self.prims):
+            return None
+        prim, i = self.prims[k]
+        if prim not in ("coupling_fwd", "coupling_bwd"):
+            return None
+        cp = self.pk["coupling"][i]
+        if (self.has_ctx and cp["has_ctx"]) or not e._planes_coupling_fused(list(cp["raw"]["h"]), self.B, self.fmt):
+            return None
+        geo = e._coupling_geometry(cp)
+        t0, t1 = geo["kb_t0"], geo["kb_t0"] + geo["nk_t"]
+        b0, b1 = max(t0, geo["kb_p0"]), min(t1, geo["kb_p0"] + geo["nk_p"])
+        return (i, t0, t1 - t0, b0, b1 - b0) if b1 > b0 else (i, t0, t1 - t0, t0, 0)
+
+    def _side_output(self, k: int) -> None:
+        """the prefix op in front of an affine GEMM whose transformed half goes to the coupling behind it as fp32 (side_range)"""
+        self.side_for = None
+        r = self.side_range(k)
+        if r is None:
+            return
+        i, t0, nt, b0, nb = r
+        # ONE buffer per plan, reused by every (GEMM, coupling) pair: sized for the widest transformed range of the flow's
+        # couplings up front (ops built earlier hold its address)
+        ws = self.ws
+        nmax = max(self.eng._coupling_geometry(cp)["nk_t"] for cp in self.pk["coupling"].values())
+        n = (-(-self.B // 16)) * nmax * 2048
+        if "pside" not in ws or ws["pside"].numel() < n:
+            ws["pside"] = torch.empty(n, dtype=torch.uint8, device=self.device)
+        self.ops.append(_ext.gemm_planes_side_prefix(ws["pside"], t0, nt, b0, nb))
+        self.side_for = (i, nt)
 
     def _final_store(self, kw: dict) -> None:
         """where the last GEMM's fp32 result goes (``final``): sets its descriptor fields in kw and ``out_buf``"""
@@ -420,6 +459,10 @@ class _PlanesPlan:
         if self.train:
             self.meta.append(dict(kind="coupling", op=len(self.ops), step=i, buf=self.z_name, sign=sign, use_ctx=use_ctx,
                                   hidden_planes=hnames, **geo))
+        if self.side_for == (i, geo["nk_t"]) and not use_ctx:
+            # the affine GEMM in front of the layer left the transformed half as fp32 (_side_output): the residual comes from there
+            self.ops.append(_ext.coupling_planes_side_prefix(ws["pside"], geo["nk_t"]))
+        self.side_for = None
         self.ops.append(op)
 
     def _coupling_chained(self, i: int, cp: dict, geo: dict, sign: float) -> None:
