@@ -350,6 +350,45 @@ typedef struct usf_ln_bwd_info {
 } usf_ln_bwd_info;
 int usf_layernorm_channels_bwd_variant(int64_t B, int64_t C, int64_t P, usf_ln_bwd_info* out);
 
+/*
+ * usf_conv_wgrad_wide_f32 (an addition: USF_INTERNAL_VERSION is unchanged): the contract and the argument list of usf_conv_wgrad_f32 -- dW, db of a stride-1
+ * "same" convolution with kernel 1 or 3 from x (with the input transforms in_act, in_mul, pre_sub) and dy, exact fp32 on
+ * v_mfma_f32_16x16x4_f32, deterministic -- for the shapes that entry point refuses: one 256-thread block stages one sample at a
+ * time into LDS and the (cout tile, cin tile, tap) accumulator tiles are dealt over its four waves (usf_conv_wgrad_wide.hip).
+ * Served: 1 <= cin, cout <= 64 (ANY value: channel tiles are zero-padded to 16 in LDS), 1 <= H * W <= 256 (W == 1 included),
+ * B >= 1, tensors 4-byte aligned, provided the sample's LDS image fits 160 KiB:
+ *     kernel 3: S = W + 1, n = 4 * ceil(((H - 1) * S + W) / 4), CSy = 2odd(n), CSx = 2odd(n + 2 * S + 2)
+ *     kernel 1: CSx = CSy = 2odd(4 * ceil(H * W / 4))             (2odd(v): the smallest 2 * odd number >= v)
+ *     4 * ((16 * ceil(cin / 16) + 1) * CSx + 16 * ceil(cout / 16) * CSy) <= 163840 bytes     (+ 1: a row of ones, db's operand)
+ * -- 64 + 64 channels at 16 x 16 take 150 744 bytes; tall maps of very few columns and many channels do not
+ * (the pad column weighs most there: usf_conv_wgrad_wide_variant answers for a shape).  Returns 1 (nothing written) for other shapes, 0 when done, < 0 on error (nothing
+ * written either).  workspace: at least usf_conv_wgrad_wide_workspace(...) floats (0: shape not served); it depends on the
+ * device's compute units.  Small maps (H * W <= 64) are served too: the same sums as usf_conv_wgrad_f32 in another order.
+ * Two or three launches in stream order (the kernel, one or two rounds of the sum), no host synchronisation.
+ *
+ * usf_conv_wgrad_wide_variant: the plan such a call launches from, asked instead of launched (host only; q->masked is
+ * ignored: both forms run the same kernel; cus > 0 plans for that many compute units and blocks_per_cu > 0 for that
+ * residency -- with cus stated it needs no GPU).  served 0 / 1; tiles = COT * (CIT * T + 1) accumulator tiles (+ 1: db), dealt over
+ * wave_groups (2 or 4) groups of waves with tiles_per_wave each -- the kernel's instantiation, one of
+ * usf_conv_wgrad_wide_instances -- while position_parts = 4 / wave_groups waves share a tile and split the nch position chunks;
+ * blocks (the grid: min(B, cus * min(blocks_per_cu, 2))), lds_bytes, the staging geometry (S, q0, CSx, CSy, nch), nacc floats
+ * per partial slot, slots = blocks * position_parts summed in `rounds` (1 or 2) rounds, the first of two with rows_used rows
+ * of `per` slots; max_samples_per_block = ceil(B / blocks).
+ * usf_conv_wgrad_wide_instances: writes the tiles_per_wave values the kernel is instantiated for (up to cap) and returns
+ * their count.
+ */
+typedef struct usf_conv_wgrad_wide_info {
+  int32_t served, CIT, COT, T, tiles, tiles_per_wave, wave_groups, position_parts;
+  int32_t blocks, lds_bytes, S, q0, CSx, CSy, nch, nacc;
+  int32_t slots, rounds, per, rows_used, max_samples_per_block, blocks_per_cu, cus, reserved;
+} usf_conv_wgrad_wide_info;
+int64_t usf_conv_wgrad_wide_workspace(int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks);
+int usf_conv_wgrad_wide_f32(const float* x, const float* dy, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
+                            const float* in_mul, const float* pre_sub, int32_t in_act, float in_slope, float* dW, float* db,
+                            float* workspace, int64_t workspace_floats, usf_stream_t stream);
+int usf_conv_wgrad_wide_variant(const usf_conv_wgrad_query* q, usf_conv_wgrad_wide_info* out);
+int usf_conv_wgrad_wide_instances(int32_t* out, int32_t cap);
+
 /* usf_conv2d_weight_planes_f32(transposed = 2) for MANY weights in one launch.  jobs / block_job are DEVICE arrays (as for
  * usf_partial_sum_jobs_f32): job j splits the fp32 weight w [cout, cin, ks, ks] into its planes followed by the planes of its
  * data-gradient convolution, at planes_base + out_off (bf16 elements; usf_conv2d_weight_elems(cin, cout, ks) +

@@ -143,6 +143,13 @@ class LnBwdInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("kernel", "width", "blocks", "slots", "rounds", "per", "rows_used", "reserved")]
 
 
+class ConvWgradWideInfo(C.Structure):
+    """usf_conv_wgrad_wide_info: the instantiation, grid, staging geometry and reduction usf_conv_wgrad_wide_f32 launches"""
+    _fields_ = [(n, C.c_int32) for n in ("served", "CIT", "COT", "T", "tiles", "tiles_per_wave", "wave_groups", "position_parts",
+                                         "blocks", "lds_bytes", "S", "q0", "CSx", "CSy", "nch", "nacc", "slots", "rounds", "per",
+                                         "rows_used", "max_samples_per_block", "blocks_per_cu", "cus", "reserved")]
+
+
 CONV_ENTRIES = {"plain": 0, "ctx": 1, "res": 2, "gate_mul": 3, "gate_add": 4, "gated": 5}   # USF_CONV_ENTRY_*
 
 
@@ -233,7 +240,7 @@ class GradJob(C.Structure):
 SIZEOF_KINDS = {OP_LINEAR: LinearDesc, OP_COUPLING: CouplingDesc, 0: Op, 3: LuPrepDesc, 4: PackJob, OP_PACK_PLANES: PackPlanesDesc,
                 OP_GEMM_PLANES: GemmPlanesDesc, OP_COUPLING_PLANES: CouplingPlanesDesc, 8: MtChunk, OP_GATED_NORM: GatedNormDesc,
                 OP_CALL: CallDesc, 11: GradJob, 12: PsumJob, 13: GatedNormBwdDesc, 14: WgradJob, 15: WReduceJob, 16: WPlanesJob, 17: AdamChunk, 18: GradChunk,
-                19: ConvVariantQuery, 20: ConvVariant, 21: ConvWgradQuery, 22: ConvWgradInfo, 23: LnBwdInfo}
+                19: ConvVariantQuery, 20: ConvVariant, 21: ConvWgradQuery, 22: ConvWgradInfo, 23: LnBwdInfo, 24: ConvWgradWideInfo}
 
 
 # every symbol include/usflows_hip.h declares (the stable public ABI): (restype, argtypes)
@@ -323,6 +330,11 @@ INTERNAL_SYMBOLS = {
     "usf_conv_wgrad_variant": (C.c_int, [C.POINTER(ConvWgradQuery), C.POINTER(ConvWgradInfo)]),
     "usf_layernorm_channels_bwd_variant": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(LnBwdInfo)]),
     "usf_conv_wgrad_workspace": (C.c_int64, [C.c_int64] * 6),
+    "usf_conv_wgrad_wide_workspace": (C.c_int64, [C.c_int64] * 6),
+    "usf_conv_wgrad_wide_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [_fp, _fp, C.c_int32, C.c_float, _fp, _fp, _fp, C.c_int64,
+                                          C.c_void_p]),
+    "usf_conv_wgrad_wide_variant": (C.c_int, [C.POINTER(ConvWgradQuery), C.POINTER(ConvWgradWideInfo)]),
+    "usf_conv_wgrad_wide_instances": (C.c_int, [C.POINTER(C.c_int32), C.c_int32]),
     "usf_conv_wgrad_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [_fp, _fp, C.c_int32, C.c_float, _fp, _fp, _fp, C.c_int64,
                                      C.c_void_p]),
     "usf_conv_wgrad_deferred_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [_fp, _fp, C.c_int32, C.c_float, _fp, _fp, _fp, C.c_int64,

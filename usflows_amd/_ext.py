@@ -24,7 +24,7 @@ from ._abi import (  # noqa: E402,F401  -- the declarations, re-exported: caller
     BASE_LPNORM1, BASE_LPNORM2, BASE_LPNORMINF, BASE_ROWSUM, NORM_LOGNORMAL, NORM_GAMMA, NORM_RAW_PARAMS, NORM_WEIBULL, NORM_HALFNORMAL, NORM_CHI, RADIAL_MAX_K, OP_LINEAR,
     OP_COUPLING, OP_PACK_PLANES, OP_GEMM_PLANES, OP_COUPLING_PLANES, OP_GATED_NORM, OP_CALL, PLANES_BF16X3, PLANES_F16X2, CALL_FNS,
     FN_COUPLING_PLANES_CTX, FN_COUPLING_VCTX, FN_GEMM_PLANES_SIDE, FN_COUPLING_PLANES_SIDE, VCTX_MAX,
-    _fp, LinearDesc, CouplingDesc, PackPlanesDesc, GemmPlanesDesc, CouplingPlanesDesc, MtChunk, AdamChunk, GradChunk, ConvVariantQuery, ConvVariant, ConvWgradQuery, ConvWgradInfo, LnBwdInfo, CONV_ENTRIES, GatedNormDesc, GatedNormBwdDesc,
+    _fp, LinearDesc, CouplingDesc, PackPlanesDesc, GemmPlanesDesc, CouplingPlanesDesc, MtChunk, AdamChunk, GradChunk, ConvVariantQuery, ConvVariant, ConvWgradQuery, ConvWgradInfo, ConvWgradWideInfo, LnBwdInfo, CONV_ENTRIES, GatedNormDesc, GatedNormBwdDesc,
     CallDesc, _OpUnion, Op, LuPrepDesc, PackJob, PsumJob, WgradJob, WReduceJob, WPlanesJob, GradJob, SIZEOF_KINDS, PUBLIC_SYMBOLS,
     INTERNAL_SYMBOLS, SYMBOLS)
 
@@ -615,6 +615,24 @@ def conv_wgrad_variant(B, cin, cout, H, W, ks=3, masked=False, cus=0, blocks_per
     return {name: int(getattr(out, name)) for name, _ in ConvWgradInfo._fields_ if name != "reserved"}
 
 
+def conv_wgrad_wide_variant(B, cin, cout, H, W, ks=3, cus=0, blocks_per_cu=0) -> dict:
+    """usf_conv_wgrad_wide_variant: the plan usf_conv_wgrad_wide_f32 launches from for these sizes, as a dict of the answer's
+    fields (served 0: the call returns 1); cus / blocks_per_cu > 0 plan for that device answer (cus > 0: no GPU needed)"""
+    q = ConvWgradQuery(int(B), int(cin), int(cout), int(H), int(W), int(ks), 0, int(cus), int(blocks_per_cu), 0)
+    out = ConvWgradWideInfo()
+    check(load().usf_conv_wgrad_wide_variant(C.byref(q), C.byref(out)), "usf_conv_wgrad_wide_variant")
+    return {name: int(getattr(out, name)) for name, _ in ConvWgradWideInfo._fields_ if name != "reserved"}
+
+
+def conv_wgrad_wide_instances() -> list:
+    """usf_conv_wgrad_wide_instances: the tiles-per-wave values usf_conv_wgrad_wide.hip instantiates its kernel for"""
+    lib = load()
+    n = lib.usf_conv_wgrad_wide_instances(None, 0)
+    buf = (C.c_int32 * n)()
+    lib.usf_conv_wgrad_wide_instances(buf, n)
+    return list(buf)
+
+
 def layernorm_channels_bwd_variant(B, C_, P) -> dict:
     """usf_layernorm_channels_bwd_variant: the kernel (1 / 2), its width (CMAX / CPT), grid and reduction rounds of
     usf_layernorm_channels_bwd_f32 for these sizes (kernel 0: refused)"""
@@ -947,6 +965,23 @@ def conv_wgrad(x, dy, ks, in_mul=None, pre_sub=None, in_act=ACT_NONE, in_slope=0
         return None
     _psum_queue(job2, (ws,))
     return dW, db
+
+
+def conv_wgrad_wide(x, dy, ks, in_mul=None, pre_sub=None, in_act=ACT_NONE, in_slope=0.0, want_bias=True):
+    """usf_conv_wgrad_wide_f32: conv_wgrad's (dW, db | None) for feature maps of up to 256 pixels and any channel counts up to 64;
+    None when the shape is not served.  Never deferred or queued: its launches follow each other in the current stream with no
+    host synchronisation, so a captured training step replays them"""
+    B, cin, H, W = x.shape
+    cout = dy.shape[1]
+    ws_n = load().usf_conv_wgrad_wide_workspace(B, cin, cout, H, W, ks)
+    if ws_n <= 0:
+        return None
+    ws = torch.empty(ws_n, dtype=torch.float32, device=x.device)
+    dW = torch.empty(cout, cin, ks, ks, dtype=torch.float32, device=x.device)
+    db = torch.empty(cout, dtype=torch.float32, device=x.device) if want_bias else None
+    rc = _launch("usf_conv_wgrad_wide_f32", (x.data_ptr(), dy.data_ptr(), B, cin, cout, H, W, ks, ptr(in_mul), ptr(pre_sub), int(in_act),
+                 float(in_slope), dW.data_ptr(), ptr(db), ws.data_ptr(), ws_n, current_stream(x.device)), tape=False, unserved_ok=True)
+    return None if rc else (dW, db)
 
 
 def layernorm_channels_bwd(x, dy, gamma, eps, act=ACT_NONE, slope=0.0):

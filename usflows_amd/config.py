@@ -62,6 +62,7 @@ class Config:
         batch_wplanes=True,        # image training, launch-bound batches: all convolution weights' planes from one launch per pass
         gated_tail_infer_max_pixels=1 << 14,   # inference: the same kernel instead of the one-thread-per-pixel pass up to this many pixels
         gated_tail_max_pixels=1 << 16,   # ... up to this many pixels (eight lanes share a pixel: made for few pixels)
+        wgrad_wide=True,           # image training, feature maps of 65 .. 256 pixels: weight gradients on usf_conv_wgrad_wide_f32 (0: torch autograd + MIOpen there)
         gated_tail=True,           # image training, few pixels: GatedConv's 1x1 conv + gate + ReLU + layer norm as one launch each way
     )
 

@@ -248,6 +248,7 @@ int usf_sizeof_desc(int32_t kind) {
     case 21: return (int)sizeof(usf_conv_wgrad_query);
     case 22: return (int)sizeof(usf_conv_wgrad_info);
     case 23: return (int)sizeof(usf_ln_bwd_info);
+    case 24: return (int)sizeof(usf_conv_wgrad_wide_info);
     default: return -1;
   }
 }

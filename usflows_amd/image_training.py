@@ -6,7 +6,8 @@ Each ``torch.autograd.Function`` here is one device pass of the inference path w
 
 * data gradients reuse the forward kernels on the transposed (and, for 3 x 3, flipped) weight:
   ``usf_conv2d_same_f32``, ``usf_pointwise_conv_f32``, ``usf_channel_affine_f32``;
-* weight / bias gradients come from ``usf_conv_wgrad_f32`` (exact fp32 on the f32 matrix instruction, deterministic);
+* weight / bias gradients come from ``usf_conv_wgrad_f32`` (exact fp32 on the f32 matrix instruction, deterministic) and, for
+  feature maps of 65 .. 256 pixels, from ``usf_conv_wgrad_wide_f32`` (same contract; knob ``wgrad_wide``);
 * ``usf_layernorm_channels_bwd_f32``, ``usf_gated_residual_bwd_f32``, ``usf_act_grad_f32``, ``usf_masked_residual_f32`` and
   ``usf_base_logprob_grad_f32`` cover the elementwise pieces.
 
@@ -36,10 +37,44 @@ def _gate_inplace(d: torch.Tensor, h: torch.Tensor, act) -> None:
     _ext.act_grad(d, h, M=B, H=n, ldd=n, ldh=n, act=act[0], slope=act[1])
 
 
-def wgrad_served(B: int, cin: int, cout: int, H: int, W: int, ks: int, masked: bool) -> bool:
-    """does usf_conv_wgrad_f32 serve this call -- with an input mask (in_mul) or without?  The two forms differ: 64 -> 64
-    channels at kernel 1 and 57 .. 64 pixels run without a mask only (usf_conv_wgrad_workspace > 0 says that ONE form is served)"""
+WIDE_MIN_PIXELS = 65      # feature maps of 65 .. 256 pixels: usf_conv_wgrad_f32 refuses them, usf_conv_wgrad_wide_f32 serves them
+
+
+def wide_wgrad_served(B: int, cin: int, cout: int, H: int, W: int, ks: int) -> bool:
+    """does usf_conv_wgrad_wide_f32 take over this call?  Only above 64 pixels (below, usf_conv_wgrad_f32 alone decides, as it
+    always did) and only while the knob ``config.wgrad_wide`` is on"""
+    return (config.wgrad_wide and H * W >= WIDE_MIN_PIXELS
+            and _ext.load().usf_conv_wgrad_wide_workspace(max(B, 1), cin, cout, H, W, ks) > 0)
+
+
+def _narrow_wgrad_served(B: int, cin: int, cout: int, H: int, W: int, ks: int, masked: bool) -> bool:
     return _ext.conv_wgrad_variant(max(B, 1), cin, cout, H, W, ks, masked)["kernel"] != 0
+
+
+def wgrad_served(B: int, cin: int, cout: int, H: int, W: int, ks: int, masked: bool) -> bool:
+    """does a weight-gradient kernel serve this call -- with an input mask (in_mul) or without?  Up to 64 pixels
+    usf_conv_wgrad_f32, whose two forms differ: 64 -> 64 channels at kernel 1 and 57 .. 64 pixels run without a mask only
+    (usf_conv_wgrad_workspace > 0 says that ONE form is served); above, usf_conv_wgrad_wide_f32 (one kernel for both forms)"""
+    if H * W >= WIDE_MIN_PIXELS:
+        return wide_wgrad_served(B, cin, cout, H, W, ks)
+    return _narrow_wgrad_served(B, cin, cout, H, W, ks, masked)
+
+
+def _wgrad_workspace_ok(B: int, cin: int, cout: int, H: int, W: int) -> bool:
+    """the kernel-1 weight gradient of a pointwise convolution / an affine block is served (either kernel's workspace > 0)"""
+    if H * W >= WIDE_MIN_PIXELS:
+        return wide_wgrad_served(B, cin, cout, H, W, 1)
+    return _ext.load().usf_conv_wgrad_workspace(max(B, 1), cin, cout, H, W, 1) > 0
+
+
+def conv_wgrad(x, dy, ks, in_mul=None, pre_sub=None, in_act=_ext.ACT_NONE, in_slope=0.0, want_bias=True, defer=False, owners=()):
+    """(dW, db | None) of a convolution's backward, or None: ``_ext.conv_wgrad`` as ever; where it declines a feature map of
+    more than 64 pixels, ``_ext.conv_wgrad_wide`` (never deferred: its sums run in stream order)"""
+    r = _ext.conv_wgrad(x, dy, ks, in_mul=in_mul, pre_sub=pre_sub, in_act=in_act, in_slope=in_slope, want_bias=want_bias,
+                        defer=defer, owners=owners)
+    if r is None and config.wgrad_wide and x.shape[2] * x.shape[3] >= WIDE_MIN_PIXELS:
+        r = _ext.conv_wgrad_wide(x, dy, ks, in_mul=in_mul, pre_sub=pre_sub, in_act=in_act, in_slope=in_slope, want_bias=want_bias)
+    return r
 
 
 def conv_shape_ok(conv, B: int, H: int, W: int, masked: bool = False) -> bool:
@@ -179,10 +214,10 @@ class ConvSame(torch.autograd.Function):
         ia = _act(in_act)
         dW = db = dx = None
         if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            r = _ext.conv_wgrad(x, dy, ks, in_mul=in_mul, in_act=ia[0], in_slope=ia[1], want_bias=has_bias,
+            r = conv_wgrad(x, dy, ks, in_mul=in_mul, in_act=ia[0], in_slope=ia[1], want_bias=has_bias,
                                 defer=_takeable(ctx.params), owners=tuple(id(q) for q in ctx.params if q is not None))
             if r is None:
-                raise RuntimeError("usflows_amd: usf_conv_wgrad_f32 does not serve this shape (conv_shape_ok was not consulted)")
+                raise RuntimeError("usflows_amd: neither usf_conv_wgrad_f32 nor usf_conv_wgrad_wide_f32 serves this shape (conv_shape_ok was not consulted)")
             dW, db = r
         if ctx.needs_input_grad[0]:
             planes_t = ctx.planes_t if ctx.planes_t is not None else _ext.conv2d_weight_planes(w, transposed=True)
@@ -232,10 +267,10 @@ class ConvSameRes(torch.autograd.Function):
         dt = _ext.masked_residual(None, dy, om, sign)
         dW = db = dx = None
         if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            r = _ext.conv_wgrad(x, dt, ks, want_bias=has_bias, defer=_takeable(ctx.params),
+            r = conv_wgrad(x, dt, ks, want_bias=has_bias, defer=_takeable(ctx.params),
                                 owners=tuple(id(q) for q in ctx.params if q is not None))
             if r is None:
-                raise RuntimeError("usflows_amd: usf_conv_wgrad_f32 does not serve this shape")
+                raise RuntimeError("usflows_amd: neither usf_conv_wgrad_f32 nor usf_conv_wgrad_wide_f32 serves this shape")
             dW, db = r
         if ctx.needs_input_grad[0]:
             planes_t = ctx.planes_t if ctx.planes_t is not None else _ext.conv2d_weight_planes(w, transposed=True)
@@ -272,10 +307,10 @@ class ConvSameFork(torch.autograd.Function):
         ia = _act(in_act)
         dW = db = dx = None
         if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            r = _ext.conv_wgrad(x, dy, ks, in_mul=in_mul, in_act=ia[0], in_slope=ia[1], want_bias=has_bias,
+            r = conv_wgrad(x, dy, ks, in_mul=in_mul, in_act=ia[0], in_slope=ia[1], want_bias=has_bias,
                                 defer=_takeable(ctx.params), owners=tuple(id(q) for q in ctx.params if q is not None))
             if r is None:
-                raise RuntimeError("usflows_amd: usf_conv_wgrad_f32 does not serve this shape")
+                raise RuntimeError("usflows_amd: neither usf_conv_wgrad_f32 nor usf_conv_wgrad_wide_f32 serves this shape")
             dW, db = r
         if ctx.needs_input_grad[0]:
             planes_t = ctx.planes_t if ctx.planes_t is not None else _ext.conv2d_weight_planes(w, transposed=True)
@@ -330,9 +365,9 @@ class ConvSameCtxFork(torch.autograd.Function):
         dW = db = dx = None
         if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
             # (not deferred: the data columns are joined with the context column here, in this pass)
-            r = _ext.conv_wgrad(x, dy, ks, in_mul=in_mul, want_bias=has_bias)
+            r = conv_wgrad(x, dy, ks, in_mul=in_mul, want_bias=has_bias)
             if r is None:
-                raise RuntimeError("usflows_amd: usf_conv_wgrad_f32 does not serve this shape")
+                raise RuntimeError("usflows_amd: neither usf_conv_wgrad_f32 nor usf_conv_wgrad_wide_f32 serves this shape")
             dWd, db = r
             dW = torch.cat([dWd, _ext.conv_ctx_wgrad(dy, ctx_rows, ks).view(cout, 1, ks, ks)], 1)
         if ctx.needs_input_grad[0]:
@@ -365,7 +400,8 @@ def conv_ctx_shape_ok(conv, B: int, H: int, W: int) -> bool:
     lib = _ext.load()
     C, cout = conv.in_channels - 1, conv.out_channels
     return (lib.usf_conv2d_same_fits(C, cout, H, W, k[0]) >= 2 and lib.usf_conv2d_same_fits(cout, C, H, W, k[0]) >= 2
-            and wgrad_served(B, C, cout, H, W, k[0], True))            # (the first convolution: it may be handed the coupling's mask)
+            and _narrow_wgrad_served(B, C, cout, H, W, k[0], True))    # (the first convolution: it may be handed the coupling's mask;
+                                                                       # above 64 pixels conditional conditioners stay declined)
 
 
 class Pointwise(torch.autograd.Function):
@@ -390,9 +426,9 @@ class Pointwise(torch.autograd.Function):
         ia = _act(in_act)
         dW = db = dx = None
         if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            r = _ext.conv_wgrad(x, dy, 1, in_act=ia[0], in_slope=ia[1], want_bias=has_bias, defer=_takeable(ctx.params), owners=tuple(id(q) for q in ctx.params if q is not None))
+            r = conv_wgrad(x, dy, 1, in_act=ia[0], in_slope=ia[1], want_bias=has_bias, defer=_takeable(ctx.params), owners=tuple(id(q) for q in ctx.params if q is not None))
             if r is None:
-                raise RuntimeError("usflows_amd: usf_conv_wgrad_f32 does not serve this shape")
+                raise RuntimeError("usflows_amd: neither usf_conv_wgrad_f32 nor usf_conv_wgrad_wide_f32 serves this shape")
             dW, db = r[0].reshape(wshape), r[1]
         if ctx.needs_input_grad[0]:
             if in_act is not None and ia[0] == _ext.ACT_LEAKY_RELU:
@@ -412,7 +448,7 @@ def pointwise_shape_ok(conv, B: int, H: int, W: int) -> bool:
         return False
     cin, cout = conv.in_channels, conv.out_channels
     return (_ext.pointwise_conv_supported(cin, cout, False) and _ext.pointwise_conv_supported(cout, cin, False)
-            and _ext.load().usf_conv_wgrad_workspace(max(B, 1), cin, cout, H, W, 1) > 0)
+            and _wgrad_workspace_ok(B, cin, cout, H, W))
 
 
 class GatedResidual(torch.autograd.Function):
@@ -443,6 +479,8 @@ def gated_tail_ok(conv2, x, ln=None) -> bool:
     if not (pad == "same" or (not isinstance(pad, str) and tuple(pad) == (0, 0))):
         return False
     B, Cc, H, W = x.shape
+    if H * W >= WIDE_MIN_PIXELS:
+        return False        # the fused tail's backward carries usf_conv_wgrad_f32's weight gradient: up to 64 pixels, the two-pass form above
     if not (conv2.in_channels == Cc and conv2.out_channels == 2 * Cc and 0 < B * H * W <= config.gated_tail_max_pixels
             and _ext.gated_tail_supported(Cc)):
         return False
@@ -555,9 +593,9 @@ class ChannelAffine(torch.autograd.Function):
         dy = dy.contiguous()
         dx = dW = db = None
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            r = _ext.conv_wgrad(x, dy, 1, pre_sub=bd if ctx.pre_sub else None, want_bias=True, defer=ctx.defer, owners=(id(ctx),))
+            r = conv_wgrad(x, dy, 1, pre_sub=bd if ctx.pre_sub else None, want_bias=True, defer=ctx.defer, owners=(id(ctx),))
             if r is None:
-                raise RuntimeError("usflows_amd: usf_conv_wgrad_f32 does not serve this channel count")
+                raise RuntimeError("usflows_amd: neither usf_conv_wgrad_f32 nor usf_conv_wgrad_wide_f32 serves this channel count")
             dW = r[0].reshape(Wd.shape)
             db = -(Wd.t() @ r[1]) if ctx.pre_sub else r[1]
         if ctx.needs_input_grad[0]:
@@ -568,7 +606,7 @@ class ChannelAffine(torch.autograd.Function):
 
 def channel_affine_train_ok(x, C) -> bool:
     return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == C and C in (16, 32, 48, 64)
-            and _ext.load().usf_conv_wgrad_workspace(max(x.shape[0], 1), C, C, x.shape[2], x.shape[3], 1) > 0)
+            and _wgrad_workspace_ok(x.shape[0], C, C, x.shape[2], x.shape[3]))
 
 
 class BaseLogProb(torch.autograd.Function):
