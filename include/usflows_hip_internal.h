@@ -415,6 +415,45 @@ int usf_gated_tail_bwd_f32(const float* h, const float* x, const float* dy, floa
                            float post_slope, const float* ln_gamma, const float* ln_beta, float ln_eps, float* dparams,
                            float* workspace, int64_t workspace_floats, struct usf_psum_job* job, usf_stream_t stream);
 
+/*
+ * usf_channel_affine_bwd_f32 (an addition: USF_INTERNAL_VERSION is unchanged): the WHOLE backward of usf_channel_affine_f32
+ * (usflows_hip.h) with few channels in ONE launch plus the sum over its per-block slots -- contiguous fp32 [B, C, P] tensors:
+ *     dx[b, c', p] = sum_c W[c, c'] * dy[b, c, p]                       (W [C, C] as the forward used it; dx may be NULL)
+ *     dW[c, c']    = sum_{b, p} dy[b, c, p] * (x[b, c', p] - pre_sub[c'])    (pre_sub [C] or NULL)
+ *     db[c]        = sum_{b, p} dy[b, c, p]                             (db may be NULL; else db == dW + C * C: the last sum
+ *                                                                        writes dW and db as one buffer of C * C + C floats)
+ * Served: 1 <= C <= 12, any P >= 1, any B >= 1; other sizes return 1 and write nothing; B == 0 returns 0 and writes nothing;
+ * < 0 on error (nothing written either).  A thread owns whole pixels and keeps the C^2 + C sums in registers (channels padded
+ * to 4, 8 or 12; channels >= C are never loaded or stored); 16-byte loads and stores where P % 4 == 0 and x, dy, dx are 16-byte
+ * aligned, one float at a time otherwise.  Exact fp32: fmaf chains in ascending channel order, every thread's pixels in
+ * ascending order, a fixed shuffle order inside a wave, the four waves in ascending order through LDS, one slot per block,
+ * the slots by the sum usf_gated_tail_bwd_f32 uses (job == NULL: at once; else job[0 .. 1], HOST memory, describe it for
+ * usf_partial_sum_jobs_f32 as usf_conv_wgrad_deferred_f32 does).  The grid depends on the sizes and the form alone -- at most
+ * 256 blocks; the tuning aid channel_affine_bwd_blocks > 0 lowers that cap (tests: several loop trips at a small size) --
+ * so two runs give the same bits.  No matrix instructions, no atomics.
+ * workspace: at least usf_channel_affine_bwd_workspace(B, C, P) floats (0: sizes not served; host only).
+ * usf_channel_affine_bwd_variant (host only, launches nothing): the plan such a call launches from.  Query: the sizes,
+ * aligned16 (1: x, dy and dx are 16-byte aligned), want_bias (1: db is asked for), grid_cap (> 0: plan for this cap on the grid
+ * instead of the tuning aid's / the default -- works without a GPU, as everything here does).  Answer: served 0 / 1, width
+ * (4 / 8 / 12: the instantiation's padded channel count), vec (1: the 16-byte form), blocks, trips (loop trips of the busiest
+ * thread), slot_floats (C * C [+ C]), slots (= blocks) summed in `rounds` (1 or 2) rounds, the first of two with rows_used rows
+ * of `per` slots; grid_cap: the cap the plan was made with.  Returns 0 or -1 (null pointer).
+ * usf_sizeof_desc reports sizeof(usf_channel_affine_bwd_query|usf_channel_affine_bwd_info) for kind 25|26.
+ */
+typedef struct usf_channel_affine_bwd_query {
+  int64_t B, C, P;
+  int32_t aligned16, want_bias, grid_cap, reserved;
+} usf_channel_affine_bwd_query;
+typedef struct usf_channel_affine_bwd_info {
+  int32_t served, width, vec, blocks, trips, slot_floats;
+  int32_t slots, rounds, per, rows_used, grid_cap, reserved;
+} usf_channel_affine_bwd_info;
+int64_t usf_channel_affine_bwd_workspace(int64_t B, int64_t C, int64_t P);
+int usf_channel_affine_bwd_f32(const float* x, const float* dy, float* dx, int64_t B, int64_t C, int64_t P, const float* W,
+                               const float* pre_sub, float* dW, float* db, float* workspace, int64_t workspace_floats,
+                               struct usf_psum_job* job, usf_stream_t stream);
+int usf_channel_affine_bwd_variant(const usf_channel_affine_bwd_query* q, usf_channel_affine_bwd_info* out);
+
 /* A data-gradient convolution with the factors of the layer's INPUT transforms in its output stream:
  *   y = conv(x) * (gate_h > 0 ? 1 : gate_slope) * gate_mul          (gate_add == NULL)
  *   y = gate_add + conv(x) * (gate_h > 0 ? 1 : gate_slope)          (gate_add != NULL; then gate_mul must be NULL)

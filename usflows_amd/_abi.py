@@ -150,6 +150,19 @@ class ConvWgradWideInfo(C.Structure):
                                          "rows_used", "max_samples_per_block", "blocks_per_cu", "cus", "reserved")]
 
 
+class ChannelAffineBwdQuery(C.Structure):
+    """usf_channel_affine_bwd_query: one call of usf_channel_affine_bwd_f32, as usf_channel_affine_bwd_variant is asked about it"""
+    _fields_ = [("B", C.c_int64), ("C", C.c_int64), ("P", C.c_int64),
+                ("aligned16", C.c_int32), ("want_bias", C.c_int32), ("grid_cap", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ChannelAffineBwdInfo(C.Structure):
+    """usf_channel_affine_bwd_info: the instantiation (padded width, 16-byte or scalar form), grid, loop trips and reduction
+    usf_channel_affine_bwd_f32 launches"""
+    _fields_ = [(n, C.c_int32) for n in ("served", "width", "vec", "blocks", "trips", "slot_floats", "slots", "rounds", "per",
+                                         "rows_used", "grid_cap", "reserved")]
+
+
 CONV_ENTRIES = {"plain": 0, "ctx": 1, "res": 2, "gate_mul": 3, "gate_add": 4, "gated": 5}   # USF_CONV_ENTRY_*
 
 
@@ -240,7 +253,8 @@ class GradJob(C.Structure):
 SIZEOF_KINDS = {OP_LINEAR: LinearDesc, OP_COUPLING: CouplingDesc, 0: Op, 3: LuPrepDesc, 4: PackJob, OP_PACK_PLANES: PackPlanesDesc,
                 OP_GEMM_PLANES: GemmPlanesDesc, OP_COUPLING_PLANES: CouplingPlanesDesc, 8: MtChunk, OP_GATED_NORM: GatedNormDesc,
                 OP_CALL: CallDesc, 11: GradJob, 12: PsumJob, 13: GatedNormBwdDesc, 14: WgradJob, 15: WReduceJob, 16: WPlanesJob, 17: AdamChunk, 18: GradChunk,
-                19: ConvVariantQuery, 20: ConvVariant, 21: ConvWgradQuery, 22: ConvWgradInfo, 23: LnBwdInfo, 24: ConvWgradWideInfo}
+                19: ConvVariantQuery, 20: ConvVariant, 21: ConvWgradQuery, 22: ConvWgradInfo, 23: LnBwdInfo, 24: ConvWgradWideInfo,
+                25: ChannelAffineBwdQuery, 26: ChannelAffineBwdInfo}
 
 
 # every symbol include/usflows_hip.h declares (the stable public ABI): (restype, argtypes)
@@ -349,6 +363,9 @@ INTERNAL_SYMBOLS = {
     "usf_gated_residual_bwd_f32": (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int64, C.c_void_p]),
     "usf_conv2d_weight_planes_batch_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "usf_gated_tail_workspace": (C.c_int64, [C.c_int64] * 3),
+    "usf_channel_affine_bwd_workspace": (C.c_int64, [C.c_int64] * 3),
+    "usf_channel_affine_bwd_f32": (C.c_int, [_fp, _fp, _fp] + [C.c_int64] * 3 + [_fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_void_p, C.c_void_p]),
+    "usf_channel_affine_bwd_variant": (C.c_int, [C.POINTER(ChannelAffineBwdQuery), C.POINTER(ChannelAffineBwdInfo)]),
     "usf_gated_tail_bwd_f32": (C.c_int, [_fp] * 6 + [C.c_int64] * 3 + [_fp, _fp, C.c_int32, C.c_float, C.c_int32, C.c_float, _fp, _fp,
                                          C.c_float, _fp, _fp, C.c_int64, C.c_void_p, C.c_void_p]),
     "usf_lu_grad_finish_f64": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_int64, _fp, _fp, C.c_void_p]),

@@ -24,7 +24,7 @@ from ._abi import (  # noqa: E402,F401  -- the declarations, re-exported: caller
     BASE_LPNORM1, BASE_LPNORM2, BASE_LPNORMINF, BASE_ROWSUM, NORM_LOGNORMAL, NORM_GAMMA, NORM_RAW_PARAMS, NORM_WEIBULL, NORM_HALFNORMAL, NORM_CHI, RADIAL_MAX_K, OP_LINEAR,
     OP_COUPLING, OP_PACK_PLANES, OP_GEMM_PLANES, OP_COUPLING_PLANES, OP_GATED_NORM, OP_CALL, PLANES_BF16X3, PLANES_F16X2, CALL_FNS,
     FN_COUPLING_PLANES_CTX, FN_COUPLING_VCTX, FN_GEMM_PLANES_SIDE, FN_COUPLING_PLANES_SIDE, VCTX_MAX,
-    _fp, LinearDesc, CouplingDesc, PackPlanesDesc, GemmPlanesDesc, CouplingPlanesDesc, MtChunk, AdamChunk, GradChunk, ConvVariantQuery, ConvVariant, ConvWgradQuery, ConvWgradInfo, ConvWgradWideInfo, LnBwdInfo, CONV_ENTRIES, GatedNormDesc, GatedNormBwdDesc,
+    _fp, LinearDesc, CouplingDesc, PackPlanesDesc, GemmPlanesDesc, CouplingPlanesDesc, MtChunk, AdamChunk, GradChunk, ConvVariantQuery, ConvVariant, ConvWgradQuery, ConvWgradInfo, ConvWgradWideInfo, ChannelAffineBwdQuery, ChannelAffineBwdInfo, LnBwdInfo, CONV_ENTRIES, GatedNormDesc, GatedNormBwdDesc,
     CallDesc, _OpUnion, Op, LuPrepDesc, PackJob, PsumJob, WgradJob, WReduceJob, WPlanesJob, GradJob, SIZEOF_KINDS, PUBLIC_SYMBOLS,
     INTERNAL_SYMBOLS, SYMBOLS)
 
@@ -633,6 +633,16 @@ def conv_wgrad_wide_instances() -> list:
     return list(buf)
 
 
+def channel_affine_bwd_variant(B, C_, P, aligned=True, want_bias=True, grid_cap=0) -> dict:
+    """usf_channel_affine_bwd_variant: the plan usf_channel_affine_bwd_f32 launches from for these sizes, as a dict of the
+    answer's fields (served 0: the call returns 1); aligned: the tensors are 16-byte aligned; grid_cap > 0 plans for that cap on
+    the grid.  Host only: no GPU needed"""
+    q = ChannelAffineBwdQuery(int(B), int(C_), int(P), int(bool(aligned)), int(bool(want_bias)), int(grid_cap), 0)
+    out = ChannelAffineBwdInfo()
+    check(load().usf_channel_affine_bwd_variant(C.byref(q), C.byref(out)), "usf_channel_affine_bwd_variant")
+    return {name: int(getattr(out, name)) for name, _ in ChannelAffineBwdInfo._fields_ if name != "reserved"}
+
+
 def layernorm_channels_bwd_variant(B, C_, P) -> dict:
     """usf_layernorm_channels_bwd_variant: the kernel (1 / 2), its width (CMAX / CPT), grid and reduction rounds of
     usf_layernorm_channels_bwd_f32 for these sizes (kernel 0: refused)"""
@@ -1049,6 +1059,33 @@ def gated_tail_bwd(h, x, dy, W, bias, in_act=ACT_NONE, in_slope=0.0, post_act=AC
     if ln is None:
         return dx, dh, dW, db, None, None, dvg
     return dx, dh, dW, db, dpar[nW + 2 * Cc: nW + 3 * Cc], dpar[nW + 3 * Cc:], dvg
+
+
+def channel_affine_bwd(x, dy, W, pre_sub=None, want_dx=True, want_bias=True, defer=False, owners=()):
+    """usf_channel_affine_bwd_f32: (dx | None, dW [C, C], db [C] | None) of a channel-affine layer y = W (x - pre_sub) [+ b] on
+    contiguous [B, C, *spatial] fp32 tensors, 1 <= C <= 12, in one launch (dx = W^T dy from W as the forward used it); None when
+    the sizes are not served.  dW and db are views of one buffer.  defer / owners as in conv_wgrad: the last sum may be queued
+    until the backward pass ends (dx is complete in stream order either way)"""
+    B, Cc = x.shape[0], x.shape[1]
+    P = math.prod(x.shape[2:])
+    ws_n = load().usf_channel_affine_bwd_workspace(max(B, 1), Cc, P)
+    if ws_n <= 0:
+        return None
+    if B == 0:                                   # (an empty batch: the entry point launches nothing; the sums are zero)
+        dpar = torch.zeros(Cc * Cc + Cc, dtype=torch.float32, device=x.device)
+        return (torch.empty_like(x) if want_dx else None), dpar[:Cc * Cc].view(Cc, Cc), dpar[Cc * Cc:] if want_bias else None
+    ws = torch.empty(ws_n, dtype=torch.float32, device=x.device)
+    dx = torch.empty_like(x) if want_dx else None
+    dpar = torch.empty(Cc * Cc + (Cc if want_bias else 0), dtype=torch.float32, device=x.device)
+    job2 = (PsumJob * 2)() if (defer and _psum_may_defer(x, owners)) else None
+    args = (x.data_ptr(), dy.data_ptr(), ptr(dx), B, Cc, P, W.data_ptr(), ptr(pre_sub), dpar.data_ptr(),
+            dpar.data_ptr() + 4 * Cc * Cc if want_bias else None, ws.data_ptr(), ws_n,
+            C.cast(job2, C.c_void_p) if job2 is not None else None, current_stream(x.device))
+    if _launch("usf_channel_affine_bwd_f32", args, tape=False, unserved_ok=True):
+        return None
+    if job2 is not None:
+        _psum_queue(job2, (ws,))
+    return dx, dpar[:Cc * Cc].view(Cc, Cc), dpar[Cc * Cc:] if want_bias else None
 
 
 AFFINE_PREP_MAX_C = 64

@@ -63,6 +63,8 @@ class Config:
         gated_tail_infer_max_pixels=1 << 14,   # inference: the same kernel instead of the one-thread-per-pixel pass up to this many pixels
         gated_tail_max_pixels=1 << 16,   # ... up to this many pixels (eight lanes share a pixel: made for few pixels)
         wgrad_wide=True,           # image training, feature maps of 65 .. 256 pixels: weight gradients on usf_conv_wgrad_wide_f32 (0: torch autograd + MIOpen there)
+        affine_small_c=True,       # image training, affine blocks of up to 12 channels: the whole backward on usf_channel_affine_bwd_f32 (0: torch autograd there)
+        gated_tail_wide=False,     # image training, feature maps of 65 .. 256 pixels: the fused gated tail there too (off: the two-pass form; measured beyond the spread at batch 32 only, profiles/affine_small_c_bench.json)
         gated_tail=True,           # image training, few pixels: GatedConv's 1x1 conv + gate + ReLU + layer norm as one launch each way
     )
 

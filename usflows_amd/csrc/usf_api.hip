@@ -143,6 +143,11 @@ int conv_wgrad_jobs(const usf_wgrad_job* jobs, const int32_t* block_job, int64_t
 int partial_sum_jobs(const usf_psum_job* jobs, const int32_t* block_job, int64_t n_blocks, hipStream_t stream);
 int conv2d_weight_planes_batch(const usf_wplanes_job* jobs, const int32_t* block_job, int64_t n_blocks, void* planes_base,
                                hipStream_t stream);
+int64_t channel_affine_bwd_workspace(int64_t B, int64_t C, int64_t P);
+int channel_affine_bwd(const float* x, const float* dy, float* dx, int64_t B, int64_t C, int64_t P, const float* W,
+                       const float* pre_sub, float* dW, float* db, float* workspace, int64_t workspace_floats, usf_psum_job* job,
+                       hipStream_t stream);
+int channel_affine_bwd_variant(const usf_channel_affine_bwd_query* q, usf_channel_affine_bwd_info* out);
 int gated_tail_supported(int64_t C);
 int64_t gated_tail_workspace(int64_t B, int64_t C, int64_t P);
 int gated_tail_fwd(const float* h, const float* x, float* y, int64_t B, int64_t C, int64_t P, const float* W, const float* bias,
@@ -249,6 +254,8 @@ int usf_sizeof_desc(int32_t kind) {
     case 22: return (int)sizeof(usf_conv_wgrad_info);
     case 23: return (int)sizeof(usf_ln_bwd_info);
     case 24: return (int)sizeof(usf_conv_wgrad_wide_info);
+    case 25: return (int)sizeof(usf_channel_affine_bwd_query);
+    case 26: return (int)sizeof(usf_channel_affine_bwd_info);
     default: return -1;
   }
 }
@@ -480,6 +487,15 @@ int usf_gated_residual_bwd_f32(const float* dy, const float* vg, float* dvg, int
 int usf_conv2d_weight_planes_batch_f32(const usf_wplanes_job* jobs, const int32_t* block_job, int64_t n_blocks, void* planes_base,
                                        usf_stream_t stream) {
   return usf::conv2d_weight_planes_batch(jobs, block_job, n_blocks, planes_base, (hipStream_t)stream);
+}
+int64_t usf_channel_affine_bwd_workspace(int64_t B, int64_t C, int64_t P) { return usf::channel_affine_bwd_workspace(B, C, P); }
+int usf_channel_affine_bwd_f32(const float* x, const float* dy, float* dx, int64_t B, int64_t C, int64_t P, const float* W,
+                               const float* pre_sub, float* dW, float* db, float* workspace, int64_t workspace_floats,
+                               usf_psum_job* job, usf_stream_t stream) {
+  return usf::channel_affine_bwd(x, dy, dx, B, C, P, W, pre_sub, dW, db, workspace, workspace_floats, job, (hipStream_t)stream);
+}
+int usf_channel_affine_bwd_variant(const usf_channel_affine_bwd_query* q, usf_channel_affine_bwd_info* out) {
+  return usf::channel_affine_bwd_variant(q, out);
 }
 int usf_gated_tail_supported(int64_t C) { return usf::gated_tail_supported(C); }
 int64_t usf_gated_tail_workspace(int64_t B, int64_t C, int64_t P) { return usf::gated_tail_workspace(B, C, P); }

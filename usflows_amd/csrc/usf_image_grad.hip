@@ -385,8 +385,9 @@ __global__ __launch_bounds__(256) void partial_sum_jobs_kernel(const usf_psum_jo
 constexpr int kReduceRows = 64;        // scratch rows of the two-round sum (workspace: kReduceRows * n floats behind the slots)
 
 // the rounds of the sum of `nparts` slots: 1 up to 64 slots; else 2: a first round of `used` rows (<= kReduceRows) of `per` slots
-// each, the last row possibly shorter.  Every caller below -- and the probes -- take the geometry from here.
-static int reduce_rounds(int nparts, int& per, int& used) {
+// each, the last row possibly shorter.  Every caller below -- and the probes -- take the geometry from here (so does
+// usf_channel_affine_bwd.hip's variant query).
+int reduce_rounds(int nparts, int& per, int& used) {
   per = nparts;
   used = 1;
   if (nparts <= 64) return 1;

@@ -8,6 +8,8 @@ Each ``torch.autograd.Function`` here is one device pass of the inference path w
   ``usf_conv2d_same_f32``, ``usf_pointwise_conv_f32``, ``usf_channel_affine_f32``;
 * weight / bias gradients come from ``usf_conv_wgrad_f32`` (exact fp32 on the f32 matrix instruction, deterministic) and, for
   feature maps of 65 .. 256 pixels, from ``usf_conv_wgrad_wide_f32`` (same contract; knob ``wgrad_wide``);
+* an affine block of up to 12 channels takes its whole backward (dx, dW, db) from ONE launch of
+  ``usf_channel_affine_bwd_f32`` (knob ``affine_small_c``);
 * ``usf_layernorm_channels_bwd_f32``, ``usf_gated_residual_bwd_f32``, ``usf_act_grad_f32``, ``usf_masked_residual_f32`` and
   ``usf_base_logprob_grad_f32`` cover the elementwise pieces.
 
@@ -479,14 +481,18 @@ def gated_tail_ok(conv2, x, ln=None) -> bool:
     if not (pad == "same" or (not isinstance(pad, str) and tuple(pad) == (0, 0))):
         return False
     B, Cc, H, W = x.shape
-    if H * W >= WIDE_MIN_PIXELS:
-        return False        # the fused tail's backward carries usf_conv_wgrad_f32's weight gradient: up to 64 pixels, the two-pass form above
+    wide = H * W >= WIDE_MIN_PIXELS
+    if wide and not config.gated_tail_wide:
+        return False        # knob off: above 64 pixels the two-pass form (layer norm, gated residual, pointwise, usf_conv_wgrad_wide_f32)
     if not (conv2.in_channels == Cc and conv2.out_channels == 2 * Cc and 0 < B * H * W <= config.gated_tail_max_pixels
             and _ext.gated_tail_supported(Cc)):
         return False
     if ln is not None and not (ln.gamma.numel() == Cc and ln.gamma.dtype == torch.float32):
         return False
-    return _ext.load().usf_conv_wgrad_workspace(max(B, 1), Cc, 2 * Cc, H, W, 1) > 0
+    if not config.gated_tail_wide:
+        return _ext.load().usf_conv_wgrad_workspace(max(B, 1), Cc, 2 * Cc, H, W, 1) > 0      # (the rule before the knob existed)
+    # the kernel indexes pixels as b * P + p and carries its own weight gradient: its own workspace query decides, at any P
+    return _ext.load().usf_gated_tail_workspace(max(B, 1), Cc, H * W) > 0
 
 
 class GatedTail(torch.autograd.Function):
@@ -592,7 +598,18 @@ class ChannelAffine(torch.autograd.Function):
         x, Wd, bd, Wt = ctx.saved_tensors
         dy = dy.contiguous()
         dx = dW = db = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+        want_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        if want_w and affine_small_c_served(x.shape[0], x.shape[1], x.shape[2] * x.shape[3]):
+            # few channels: dx, dW and db from ONE launch, on W as the forward used it (usf_channel_affine_bwd_f32)
+            r = _ext.channel_affine_bwd(x, dy, Wd, pre_sub=bd if ctx.pre_sub else None, want_dx=ctx.needs_input_grad[0],
+                                        want_bias=True, defer=ctx.defer, owners=(id(ctx),))
+            if r is None:
+                raise RuntimeError("usflows_amd: usf_channel_affine_bwd_f32 does not serve this shape (channel_affine_train_ok was not consulted)")
+            dx, dW, db = r
+            if ctx.pre_sub:
+                db = -(Wd.t() @ db)
+            return dx, dW, db, None, None, None
+        if want_w:
             r = conv_wgrad(x, dy, 1, pre_sub=bd if ctx.pre_sub else None, want_bias=True, defer=ctx.defer, owners=(id(ctx),))
             if r is None:
                 raise RuntimeError("usflows_amd: neither usf_conv_wgrad_f32 nor usf_conv_wgrad_wide_f32 serves this channel count")
@@ -604,9 +621,29 @@ class ChannelAffine(torch.autograd.Function):
         return dx, dW, db, None, None, None
 
 
+AFFINE_SMALL_C_MAX = 12       # usf_channel_affine_bwd_f32: C^2 + C sums per thread in registers
+
+
+def affine_small_c_served(B: int, C: int, P: int) -> bool:
+    """does usf_channel_affine_bwd_f32 take the backward of a C-channel affine layer?  1 <= C <= 12 at any pixel count, while the
+    knob ``config.affine_small_c`` is on"""
+    return (config.affine_small_c and 1 <= C <= AFFINE_SMALL_C_MAX
+            and _ext.load().usf_channel_affine_bwd_workspace(max(B, 1), C, P) > 0)
+
+
 def channel_affine_train_ok(x, C) -> bool:
-    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == C and C in (16, 32, 48, 64)
-            and _wgrad_workspace_ok(x.shape[0], C, C, x.shape[2], x.shape[3]))
+    """the training route of a C-channel affine block at this input: C in {16, 32, 48, 64} on the matrix-core weight gradients (as
+    ever: usf_conv_wgrad_f32 up to 64 pixels, usf_conv_wgrad_wide_f32 above); C <= 12 on usf_channel_affine_bwd_f32 at any pixel
+    count (knob ``affine_small_c``; off: declined, the torch route); every other C <= 64 at 65 .. 256 pixels on
+    usf_conv_wgrad_wide_f32 + usf_channel_affine_f32 (knob ``wgrad_wide``), declined up to 64 pixels"""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == C and 1 <= C <= 64):
+        return False
+    B, H, W = x.shape[0], x.shape[2], x.shape[3]
+    if C in (16, 32, 48, 64):
+        return _wgrad_workspace_ok(B, C, C, H, W)
+    if C <= AFFINE_SMALL_C_MAX:
+        return affine_small_c_served(B, C, H * W)
+    return H * W >= WIDE_MIN_PIXELS and wide_wgrad_served(B, C, C, H, W, 1)
 
 
 class BaseLogProb(torch.autograd.Function):
