@@ -237,7 +237,7 @@ int usf_coupling_additive_vctx_f32(const usf_coupling_desc* d, const float* ctx,
                                    const float* W_ctx_t, int64_t ldw_ctx, const float* b_ctx, usf_stream_t stream);
 int usf_coupling_additive_vctx_variant(const usf_coupling_desc* d, int32_t ctx_dim);
 
-/* usf_conv_ctx_wgrad_f32 (ABI 36): the weight gradient of the context channel of usf_conv2d_same_ctx_f32 (usflows_hip.h;
+/* usf_conv_ctx_wgrad_f32 (ABI 36; ks = 1, 3 or 5 -- 5 on a 25-tap instantiation of the same kernel): the weight gradient of the context channel of usf_conv2d_same_ctx_f32 (usflows_hip.h;
  * reference networks.py:513-680 under autograd),
  *   dw_ctx[co, t] = sum_b ctx[b * ctx_stride] * sum over the p whose tap t lands inside the image of dy[b, co, p]
  * dy [B, cout, H, W] contiguous fp32, dw_ctx [cout, ks * ks].  One block per output channel reads its dy plane once; the sums
@@ -389,6 +389,31 @@ int usf_conv_wgrad_wide_f32(const float* x, const float* dy, int64_t B, int64_t 
 int usf_conv_wgrad_wide_variant(const usf_conv_wgrad_query* q, usf_conv_wgrad_wide_info* out);
 int usf_conv_wgrad_wide_instances(int32_t* out, int32_t cap);
 
+/*
+ * usf_conv_wgrad_k5_f32 (an addition: USF_INTERNAL_VERSION is unchanged): the contract and the argument list of
+ * usf_conv_wgrad_wide_f32 for kernel 5 -- dW [cout, cin, 5, 5] and db [cout] (or NULL) from x (with in_act, in_mul, pre_sub) and
+ * dy, exact fp32 on v_mfma_f32_16x16x4_f32, fixed-order sums, the same bits on every run, no atomics (usf_conv_wgrad_k5.hip).
+ * The wide kernel's design -- a 256-thread block owns one sample at a time in LDS -- with the 25 taps dealt over the grid:
+ * blockIdx.y is a tap row of 5, so a wave holds at most 21 accumulator tiles; the bias tiles belong to tap row 0 alone; every
+ * (tap row, block) owns its partial slot.  Served: ks == 5 only (usf_conv_wgrad_f32 and usf_conv_wgrad_wide_f32 keep refusing
+ * it), 1 <= cin, cout <= 64 (any value), 1 <= H * W <= 256 at every pixel count (no 64-pixel split), B >= 1, provided
+ *     S = W + 2, n = 4 * ceil(((H - 1) * S + W) / 4), CSy = 2odd(n), CSx = 2odd(n + 4 * S + 5)
+ *     4 * ((16 * ceil(cin / 16) + 1) * CSx + 16 * ceil(cout / 16) * CSy) <= 163840 bytes
+ * (64 + 64 channels up to 15 x 15; 16 x 16 up to 48 + 64).  Returns 1 (nothing written) for other shapes, 0 when done, < 0 on
+ * error.  workspace: at least usf_conv_wgrad_k5_workspace(...) floats (0: not served; it depends on the device's compute units).
+ * Two or three launches in stream order, no host synchronisation.
+ * usf_conv_wgrad_k5_variant answers with the plan in a usf_conv_wgrad_wide_info (host only; cus > 0: no GPU needed): T = 5 taps
+ * per tap row, position_parts = 5 tap rows (grid.y), wave_groups = 4, tiles = COT * (CIT * 5 + 1) accumulator tiles of tap row
+ * 0, tiles_per_wave = ceil(tiles / 4) rounded up to one of usf_conv_wgrad_k5_instances, blocks = grid.x = min(B, ceil(cus *
+ * min(blocks_per_cu, 2) / 5)), slots = blocks partial slots per tap row of nacc floats, summed per tap row in `rounds` rounds.
+ */
+int64_t usf_conv_wgrad_k5_workspace(int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks);
+int usf_conv_wgrad_k5_f32(const float* x, const float* dy, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
+                          const float* in_mul, const float* pre_sub, int32_t in_act, float in_slope, float* dW, float* db,
+                          float* workspace, int64_t workspace_floats, usf_stream_t stream);
+int usf_conv_wgrad_k5_variant(const usf_conv_wgrad_query* q, usf_conv_wgrad_wide_info* out);
+int usf_conv_wgrad_k5_instances(int32_t* out, int32_t cap);
+
 /* usf_conv2d_weight_planes_f32(transposed = 2) for MANY weights in one launch.  jobs / block_job are DEVICE arrays (as for
  * usf_partial_sum_jobs_f32): job j splits the fp32 weight w [cout, cin, ks, ks] into its planes followed by the planes of its
  * data-gradient convolution, at planes_base + out_off (bf16 elements; usf_conv2d_weight_elems(cin, cout, ks) +
@@ -471,11 +496,16 @@ int usf_conv2d_same_gate_f32(const float* x, float* y, int64_t B, int64_t cin, i
 /*
  * usf_conv2d_same_variant (internal version 5): which kernel a call of the "same" convolution's entry points launches, and
  * how -- answered by the planning functions the entry points themselves launch from (host only, nothing is launched, no
- * tensor pointer exists).  Three kernels serve the five entry points:
+ * tensor pointer exists).  Four kernels serve the five entry points:
  *   1  conv2d_same_bf16x3_kernel<CTX>            every shape usf_conv2d_same_f32 accepts, gated mode, 4-byte tensor accesses
  *   2  conv2d_same_wreg_kernel<NB, CP, NCT, CTX> 3 x 3, 16 / 32 -> 16 / 32 / 64 channels, H W <= 64; only under the tuning
  *                                                knob conv_wsp=0; no gate-add form, residual forms up to 8192 outputs per group
  *   3  conv2d_same_wsp_kernel<NB, CP, NCT, CTX>  3 x 3, 16 / 32 / 48 -> 16 / 32 / 48 / 64 channels, H W <= 64
+ *   4  conv2d_same_k5_stream_kernel<NR, CTX>     5 x 5 (an addition: USF_INTERNAL_VERSION is unchanged, the struct is as it
+ *                                                was), plain / ctx calls where kernel 1 cannot hold the 25 taps' weight planes
+ *                                                and two padded samples in the LDS: the group's image stays resident, the weights
+ *                                                move through a ring of two K slabs, one barrier per slab (usf_conv_stream.hip).
+ *                                                ks = 5 runs on kernel 1 where its best S is >= 2 (or nothing else fits), else here
  * Kernels 2 and 3 want (cin H W) and (cout H W) multiples of 4 and every tensor 16-byte aligned; a plain / ctx call they do
  * not serve runs on kernel 1, a res / gate call they do not serve is answered with return code 1 (kernel 0 here).
  * Query: entry (USF_CONV_ENTRY_*; GATED: usf_conv2d_same_f32 with gate_x, cout = the packed row count), B, cin, cout, H, W,
@@ -484,8 +514,10 @@ int usf_conv2d_same_gate_f32(const float* x, float* y, int64_t B, int64_t cin, i
  * Answer: kernel (0: not served / refused); S samples per group, groups = ceil(B / S), grid blocks, lds_bytes; for kernels 2
  * and 3 the instantiation (NB k-blocks, CP padded input channels, NCT output tiles) and the largest n each magic-number
  * division umulhi(n, m) is applied to (max_mHW / mW / mSE / mSO; -1: that division is not made); for kernel 1 the patch shape
- * (PC, PR) in 16-row tiles of a full group and of the last group (they differ when the last group is ragged); CTX: the
- * context instantiation.  Returns 0, -1 (null pointer) or -2 (bad entry).
+ * (PC, PR) in 16-row tiles of a full group and of the last group (they differ when the last group is ragged); for kernel 4
+ * NB = 32-value k-blocks per slab (2: a slab of 64 K values, a tap at 64 padded channels; 1: half of that, where only it brings a
+ * second sample into the LDS), CP = padded input channels, NCT = slabs in the ring (2), PC = 2 and PR = NR, the 16-row tiles
+ * per wave of the instantiation (1, 2, 4); CTX: the context instantiation.  Returns 0, -1 (null pointer) or -2 (bad entry).
  */
 #define USF_CONV_ENTRY_PLAIN 0
 #define USF_CONV_ENTRY_CTX 1

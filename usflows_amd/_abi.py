@@ -349,6 +349,11 @@ INTERNAL_SYMBOLS = {
                                           C.c_void_p]),
     "usf_conv_wgrad_wide_variant": (C.c_int, [C.POINTER(ConvWgradQuery), C.POINTER(ConvWgradWideInfo)]),
     "usf_conv_wgrad_wide_instances": (C.c_int, [C.POINTER(C.c_int32), C.c_int32]),
+    "usf_conv_wgrad_k5_workspace": (C.c_int64, [C.c_int64] * 6),
+    "usf_conv_wgrad_k5_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [_fp, _fp, C.c_int32, C.c_float, _fp, _fp, _fp, C.c_int64,
+                                        C.c_void_p]),
+    "usf_conv_wgrad_k5_variant": (C.c_int, [C.POINTER(ConvWgradQuery), C.POINTER(ConvWgradWideInfo)]),
+    "usf_conv_wgrad_k5_instances": (C.c_int, [C.POINTER(C.c_int32), C.c_int32]),
     "usf_conv_wgrad_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [_fp, _fp, C.c_int32, C.c_float, _fp, _fp, _fp, C.c_int64,
                                      C.c_void_p]),
     "usf_conv_wgrad_deferred_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [_fp, _fp, C.c_int32, C.c_float, _fp, _fp, _fp, C.c_int64,

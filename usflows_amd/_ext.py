@@ -994,6 +994,39 @@ def conv_wgrad_wide(x, dy, ks, in_mul=None, pre_sub=None, in_act=ACT_NONE, in_sl
     return None if rc else (dW, db)
 
 
+def conv_wgrad_k5(x, dy, in_mul=None, pre_sub=None, in_act=ACT_NONE, in_slope=0.0, want_bias=True):
+    """usf_conv_wgrad_k5_f32: conv_wgrad's (dW [cout, cin, 5, 5], db | None) of a 5 x 5 "same" convolution; None when the shape is
+    not served.  Never deferred or queued, as conv_wgrad_wide: a captured training step replays its launches"""
+    B, cin, H, W = x.shape
+    cout = dy.shape[1]
+    ws_n = load().usf_conv_wgrad_k5_workspace(B, cin, cout, H, W, 5)
+    if ws_n <= 0:
+        return None
+    ws = torch.empty(ws_n, dtype=torch.float32, device=x.device)
+    dW = torch.empty(cout, cin, 5, 5, dtype=torch.float32, device=x.device)
+    db = torch.empty(cout, dtype=torch.float32, device=x.device) if want_bias else None
+    rc = _launch("usf_conv_wgrad_k5_f32", (x.data_ptr(), dy.data_ptr(), B, cin, cout, H, W, 5, ptr(in_mul), ptr(pre_sub), int(in_act),
+                 float(in_slope), dW.data_ptr(), ptr(db), ws.data_ptr(), ws_n, current_stream(x.device)), tape=False, unserved_ok=True)
+    return None if rc else (dW, db)
+
+
+def conv_wgrad_k5_variant(B, cin, cout, H, W, ks=5, cus=0, blocks_per_cu=0) -> dict:
+    """usf_conv_wgrad_k5_variant: the plan usf_conv_wgrad_k5_f32 launches from, as a dict (served 0: the call returns 1)"""
+    q = ConvWgradQuery(int(B), int(cin), int(cout), int(H), int(W), int(ks), 0, int(cus), int(blocks_per_cu), 0)
+    out = ConvWgradWideInfo()
+    check(load().usf_conv_wgrad_k5_variant(C.byref(q), C.byref(out)), "usf_conv_wgrad_k5_variant")
+    return {name: int(getattr(out, name)) for name, _ in ConvWgradWideInfo._fields_ if name != "reserved"}
+
+
+def conv_wgrad_k5_instances() -> list:
+    """usf_conv_wgrad_k5_instances: the tiles-per-wave values usf_conv_wgrad_k5.hip instantiates its kernel for"""
+    lib = load()
+    n = lib.usf_conv_wgrad_k5_instances(None, 0)
+    buf = (C.c_int32 * n)()
+    lib.usf_conv_wgrad_k5_instances(buf, n)
+    return list(buf)
+
+
 def layernorm_channels_bwd(x, dy, gamma, eps, act=ACT_NONE, slope=0.0):
     """usf_layernorm_channels_bwd_f32 -> (dx, dgamma [C], dbeta [C])"""
     B, Cc = x.shape[0], x.shape[1]

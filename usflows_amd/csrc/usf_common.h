@@ -104,11 +104,22 @@ __device__ __forceinline__ void vctx_add(f32x4 (&X)[T], const float* crow, int C
 // The context channel of a conditional conditioner's first convolution (usf_conv2d_same_ctx_f32): a constant plane ctx[b]
 // under zero padding contributes ctx[b] * S[co, p] with S = the sum of the channel's taps that land inside the image at p.
 // ctx_tapmask: bit t (t = dy * ks + dx) set when tap t of output pixel (py, px) reads inside the H x W image.
-__device__ __forceinline__ unsigned ctx_tapmask(int py, int px, int H, int W, int ks) {
+__host__ __device__ __forceinline__ unsigned ctx_tapmask(int py, int px, int H, int W, int ks) {
   if (ks == 1) return 1u;
   const unsigned rowok = (py > 0 ? 0x007u : 0u) | 0x038u | (py + 1 < H ? 0x1c0u : 0u);
   const unsigned colok = (px > 0 ? 0x049u : 0u) | 0x092u | (px + 1 < W ? 0x124u : 0u);
   return rowok & colok;
+}
+// ks = 5: 25 bits; a row / column of taps is inside at distance 0, 1 or >= 2 from each border (H or W below 3: both borders at
+// once).  A function of its own, chosen at compile time by the 5 x 5 instantiations: the ks = 1 / 3 callers compile as before.
+__host__ __device__ __forceinline__ unsigned ctx_tapmask5(int py, int px, int H, int W) {
+  unsigned rows = 0u, cols = 0u;
+#pragma unroll
+  for (int d = 0; d < 5; ++d) {
+    rows |= ((unsigned)(py + d - 2) < (unsigned)H ? 1u : 0u) << (5 * d);     // bit 5 d: tap row d reads inside
+    cols |= ((unsigned)(px + d - 2) < (unsigned)W ? 1u : 0u) << d;
+  }
+  return rows * cols;                                                        // (no carries: cols < 32)
 }
 // S for one output channel: wc = w_ctx + co * ks * ks, taps added in index order (deterministic)
 __device__ __forceinline__ float ctx_tapsum(const float* wc, int taps, unsigned mask) {

@@ -1,5 +1,6 @@
 // Convolution conditioner of the image-shaped flows: Conv2d with stride 1, "same" zero padding,
-// kernel 1 x 1 or 3 x 3 (networks.py:405-510 ConvNet2D, :61-122 GatedConv) as an implicit GEMM on the bf16 matrix cores
+// kernel 1 x 1, 3 x 3 or 5 x 5 (networks.py:405-510 ConvNet2D, :61-122 GatedConv; 5 x 5 where the 25 taps' weight planes and two
+// samples fit the LDS, otherwise on the streamed kernel of usf_conv_stream.hip) as an implicit GEMM on the bf16 matrix cores
 // with the fp32-equivalent bf16x3 arithmetic of the rest of the path (three bf16 planes per operand, six
 // v_mfma_f32_16x16x32_bf16 per product, fp32 accumulation).
 //
@@ -51,7 +52,8 @@ __device__ __forceinline__ void cv_split(float x, __bf16& h, __bf16& m, __bf16& 
 }
 
 // CTX: the context channel's rank-1 term joins the bias in the epilogue (usf_conv2d_same_ctx_f32); false: the plain kernel
-template <bool CTX>
+// K5: the ks = 5 instantiations (their context mask is ctx_tapmask5); false: ks = 1 / 3, compiled as before ks = 5 existed
+template <bool CTX, bool K5 = false>
 __global__ __launch_bounds__(512, 2) void conv2d_same_bf16x3_kernel(const ConvArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -230,7 +232,7 @@ __global__ __launch_bounds__(512, 2) void conv2d_same_bf16x3_kernel(const ConvAr
           if constexpr (CTX) {
             const int py = p / a.W;
             cx = a.ctx[(size_t)(s0 + sl) * a.ctx_stride];
-            cmask = ctx_tapmask(py, p - py * a.W, a.H, a.W, a.ks);
+            cmask = K5 ? ctx_tapmask5(py, p - py * a.W, a.H, a.W) : ctx_tapmask(py, p - py * a.W, a.H, a.W, a.ks);
           }
           if (PC == 2 && a.gateC > 0) {
             // gated mode: the patch's two tiles are (value, gate) of the same 16 channels (rows interleaved at pack time):
@@ -281,8 +283,10 @@ int conv2d_same_wreg(const float* x, float* y, int64_t B, int64_t cin, int64_t c
                      const float* ctx = nullptr, int64_t ctx_stride = 0, const float* w_ctx = nullptr);
 
 static int odd16(int units) { return units | 1; }
-// register-staged iterations per thread for a group of S samples (the kernel holds at most 16 pixel pairs per thread)
-static int conv_stage_iters(int cin, int HW, int S) { return ((S * ((cin + 1) / 2) + 7) / 8) * ((HW + 63) / 64); }
+// fourth kernel (usf_conv_stream.hip)
+int conv2d_same_stream(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, const void* wplanes,
+                       const float* bias, const float* in_mul, int32_t in_act, float in_slope, int32_t out_act, float out_slope,
+                       const float* ctx, int64_t ctx_stride, const float* w_ctx, const ConvSPlan& pl, hipStream_t stream);
 
 // LDS bytes of a launch with S samples per group; the layout the kernel derives from the same numbers
 static int64_t conv_lds_bytes(int cin, int cout, int H, int W, int ks, int S, int* xs16, int* ws16, int* cp_, int* kp_, int* coutp_) {
@@ -294,14 +298,18 @@ static int64_t conv_lds_bytes(int cin, int cout, int H, int W, int ks, int S, in
 
 // elements ([3][coutp][kp] bf16) of the weight planes usf_conv2d_same_f32 expects for these sizes
 int64_t conv2d_weight_elems(int64_t cin, int64_t cout, int64_t ks) {
-  if (cin <= 0 || cout <= 0 || (ks != 1 && ks != 3)) return -1;
+  if (cin <= 0 || cout <= 0 || (ks != 1 && ks != 3 && ks != 5)) return -1;
   const int64_t cp = (cin + 7) / 8 * 8, kp = (ks * ks * cp + 31) / 32 * 32, coutp = (cout + 15) / 16 * 16;
   return 3 * coutp * kp;
 }
 
 // samples per group the kernel would use for these sizes (the LDS decides); 0: the shape is not served
 int conv2d_same_fits(int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks) {
-  if (cin <= 0 || cout <= 0 || H <= 0 || W <= 0 || cin > 64 || cout > 64 || H * W > 256 || (ks != 1 && ks != 3)) return 0;
+  if (cin <= 0 || cout <= 0 || H <= 0 || W <= 0 || cin > 64 || cout > 64 || H * W > 256 || (ks != 1 && ks != 3 && ks != 5)) return 0;
+  if (ks == 5) {
+    int S = 0;
+    return conv_k5_route((int)cin, (int)cout, (int)H, (int)W, false, &S) ? S : 0;
+  }
   int xs, ws, cp, kp, coutp;
   for (int S = 8; S >= 1; --S)
     if (conv_lds_bytes((int)cin, (int)cout, (int)H, (int)W, (int)ks, S, &xs, &ws, &cp, &kp, &coutp) <= 158 * 1024 &&
@@ -334,6 +342,18 @@ int conv_first_plan(int64_t B, int cin, int cout, int H, int W, int ks, int cus,
   return 0;
 }
 
+// ks = 5: the first kernel where its weights and two samples fit the LDS, otherwise the streamed kernel (no gated mode there),
+// otherwise the first kernel with one sample
+int conv_k5_route(int cin, int cout, int H, int W, bool gated, int* S_best) {
+  ConvPlan p1;
+  const int s1 = conv_first_plan(1 << 20, cin, cout, H, W, 5, 1, &p1) == 0 ? p1.S : 0;
+  ConvSPlan ps;
+  const int ss = gated ? 0 : (conv_stream_plan(1 << 20, cin, cout, H, W, 1, &ps) == 0 ? ps.S : 0);
+  if (s1 >= 2 || ss < 1) { *S_best = s1; return s1 >= 1 ? 1 : 0; }
+  *S_best = ss;
+  return 4;
+}
+
 // usf_conv2d_same_variant: the plans above, asked instead of launched (no pointer is looked at, nothing is launched)
 int conv2d_same_variant(const usf_conv_variant_query* q, usf_conv_variant* o) {
   if (!q || !o) { set_error("usf_conv2d_same_variant: null pointer"); return -1; }
@@ -344,7 +364,7 @@ int conv2d_same_variant(const usf_conv_variant_query* q, usf_conv_variant* o) {
   if (e < USF_CONV_ENTRY_PLAIN || e > USF_CONV_ENTRY_GATED) { set_error("usf_conv2d_same_variant: bad entry"); return -2; }
   if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0 || B > 0x7fffffff) return 0;
   const bool fused = e == USF_CONV_ENTRY_RES || e == USF_CONV_ENTRY_GATE_MUL || e == USF_CONV_ENTRY_GATE_ADD;
-  const bool first_ok = !(cin > 64 || cout > 64 || H * W > 256 || (ks != 1 && ks != 3));   // conv2d_same's size rule
+  const bool first_ok = !(cin > 64 || cout > 64 || H * W > 256 || (ks != 1 && ks != 3 && ks != 5));   // conv2d_same's size rule
   if (fused ? ks != 3 : !first_ok) return 0;
   if (e == USF_CONV_ENTRY_GATED && cout % 32 != 0) return 0;
   const int cus = q->cus > 0 ? q->cus : device_cu_count();
@@ -365,6 +385,19 @@ int conv2d_same_variant(const usf_conv_variant_query* q, usf_conv_variant* o) {
     }
   }
   if (fused) return 0;                                     // the fused forms live on the second / third kernel only
+  if (ks == 5) {
+    int sb = 0;
+    const int route = conv_k5_route((int)cin, (int)cout, (int)H, (int)W, e == USF_CONV_ENTRY_GATED, &sb);
+    if (route == 0) return 0;
+    if (route == 4) {
+      ConvSPlan sp;
+      if (conv_stream_plan(B, (int)cin, (int)cout, (int)H, (int)W, cus, &sp) != 0) return 0;
+      o->kernel = 4; o->S = sp.S; o->grid = sp.grid; o->groups = sp.groups; o->lds_bytes = sp.lds;
+      o->NB = sp.KS / 32; o->CP = sp.cp; o->NCT = sp.depth; o->CTX = e == USF_CONV_ENTRY_CTX;
+      o->PC_full = o->PC_last = 2; o->PR_full = o->PR_last = sp.NR;
+      return 0;
+    }
+  }
   ConvPlan p;
   if (conv_first_plan(B, (int)cin, (int)cout, (int)H, (int)W, (int)ks, cus, &p) != 0) return 0;
   o->kernel = 1; o->S = p.S; o->grid = p.grid; o->groups = p.groups; o->lds_bytes = p.lds;
@@ -380,9 +413,9 @@ int conv2d_same(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, 
                 const void* wplanes, const float* bias, const float* in_mul, int32_t in_act, float in_slope,
                 int32_t out_act, float out_slope, const float* gate_x, int64_t gate_channels, hipStream_t stream,
                 const float* ctx, int64_t ctx_stride, const float* w_ctx) {
-  if (B < 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0 || cin > 64 || cout > 64 || H * W > 256 || (ks != 1 && ks != 3) ||
+  if (B < 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0 || cin > 64 || cout > 64 || H * W > 256 || (ks != 1 && ks != 3 && ks != 5) ||
       B > 0x7fffffff) {
-    set_error("usf_conv2d_same_f32: unsupported sizes (channels 1..64, H * W <= 256, kernel 1 or 3)");
+    set_error("usf_conv2d_same_f32: unsupported sizes (channels 1..64, H * W <= 256, kernel 1, 3 or 5)");
     return -2;
   }
   if (B == 0) return 0;
@@ -405,6 +438,19 @@ int conv2d_same(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, 
                                     nullptr, 0.f, 0, stream, ctx, ctx_stride, w_ctx);
     if (rc != 0) return rc < 0 ? rc : 0;
   }
+  if (ks == 5) {
+    int sb = 0;
+    const int route = conv_k5_route((int)cin, (int)cout, (int)H, (int)W, gate_x != nullptr, &sb);
+    if (route == 4) {
+      ConvSPlan sp;
+      if (conv_stream_plan(B, (int)cin, (int)cout, (int)H, (int)W, 0, &sp) != 0) {
+        set_error("usf_conv2d_same_f32: no streamed plan");
+        return -3;
+      }
+      return conv2d_same_stream(x, y, B, cin, cout, H, W, wplanes, bias, in_mul, in_act, in_slope, out_act, out_slope, ctx, ctx_stride,
+                                w_ctx, sp, stream);
+    }
+  }
   ConvArgs a;
   a.x = x; a.y = y; a.wp = reinterpret_cast<const __bf16*>(wplanes); a.bias = bias; a.in_mul = in_mul;
   a.B = (int)B; a.cin = (int)cin; a.cout = (int)cout; a.H = (int)H; a.W = (int)W; a.ks = (int)ks;
@@ -420,10 +466,13 @@ int conv2d_same(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, 
   const int64_t lds = pl.lds;
   a.xs16 = pl.xs16; a.ws16 = pl.ws16; a.cp = pl.cp; a.kp = pl.kp; a.coutp = pl.coutp;
   a.S = pl.S;
-  static bool attr_done_dev[2][USF_MAX_DEVICES] = {{false}};   // (the attribute belongs to the device and the instantiation)
-  bool& attr_done = attr_done_dev[ctx ? 1 : 0][current_device_slot()];
-  const void* kfn = ctx ? reinterpret_cast<const void*>(&conv2d_same_bf16x3_kernel<true>)
-                        : reinterpret_cast<const void*>(&conv2d_same_bf16x3_kernel<false>);
+  static bool attr_done_dev[4][USF_MAX_DEVICES] = {{false}};   // (the attribute belongs to the device and the instantiation)
+  const bool k5 = ks == 5;
+  bool& attr_done = attr_done_dev[(ctx ? 1 : 0) + (k5 ? 2 : 0)][current_device_slot()];
+  const void* kfn = k5 ? (ctx ? reinterpret_cast<const void*>(&conv2d_same_bf16x3_kernel<true, true>)
+                              : reinterpret_cast<const void*>(&conv2d_same_bf16x3_kernel<false, true>))
+                       : (ctx ? reinterpret_cast<const void*>(&conv2d_same_bf16x3_kernel<true>)
+                              : reinterpret_cast<const void*>(&conv2d_same_bf16x3_kernel<false>));
   if (!attr_done) {
     if (hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
       set_error("usf_conv2d_same_f32: cannot raise the LDS limit");
@@ -432,7 +481,9 @@ int conv2d_same(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, 
     attr_done = true;
   }
   const unsigned grid = pl.grid;
-  if (ctx) hipLaunchKernelGGL(conv2d_same_bf16x3_kernel<true>, dim3(grid), dim3(512), (size_t)lds, stream, a);
+  if (k5 && ctx) hipLaunchKernelGGL((conv2d_same_bf16x3_kernel<true, true>), dim3(grid), dim3(512), (size_t)lds, stream, a);
+  else if (k5) hipLaunchKernelGGL((conv2d_same_bf16x3_kernel<false, true>), dim3(grid), dim3(512), (size_t)lds, stream, a);
+  else if (ctx) hipLaunchKernelGGL(conv2d_same_bf16x3_kernel<true>, dim3(grid), dim3(512), (size_t)lds, stream, a);
   else hipLaunchKernelGGL(conv2d_same_bf16x3_kernel<false>, dim3(grid), dim3(512), (size_t)lds, stream, a);
   return check_launch(ctx ? "usf_conv2d_same_ctx_f32" : "usf_conv2d_same_f32");
 }

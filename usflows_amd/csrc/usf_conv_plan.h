@@ -51,7 +51,26 @@ struct ConvWQuery {
   int cus;                      // compute units to plan for
 };
 
+// fourth kernel (conv2d_same_k5_stream_kernel, usf_conv_stream.hip): 5 x 5, weights streamed through an LDS ring
+struct ConvSPlan {
+  int S;                        // samples per group, clipped to B (0: not even one sample fits)
+  int S_best;                   // ... of a batch that does not clip it
+  int KS, depth, nslab;         // K values per slab (64 / 32), slabs in the ring (2), slabs per walk
+  int NR;                       // the instantiation: 16-row tiles per wave (1, 2, 4)
+  int64_t lds;
+  int xs16, ss16, cp, kp, coutp;
+  int64_t groups;
+  unsigned grid;
+};
+
+// register-staged iterations per thread for a group of S samples (the first and fourth kernel hold at most 16 pixel pairs per thread)
+inline int conv_stage_iters(int cin, int HW, int S) { return ((S * ((cin + 1) / 2) + 7) / 8) * ((HW + 63) / 64); }
+
 int conv_first_plan(int64_t B, int cin, int cout, int H, int W, int ks, int cus, ConvPlan* p);
+int conv_stream_plan(int64_t B, int cin, int cout, int H, int W, int cus, ConvSPlan* p);
+// which kernel serves ks = 5 for these sizes: 1 (weights resident: its best S >= 2, or nothing else fits), 4 (streamed), 0 (none);
+// *S_best = samples per group of a batch that does not clip them
+int conv_k5_route(int cin, int cout, int H, int W, bool gated, int* S_best);
 void conv_wreg_launch_plan(const ConvWQuery& q, ConvWPlan* p);
 
 }  // namespace usf

@@ -53,28 +53,53 @@ def _narrow_wgrad_served(B: int, cin: int, cout: int, H: int, W: int, ks: int, m
     return _ext.conv_wgrad_variant(max(B, 1), cin, cout, H, W, ks, masked)["kernel"] != 0
 
 
+def _small_map_wide_served(B: int, cin: int, cout: int, H: int, W: int, ks: int) -> bool:
+    """under the knob ``conv_k5`` only: a kernel-1 / 3 weight gradient that usf_conv_wgrad_f32 refuses at up to 64 pixels (channel
+    counts that are no multiple of 16: the 8 hidden channels of the hyper-parameter search) goes to usf_conv_wgrad_wide_f32, which
+    serves small maps at any channel counts with the same sums in another order.  Knob off: refused there, as ever"""
+    return (config.conv_k5 and config.wgrad_wide
+            and _ext.load().usf_conv_wgrad_wide_workspace(max(B, 1), cin, cout, H, W, ks) > 0)
+
+
+def train_kernel_sizes() -> tuple:
+    """kernel sizes of the convolutions the device training path takes: 1 and 3, and 5 under the knob ``conv_k5``"""
+    return (1, 3, 5) if config.conv_k5 else (1, 3)
+
+
+def k5_wgrad_served(B: int, cin: int, cout: int, H: int, W: int) -> bool:
+    """does usf_conv_wgrad_k5_f32 serve this 5 x 5 call (one kernel for both forms, every pixel count up to 256)?"""
+    return config.conv_k5 and _ext.load().usf_conv_wgrad_k5_workspace(max(B, 1), cin, cout, H, W, 5) > 0
+
+
 def wgrad_served(B: int, cin: int, cout: int, H: int, W: int, ks: int, masked: bool) -> bool:
     """does a weight-gradient kernel serve this call -- with an input mask (in_mul) or without?  Up to 64 pixels
     usf_conv_wgrad_f32, whose two forms differ: 64 -> 64 channels at kernel 1 and 57 .. 64 pixels run without a mask only
-    (usf_conv_wgrad_workspace > 0 says that ONE form is served); above, usf_conv_wgrad_wide_f32 (one kernel for both forms)"""
+    (usf_conv_wgrad_workspace > 0 says that ONE form is served); above, usf_conv_wgrad_wide_f32 (one kernel for both forms);
+    kernel 5: usf_conv_wgrad_k5_f32 at every pixel count"""
+    if ks == 5:
+        return k5_wgrad_served(B, cin, cout, H, W)
     if H * W >= WIDE_MIN_PIXELS:
         return wide_wgrad_served(B, cin, cout, H, W, ks)
-    return _narrow_wgrad_served(B, cin, cout, H, W, ks, masked)
+    return _narrow_wgrad_served(B, cin, cout, H, W, ks, masked) or _small_map_wide_served(B, cin, cout, H, W, ks)
 
 
 def _wgrad_workspace_ok(B: int, cin: int, cout: int, H: int, W: int) -> bool:
     """the kernel-1 weight gradient of a pointwise convolution / an affine block is served (either kernel's workspace > 0)"""
     if H * W >= WIDE_MIN_PIXELS:
         return wide_wgrad_served(B, cin, cout, H, W, 1)
-    return _ext.load().usf_conv_wgrad_workspace(max(B, 1), cin, cout, H, W, 1) > 0
+    return _ext.load().usf_conv_wgrad_workspace(max(B, 1), cin, cout, H, W, 1) > 0 or _small_map_wide_served(B, cin, cout, H, W, 1)
 
 
 def conv_wgrad(x, dy, ks, in_mul=None, pre_sub=None, in_act=_ext.ACT_NONE, in_slope=0.0, want_bias=True, defer=False, owners=()):
     """(dW, db | None) of a convolution's backward, or None: ``_ext.conv_wgrad`` as ever; where it declines a feature map of
-    more than 64 pixels, ``_ext.conv_wgrad_wide`` (never deferred: its sums run in stream order)"""
+    more than 64 pixels, ``_ext.conv_wgrad_wide`` (never deferred: its sums run in stream order); kernel 5:
+    ``_ext.conv_wgrad_k5`` (never deferred either)"""
+    if ks == 5:
+        return _ext.conv_wgrad_k5(x, dy, in_mul=in_mul, pre_sub=pre_sub, in_act=in_act, in_slope=in_slope, want_bias=want_bias) \
+            if config.conv_k5 else None
     r = _ext.conv_wgrad(x, dy, ks, in_mul=in_mul, pre_sub=pre_sub, in_act=in_act, in_slope=in_slope, want_bias=want_bias,
                         defer=defer, owners=owners)
-    if r is None and config.wgrad_wide and x.shape[2] * x.shape[3] >= WIDE_MIN_PIXELS:
+    if r is None and config.wgrad_wide and (x.shape[2] * x.shape[3] >= WIDE_MIN_PIXELS or config.conv_k5):
         r = _ext.conv_wgrad_wide(x, dy, ks, in_mul=in_mul, pre_sub=pre_sub, in_act=in_act, in_slope=in_slope, want_bias=want_bias)
     return r
 
@@ -85,7 +110,7 @@ def conv_shape_ok(conv, B: int, H: int, W: int, masked: bool = False) -> bool:
     if not isinstance(conv, torch.nn.Conv2d):
         return False
     k = conv.kernel_size
-    if k[0] != k[1] or k[0] not in (1, 3) or conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 \
+    if k[0] != k[1] or k[0] not in train_kernel_sizes() or conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 \
             or conv.padding_mode != "zeros":
         return False
     pad = conv.padding
@@ -123,7 +148,7 @@ _WSTATE = _WPlanesState()
 
 class batched_weight_planes:
     """context manager around one training pass of an image-shaped flow at a launch-bound batch: the bf16x3 plane pairs of ALL
-    3 x 3 convolution weights under ``layers`` from one launch (``_ext.WeightPlanesBatch``; the job table is kept on ``owner``
+    3 x 3 (and, under ``conv_k5``, 5 x 5) convolution weights under ``layers`` from one launch (``_ext.WeightPlanesBatch``; the job table is kept on ``owner``
     while the weights keep their addresses) instead of one per convolution and pass"""
 
     def __init__(self, owner, layers, device):
@@ -132,9 +157,10 @@ class batched_weight_planes:
     def __enter__(self):
         self.prev = _WSTATE.planes
         ws, srcs = [], []
+        sizes = ((3, 3), (5, 5)) if config.conv_k5 else ((3, 3),)
         for l in self.layers:
             for m in l.modules():
-                if isinstance(m, torch.nn.Conv2d) and m.kernel_size == (3, 3) and m.weight.device == self.device \
+                if isinstance(m, torch.nn.Conv2d) and m.kernel_size in sizes and m.weight.device == self.device \
                         and m.weight.dtype == torch.float32 and m.weight.is_contiguous():
                     ws.append(m.weight)
                     srcs.append(m.weight.detach())
@@ -144,7 +170,7 @@ class batched_weight_planes:
                 # weight's data columns are gathered into a buffer kept with the batch (refreshed in place every pass: the
                 # weight changes between steps, the buffer's address does not)
                 m = cond.nn[0]
-                if isinstance(m, torch.nn.Conv2d) and m.kernel_size == (3, 3) and m.weight.device == self.device \
+                if isinstance(m, torch.nn.Conv2d) and m.kernel_size in sizes and m.weight.device == self.device \
                         and m.weight.dtype == torch.float32 and m.in_channels >= 2 and id(m.weight) in {id(w) for w in ws}:
                     i = next(j for j, w in enumerate(ws) if w is m.weight)
                     srcs[i] = None
@@ -184,7 +210,7 @@ def _takeable(params) -> bool:
     """True when the autograd engine will TAKE the gradients of these Parameters as they are handed over (no ``.grad`` yet, no
     hooks that would read them): a gradient whose last sum is still queued (_ext.conv_wgrad(defer=True)) must not be read
     before the backward pass ends"""
-    return all(q is None or (q.grad is None and q.is_leaf and not q._backward_hooks
+    return all(q is None or (q.is_leaf and q.grad is None and not q._backward_hooks
                              and not getattr(q, "_post_accumulate_grad_hooks", None)) for q in params)
 
 
@@ -393,7 +419,7 @@ def conv_ctx_shape_ok(conv, B: int, H: int, W: int) -> bool:
     if not isinstance(conv, torch.nn.Conv2d) or conv.in_channels < 2:
         return False
     k = conv.kernel_size
-    if k[0] != k[1] or k[0] not in (1, 3) or conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 \
+    if k[0] != k[1] or k[0] not in train_kernel_sizes() or conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 \
             or conv.padding_mode != "zeros":
         return False
     pad = conv.padding
@@ -402,7 +428,8 @@ def conv_ctx_shape_ok(conv, B: int, H: int, W: int) -> bool:
     lib = _ext.load()
     C, cout = conv.in_channels - 1, conv.out_channels
     return (lib.usf_conv2d_same_fits(C, cout, H, W, k[0]) >= 2 and lib.usf_conv2d_same_fits(cout, C, H, W, k[0]) >= 2
-            and _narrow_wgrad_served(B, C, cout, H, W, k[0], True))    # (the first convolution: it may be handed the coupling's mask;
+            and (_narrow_wgrad_served(B, C, cout, H, W, k[0], True) if k[0] != 5 else
+                 (H * W < WIDE_MIN_PIXELS and k5_wgrad_served(B, C, cout, H, W))))    # (the first convolution: it may be handed the coupling's mask;
                                                                        # above 64 pixels conditional conditioners stay declined)
 
 
@@ -451,6 +478,29 @@ def pointwise_shape_ok(conv, B: int, H: int, W: int) -> bool:
     cin, cout = conv.in_channels, conv.out_channels
     return (_ext.pointwise_conv_supported(cin, cout, False) and _ext.pointwise_conv_supported(cout, cin, False)
             and _wgrad_workspace_ok(B, cin, cout, H, W))
+
+
+def gate_halves_ok(conv, B: int, H: int, W: int) -> bool:
+    """under the knob ``conv_k5`` only: GatedConv's 1 x 1 convolution C -> 2 C with more than the kernels' 64 output channels
+    (C = 33 .. 64: the 64 hidden channels of the hyper-parameter search) runs as TWO convolutions C -> C, the value rows and the
+    gate rows of its weight (``gate_halves``), each with a device forward, data gradient and weight gradient"""
+    if not (config.conv_k5 and isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
+            and conv.groups == 1 and conv.out_channels == 2 * conv.in_channels and 64 < conv.out_channels <= 128):
+        return False
+    pad = conv.padding
+    if not (pad == "same" or (not isinstance(pad, str) and tuple(pad) == (0, 0))):
+        return False
+    C = conv.in_channels
+    return _ext.load().usf_conv2d_same_fits(C, C, H, W, 1) >= 2 and wgrad_served(B, C, C, H, W, 1, False)
+
+
+def gate_halves(h, conv, in_act):
+    """conv(in_act(h)) [B, 2 C, H, W] of such a convolution: ConvSame on the two halves of its rows, concatenated; autograd
+    joins the halves' weight gradients in the Parameter and adds their data gradients"""
+    C = conv.in_channels
+    parts = [ConvSame.apply(h, conv.weight[i * C:(i + 1) * C], None if conv.bias is None else conv.bias[i * C:(i + 1) * C], None,
+                            in_act, None) for i in (0, 1)]
+    return torch.cat(parts, 1)
 
 
 class GatedResidual(torch.autograd.Function):

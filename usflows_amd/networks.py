@@ -419,15 +419,20 @@ def _relu_kind(m):
     return None
 
 
+def _conv_kernel_sizes() -> tuple:
+    """kernel sizes of the "same" convolution's device path: 1 and 3, and 5 under the knob ``conv_k5``"""
+    return (1, 3, 5) if config.conv_k5 else (1, 3)
+
+
 def _conv_same_shaped(conv, x) -> bool:
-    """an nn.Conv2d call the device kernels can express: stride 1, "same" zero padding, kernel 1 or 3, fp32 on a ROCm
-    device, nothing to differentiate"""
+    """an nn.Conv2d call the device kernels can express: stride 1, "same" zero padding, kernel 1 or 3 (5 under the knob
+    ``conv_k5``), fp32 on a ROCm device, nothing to differentiate"""
     if not (isinstance(conv, nn.Conv2d) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
         return False
     if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad):
         return False
     k = conv.kernel_size
-    if k[0] != k[1] or k[0] not in (1, 3) or conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 \
+    if k[0] != k[1] or k[0] not in _conv_kernel_sizes() or conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 \
             or conv.padding_mode != "zeros" or x.shape[1] != conv.in_channels:
         return False
     pad = conv.padding
@@ -500,15 +505,15 @@ def _conv_hip(conv, x, in_act=None, in_mul=None, out_act=None, residual=None):
 
 def _conv_ctx_ok(conv, x) -> bool:
     """conv is the first convolution of a conditional conditioner (one input channel more than x: the context plane) and
-    usf_conv2d_same_ctx_f32 serves it on x: stride 1, "same" zero padding, kernel 1 or 3, fp32 on a ROCm device, nothing to
-    differentiate, at least two samples per LDS group"""
+    usf_conv2d_same_ctx_f32 serves it on x: stride 1, "same" zero padding, kernel 1 or 3 (5 under the knob ``conv_k5``), fp32 on a
+    ROCm device, nothing to differentiate, at least two samples per LDS group"""
     if not (isinstance(conv, nn.Conv2d) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
             and conv.in_channels == x.shape[1] + 1 and conv.weight.dtype == torch.float32):
         return False
     if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad):
         return False
     k = conv.kernel_size
-    if k[0] != k[1] or k[0] not in (1, 3) or conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 \
+    if k[0] != k[1] or k[0] not in _conv_kernel_sizes() or conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 \
             or conv.padding_mode != "zeros":
         return False
     pad = conv.padding
@@ -617,7 +622,7 @@ class GatedConv(nn.Module):
         return (_relu_kind(n[0]) is not None and _relu_kind(n[2]) is not None and isinstance(n[1], nn.Conv2d)
                 and isinstance(n[3], nn.Conv2d) and n[1].in_channels == C and n[3].out_channels == 2 * C
                 and n[3].in_channels == n[1].out_channels and it.conv_shape_ok(n[1], B, H, W)
-                and (it.pointwise_shape_ok(n[3], B, H, W) or it.conv_shape_ok(n[3], B, H, W)))
+                and (it.pointwise_shape_ok(n[3], B, H, W) or it.conv_shape_ok(n[3], B, H, W) or it.gate_halves_ok(n[3], B, H, W)))
 
     def forward_train_device(self, x, post=None):
         """the block as differentiable device passes: 3 x 3 convolution, then -- few pixels (image_training.gated_tail_ok) -- ONE
@@ -634,6 +639,8 @@ class GatedConv(nn.Module):
                                       None if lnm is None else lnm.beta, a2, pa, 0.0 if lnm is None else lnm.eps)
         if it.pointwise_shape_ok(n[3], x.shape[0], x.shape[2], x.shape[3]):
             vg = it.Pointwise.apply(h, n[3].weight, n[3].bias, a2)
+        elif not it.conv_shape_ok(n[3], x.shape[0], x.shape[2], x.shape[3]) and it.gate_halves_ok(n[3], x.shape[0], x.shape[2], x.shape[3]):
+            vg = it.gate_halves(h, n[3], a2)                       # (2 C > 64 output channels: value rows and gate rows apart)
         else:
             vg = it.ConvSame.apply(h, n[3].weight, n[3].bias, None, a2, None)
         return it.GatedResidual.apply(x, vg)
