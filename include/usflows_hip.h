@@ -322,12 +322,15 @@ int usf_pointwise_conv_f32(const float* x, float* y, int64_t B, int64_t cin, int
 
 /*
  * Conv2d of the CNN conditioner (networks.py:405-510 ConvNet2D, :61-122 GatedConv): stride 1, dilation 1, "same" zero
- * padding, kernel ks = 1, 3 or 5, on contiguous NCHW fp32 tensors, fp32-equivalent bf16x3 arithmetic on the matrix cores
+ * padding, kernel ks = 1, 3, 4 or 5, on contiguous NCHW fp32 tensors, fp32-equivalent bf16x3 arithmetic on the matrix cores
  * (ks = 5 is accepted from the change that added the streamed kernel on, under the same signatures and the same plane layout --
  * by usf_conv2d_weight_elems, usf_conv2d_weight_planes_f32, usf_conv2d_same_fits, usf_conv2d_same_f32 and
  * usf_conv2d_same_ctx_f32; USF_ABI_VERSION is unchanged: no declaration or struct moved.  The fused forms
- * usf_conv2d_same_res_f32 / _gate_f32 keep answering 1 for ks != 3; ks = 4 is not expressible here: torch pads it 1 left /
- * 2 right, and the data gradient needs the mirror image):
+ * usf_conv2d_same_res_f32 / _gate_f32 keep answering 1 for ks != 3.  ks = 4, accepted by the same entry points (and by the
+ * internal header's batched plane split and variant probe) from the change that added the 16-tap instantiations on, again with
+ * no declaration moved, means torch's "same" placement: ONE zero before and TWO after the image in each axis,
+ * y[p] = sum_t w[t] x[p + t - 1], t = 0 .. 3; K = 16 cp is never padded.  Its data gradient needs the mirror image, two zeros
+ * before and one after: the entry point with a stated placement in usflows_hip_internal.h):
  *   y[b, co, p] = out_act( bias[co] + sum_{tap, ci} W[co, ci, tap] * (in_act(x[b, ci, p + tap]) * in_mul[ci, p + tap]) )
  * in_act / out_act: USF_ACT_NONE or USF_ACT_LEAKY_RELU (slope 0 = ReLU); in_mul [cin * H * W] or NULL (the coupling mask
  * in front of a conditioner's first convolution); bias [cout] or NULL.  Channels <= 64, H * W <= 256.
@@ -345,14 +348,15 @@ int64_t usf_conv2d_weight_elems(int64_t cin, int64_t cout, int64_t ks);
 /* The planes above from an fp32 nn.Conv2d weight w [cout, cin, ks, ks] on the device, one launch.  transposed == 0: planes of
  * this convolution (usf_conv2d_weight_elems(cin, cout, ks) bf16 elements).  transposed == 1: planes of the convolution that
  * computes its DATA gradient -- cout -> cin channels with W'[ci, co, ky, kx] = w[co, ci, ks-1-ky, ks-1-kx]
- * (usf_conv2d_weight_elems(cout, cin, ks) elements).  transposed == 2: both, back to back in `planes` (the first set, then the
+ * (usf_conv2d_weight_elems(cout, cin, ks) elements; at ks = 4 these are planes for the MIRRORED placement).  transposed == 2: both, back to back in `planes` (the first set, then the
  * second), in one launch -- what a training step needs of every convolution.  Not for the gated row packing (the caller
  * packs that on the host side). */
 int usf_conv2d_weight_planes_f32(const float* w, void* planes, int64_t cin, int64_t cout, int64_t ks, int32_t transposed,
                                  usf_stream_t stream);
 /* > 0 (samples per LDS group) when usf_conv2d_same_f32 serves these sizes: weight planes + one padded sample must fit 158 KB of LDS;
  * at ks = 5 the weights need not fit: where they leave no room for two samples they are streamed through a ring of two K slabs
- * beside the group's padded image (64 -> 64 channels at 7 x 7: two samples, 159 840 B) */
+ * beside the group's padded image (64 -> 64 channels at 7 x 7: two samples, 159 840 B); ks = 4 follows the same rule (64 -> 64 at
+ * 7 x 7: two samples, 141 696 B), and its answer holds for both placements of the zeros */
 int usf_conv2d_same_fits(int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks);
 int usf_conv2d_same_f32(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
                         const void* w_planes, const float* bias, const float* in_mul, int32_t in_act, float in_slope,

@@ -237,7 +237,7 @@ int usf_coupling_additive_vctx_f32(const usf_coupling_desc* d, const float* ctx,
                                    const float* W_ctx_t, int64_t ldw_ctx, const float* b_ctx, usf_stream_t stream);
 int usf_coupling_additive_vctx_variant(const usf_coupling_desc* d, int32_t ctx_dim);
 
-/* usf_conv_ctx_wgrad_f32 (ABI 36; ks = 1, 3 or 5 -- 5 on a 25-tap instantiation of the same kernel): the weight gradient of the context channel of usf_conv2d_same_ctx_f32 (usflows_hip.h;
+/* usf_conv_ctx_wgrad_f32 (ABI 36; ks = 1, 3, 4 or 5 -- 5 on a 25-tap, 4 on a 16-tap instantiation of the same kernel, the latter in torch's placement, one zero before and two after): the weight gradient of the context channel of usf_conv2d_same_ctx_f32 (usflows_hip.h;
  * reference networks.py:513-680 under autograd),
  *   dw_ctx[co, t] = sum_b ctx[b * ctx_stride] * sum over the p whose tap t lands inside the image of dy[b, co, p]
  * dy [B, cout, H, W] contiguous fp32, dw_ctx [cout, ks * ks].  One block per output channel reads its dy plane once; the sums
@@ -414,8 +414,42 @@ int usf_conv_wgrad_k5_f32(const float* x, const float* dy, int64_t B, int64_t ci
 int usf_conv_wgrad_k5_variant(const usf_conv_wgrad_query* q, usf_conv_wgrad_wide_info* out);
 int usf_conv_wgrad_k5_instances(int32_t* out, int32_t cap);
 
+/*
+ * usf_conv_wgrad_k4_f32 (an addition: USF_INTERNAL_VERSION is unchanged): the same for kernel 4 in torch's "same" placement,
+ *     dW[co, ci, ty, tx] = sum_{b, p} dy[b, co, p] * xin[b, ci, p + (ty - 1, tx - 1)],   db[co] = sum_{b, p} dy[b, co, p]
+ * -- an instantiation of usf_conv_wgrad_k5_f32's kernel with FOUR tap rows of FOUR taps dealt over grid.y (64 -> 64 channels:
+ * 4 * (4 * 4 + 1) = 68 tiles in tap row 0, 17 per wave), the same LDS geometry and size rule, the same instantiation set.
+ * Served: ks == 4 only (usf_conv_wgrad_k5_f32 keeps refusing it).  In the variant's answer T = 4 and position_parts = 4.
+ */
+int64_t usf_conv_wgrad_k4_workspace(int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks);
+int usf_conv_wgrad_k4_f32(const float* x, const float* dy, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
+                          const float* in_mul, const float* pre_sub, int32_t in_act, float in_slope, float* dW, float* db,
+                          float* workspace, int64_t workspace_floats, usf_stream_t stream);
+int usf_conv_wgrad_k4_variant(const usf_conv_wgrad_query* q, usf_conv_wgrad_wide_info* out);
+int usf_conv_wgrad_k4_instances(int32_t* out, int32_t cap);
+
+/*
+ * usf_conv2d_same_pad_f32 (an addition: USF_INTERNAL_VERSION is unchanged): usf_conv2d_same_f32 (usflows_hip.h) with the
+ * placement of the zero padding stated -- pad_before zeros before the image and ks - 1 - pad_before after it, in each axis:
+ *     y[p] = sum_t w[t] x[p + t - pad_before].
+ * pad_before == (ks - 1) / 2 is usf_conv2d_same_f32 itself (same kernels, same bits).  At an even ks (4) pad_before == ks / 2 is
+ * the MIRRORED placement, what the data gradient of a "same" convolution with an even kernel is on the flipped, transposed
+ * weight (usf_conv2d_weight_planes_f32 with transposed = 1): dx[q] = sum_s w[3 - s] dy[q + s - 2].  Every other pad_before, and
+ * gate_x != NULL with the mirrored placement, is refused with -2 and nothing is launched.  Only the training path's data
+ * gradient calls it (captured as a graph, never recorded as an op list).
+ * usf_conv2d_same_pad_fits: usf_conv2d_same_fits for a placement (0 for a pad_before the call refuses).  Both placements have
+ * the same padded image, (H + ks - 1) x (W + ks - 1), hence the same plan and LDS footprint: the answer for the mirrored
+ * placement IS usf_conv2d_same_fits' and usf_conv2d_same_variant's.
+ */
+int usf_conv2d_same_pad_fits(int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks, int64_t pad_before);
+int usf_conv2d_same_pad_f32(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
+                            int64_t pad_before, const void* w_planes, const float* bias, const float* in_mul, int32_t in_act,
+                            float in_slope, int32_t out_act, float out_slope, const float* gate_x, int64_t gate_channels,
+                            usf_stream_t stream);
+
 /* usf_conv2d_weight_planes_f32(transposed = 2) for MANY weights in one launch.  jobs / block_job are DEVICE arrays (as for
- * usf_partial_sum_jobs_f32): job j splits the fp32 weight w [cout, cin, ks, ks] into its planes followed by the planes of its
+ * usf_partial_sum_jobs_f32): job j splits the fp32 weight w [cout, cin, ks, ks] (any ks the single call takes; ks = 4: the second
+ * set is for the mirrored placement, usf_conv2d_same_pad_f32) into its planes followed by the planes of its
  * data-gradient convolution, at planes_base + out_off (bf16 elements; usf_conv2d_weight_elems(cin, cout, ks) +
  * usf_conv2d_weight_elems(cout, cin, ks) of them), and owns the blocks [first_block, first_block + ceil(max of the two
  * [rows x K] sizes / 256)); block_job[b] names block b's job.  Same bits as the single launches. */
@@ -501,15 +535,16 @@ int usf_conv2d_same_gate_f32(const float* x, float* y, int64_t B, int64_t cin, i
  *   2  conv2d_same_wreg_kernel<NB, CP, NCT, CTX> 3 x 3, 16 / 32 -> 16 / 32 / 64 channels, H W <= 64; only under the tuning
  *                                                knob conv_wsp=0; no gate-add form, residual forms up to 8192 outputs per group
  *   3  conv2d_same_wsp_kernel<NB, CP, NCT, CTX>  3 x 3, 16 / 32 / 48 -> 16 / 32 / 48 / 64 channels, H W <= 64
- *   4  conv2d_same_k5_stream_kernel<NR, CTX>     5 x 5 (an addition: USF_INTERNAL_VERSION is unchanged, the struct is as it
+ *   4  conv2d_same_stream_kernel<NR, CTX, KSZ>   5 x 5 and 4 x 4 (KSZ; an addition: USF_INTERNAL_VERSION is unchanged, the struct is as it
  *                                                was), plain / ctx calls where kernel 1 cannot hold the 25 taps' weight planes
  *                                                and two padded samples in the LDS: the group's image stays resident, the weights
  *                                                move through a ring of two K slabs, one barrier per slab (usf_conv_stream.hip).
- *                                                ks = 5 runs on kernel 1 where its best S is >= 2 (or nothing else fits), else here
+ *                                                ks = 4 / 5 runs on kernel 1 where its best S is >= 2 (or nothing else fits), else here
  * Kernels 2 and 3 want (cin H W) and (cout H W) multiples of 4 and every tensor 16-byte aligned; a plain / ctx call they do
  * not serve runs on kernel 1, a res / gate call they do not serve is answered with return code 1 (kernel 0 here).
  * Query: entry (USF_CONV_ENTRY_*; GATED: usf_conv2d_same_f32 with gate_x, cout = the packed row count), B, cin, cout, H, W,
- * ks, aligned (1: every tensor pointer is 16-byte aligned), cus (0: ask the device; > 0: plan for that many compute units --
+ * ks (1, 3, 4 or 5; the answer at ks = 4 holds for both placements of its zeros: the plans do not look at the placement),
+ * aligned (1: every tensor pointer is 16-byte aligned), cus (0: ask the device; > 0: plan for that many compute units --
  * works without a GPU).  The tuning knobs in force (conv_wreg, conv_wsp, conv_small_s) are honoured as a launch honours them.
  * Answer: kernel (0: not served / refused); S samples per group, groups = ceil(B / S), grid blocks, lds_bytes; for kernels 2
  * and 3 the instantiation (NB k-blocks, CP padded input channels, NCT output tiles) and the largest n each magic-number

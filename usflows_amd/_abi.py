@@ -354,6 +354,14 @@ INTERNAL_SYMBOLS = {
                                         C.c_void_p]),
     "usf_conv_wgrad_k5_variant": (C.c_int, [C.POINTER(ConvWgradQuery), C.POINTER(ConvWgradWideInfo)]),
     "usf_conv_wgrad_k5_instances": (C.c_int, [C.POINTER(C.c_int32), C.c_int32]),
+    "usf_conv2d_same_pad_fits": (C.c_int, [C.c_int64] * 6),
+    "usf_conv2d_same_pad_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 7 + [_fp, _fp, _fp, C.c_int32, C.c_float, C.c_int32, C.c_float, _fp,
+                                          C.c_int64, C.c_void_p]),
+    "usf_conv_wgrad_k4_workspace": (C.c_int64, [C.c_int64] * 6),
+    "usf_conv_wgrad_k4_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [_fp, _fp, C.c_int32, C.c_float, _fp, _fp, _fp, C.c_int64,
+                                        C.c_void_p]),
+    "usf_conv_wgrad_k4_variant": (C.c_int, [C.POINTER(ConvWgradQuery), C.POINTER(ConvWgradWideInfo)]),
+    "usf_conv_wgrad_k4_instances": (C.c_int, [C.POINTER(C.c_int32), C.c_int32]),
     "usf_conv_wgrad_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [_fp, _fp, C.c_int32, C.c_float, _fp, _fp, _fp, C.c_int64,
                                      C.c_void_p]),
     "usf_conv_wgrad_deferred_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [_fp, _fp, C.c_int32, C.c_float, _fp, _fp, _fp, C.c_int64,

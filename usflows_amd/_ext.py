@@ -544,6 +544,18 @@ def conv2d_same(x, planes, cout, ks, bias=None, in_mul=None, in_act=ACT_NONE, in
     return y
 
 
+def conv2d_same_pad(x, planes, cout, ks, pad_before, bias=None, in_mul=None, in_act=ACT_NONE, in_slope=0.0, out_act=ACT_NONE,
+                    out_slope=0.0):
+    """usf_conv2d_same_pad_f32: conv2d_same with the placement of the zeros stated (pad_before of them before the image in each
+    axis, ks - 1 - pad_before after): (ks - 1) // 2 is conv2d_same itself; ks // 2 at an even ks is the mirrored placement of a
+    data gradient.  Never recorded into an op list (the training path is captured as a graph)"""
+    B, cin, H, W = x.shape
+    y = torch.empty(B, cout, H, W, dtype=torch.float32, device=x.device)
+    _launch("usf_conv2d_same_pad_f32", (x.data_ptr(), y.data_ptr(), B, cin, cout, H, W, ks, int(pad_before), planes.data_ptr(), ptr(bias),
+            ptr(in_mul), int(in_act), float(in_slope), int(out_act), float(out_slope), None, 0, current_stream(x.device)), tape=False)
+    return y
+
+
 def conv2d_same_ctx(x, planes, cout, ks, ctx, w_ctx, bias=None, in_mul=None, in_act=ACT_NONE, in_slope=0.0, out_act=ACT_NONE,
                     out_slope=0.0):
     """usf_conv2d_same_ctx_f32: Conv2d(cin + 1, cout) over cat(in_act(x) * in_mul, ctx-plane) without the concatenated tensor.
@@ -1008,6 +1020,39 @@ def conv_wgrad_k5(x, dy, in_mul=None, pre_sub=None, in_act=ACT_NONE, in_slope=0.
     rc = _launch("usf_conv_wgrad_k5_f32", (x.data_ptr(), dy.data_ptr(), B, cin, cout, H, W, 5, ptr(in_mul), ptr(pre_sub), int(in_act),
                  float(in_slope), dW.data_ptr(), ptr(db), ws.data_ptr(), ws_n, current_stream(x.device)), tape=False, unserved_ok=True)
     return None if rc else (dW, db)
+
+
+def conv_wgrad_k4(x, dy, in_mul=None, pre_sub=None, in_act=ACT_NONE, in_slope=0.0, want_bias=True):
+    """usf_conv_wgrad_k4_f32: conv_wgrad's (dW [cout, cin, 4, 4], db | None) of a 4 x 4 "same" convolution in torch's placement
+    (one zero before, two after); None when the shape is not served.  Never deferred or queued, as conv_wgrad_k5"""
+    B, cin, H, W = x.shape
+    cout = dy.shape[1]
+    ws_n = load().usf_conv_wgrad_k4_workspace(B, cin, cout, H, W, 4)
+    if ws_n <= 0:
+        return None
+    ws = torch.empty(ws_n, dtype=torch.float32, device=x.device)
+    dW = torch.empty(cout, cin, 4, 4, dtype=torch.float32, device=x.device)
+    db = torch.empty(cout, dtype=torch.float32, device=x.device) if want_bias else None
+    rc = _launch("usf_conv_wgrad_k4_f32", (x.data_ptr(), dy.data_ptr(), B, cin, cout, H, W, 4, ptr(in_mul), ptr(pre_sub), int(in_act),
+                 float(in_slope), dW.data_ptr(), ptr(db), ws.data_ptr(), ws_n, current_stream(x.device)), tape=False, unserved_ok=True)
+    return None if rc else (dW, db)
+
+
+def conv_wgrad_k4_variant(B, cin, cout, H, W, ks=4, cus=0, blocks_per_cu=0) -> dict:
+    """usf_conv_wgrad_k4_variant: the plan usf_conv_wgrad_k4_f32 launches from, as a dict (served 0: the call returns 1)"""
+    q = ConvWgradQuery(int(B), int(cin), int(cout), int(H), int(W), int(ks), 0, int(cus), int(blocks_per_cu), 0)
+    out = ConvWgradWideInfo()
+    check(load().usf_conv_wgrad_k4_variant(C.byref(q), C.byref(out)), "usf_conv_wgrad_k4_variant")
+    return {name: int(getattr(out, name)) for name, _ in ConvWgradWideInfo._fields_ if name != "reserved"}
+
+
+def conv_wgrad_k4_instances() -> list:
+    """usf_conv_wgrad_k4_instances: the tiles-per-wave values the shared kernel file instantiates (usf_conv_wgrad_k5_instances')"""
+    lib = load()
+    n = lib.usf_conv_wgrad_k4_instances(None, 0)
+    buf = (C.c_int32 * n)()
+    lib.usf_conv_wgrad_k4_instances(buf, n)
+    return list(buf)
 
 
 def conv_wgrad_k5_variant(B, cin, cout, H, W, ks=5, cus=0, blocks_per_cu=0) -> dict:

@@ -116,7 +116,7 @@ int conv2d_same_res(const float* x, float* y, int64_t B, int64_t cin, int64_t co
 int conv2d_same(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
                 const void* wplanes, const float* bias, const float* in_mul, int32_t in_act, float in_slope,
                 int32_t out_act, float out_slope, const float* gate_x, int64_t gate_channels, hipStream_t stream,
-                const float* ctx = nullptr, int64_t ctx_stride = 0, const float* w_ctx = nullptr);
+                const float* ctx = nullptr, int64_t ctx_stride = 0, const float* w_ctx = nullptr, int pad_before = -1);
 int conv2d_same_variant(const usf_conv_variant_query* q, usf_conv_variant* out);
 int conv_ctx_wgrad(const float* dy, const float* ctx, int64_t ctx_stride, int64_t B, int64_t cout, int64_t H, int64_t W, int64_t ks,
                    float* dw_ctx, hipStream_t stream);
@@ -520,6 +520,18 @@ int usf_conv2d_same_f32(const float* x, float* y, int64_t B, int64_t cin, int64_
                         int32_t out_act, float out_slope, const float* gate_x, int64_t gate_channels, usf_stream_t stream) {
   return usf::conv2d_same(x, y, B, cin, cout, H, W, ks, w_planes, bias, in_mul, in_act, in_slope, out_act, out_slope,
                           gate_x, gate_channels, (hipStream_t)stream);
+}
+int usf_conv2d_same_pad_fits(int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks, int64_t pad_before) {
+  if (ks < 1 || (pad_before != (ks - 1) / 2 && pad_before != ks / 2)) return 0;
+  return usf::conv2d_same_fits(cin, cout, H, W, ks);                // (the plans do not look at the placement)
+}
+int usf_conv2d_same_pad_f32(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
+                            int64_t pad_before, const void* w_planes, const float* bias, const float* in_mul, int32_t in_act,
+                            float in_slope, int32_t out_act, float out_slope, const float* gate_x, int64_t gate_channels,
+                            usf_stream_t stream) {
+  if (pad_before < 0 || pad_before > ks) { usf::set_error("usf_conv2d_same_pad_f32: bad pad_before"); return -2; }
+  return usf::conv2d_same(x, y, B, cin, cout, H, W, ks, w_planes, bias, in_mul, in_act, in_slope, out_act, out_slope,
+                          gate_x, gate_channels, (hipStream_t)stream, nullptr, 0, nullptr, (int)pad_before);
 }
 int usf_conv_ctx_wgrad_f32(const float* dy, const float* ctx, int64_t ctx_stride, int64_t B, int64_t cout, int64_t H, int64_t W,
                            int64_t ks, float* dw_ctx, usf_stream_t stream) {

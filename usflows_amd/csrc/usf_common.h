@@ -121,10 +121,28 @@ __host__ __device__ __forceinline__ unsigned ctx_tapmask5(int py, int px, int H,
   }
   return rows * cols;                                                        // (no carries: cols < 32)
 }
+// ks = 4 in torch's "same" placement (one zero before, two after): 16 bits, bit dy * 4 + dx set when 0 <= py + dy - 1 < H and
+// 0 <= px + dx - 1 < W.  Chosen at compile time by the 4 x 4 instantiations, as ctx_tapmask5 by the 5 x 5 ones.
+__host__ __device__ __forceinline__ unsigned ctx_tapmask4(int py, int px, int H, int W) {
+  unsigned rows = 0u, cols = 0u;
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    rows |= ((unsigned)(py + d - 1) < (unsigned)H ? 1u : 0u) << (4 * d);     // bit 4 d: tap row d reads inside
+    cols |= ((unsigned)(px + d - 1) < (unsigned)W ? 1u : 0u) << d;
+  }
+  return rows * cols;                                                        // (no carries: cols < 16)
+}
 // S for one output channel: wc = w_ctx + co * ks * ks, taps added in index order (deterministic)
 __device__ __forceinline__ float ctx_tapsum(const float* wc, int taps, unsigned mask) {
   float s = 0.f;
   for (int t = 0; t < taps; ++t) s += ((mask >> t) & 1u) ? wc[t] : 0.f;
+  return s;
+}
+// ... over the 16 taps of ks = 4.  A function of its own for the streamed kernel's 4 x 4 instantiations: beside them, its 5 x 5
+// instantiations stay the only callers of ctx_tapsum in their unit, all with 25 taps, and compile to what they did
+__device__ __forceinline__ float ctx_tapsum4(const float* wc, unsigned mask) {
+  float s = 0.f;
+  for (int t = 0; t < 16; ++t) s += ((mask >> t) & 1u) ? wc[t] : 0.f;
   return s;
 }
 

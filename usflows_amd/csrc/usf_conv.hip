@@ -1,6 +1,6 @@
 // Convolution conditioner of the image-shaped flows: Conv2d with stride 1, "same" zero padding,
-// kernel 1 x 1, 3 x 3 or 5 x 5 (networks.py:405-510 ConvNet2D, :61-122 GatedConv; 5 x 5 where the 25 taps' weight planes and two
-// samples fit the LDS, otherwise on the streamed kernel of usf_conv_stream.hip) as an implicit GEMM on the bf16 matrix cores
+// kernel 1 x 1, 3 x 3, 4 x 4 or 5 x 5 (networks.py:405-510 ConvNet2D, :61-122 GatedConv; 4 x 4 / 5 x 5 where the taps' weight planes
+// and two samples fit the LDS, otherwise on the streamed kernel of usf_conv_stream.hip) as an implicit GEMM on the bf16 matrix cores
 // with the fp32-equivalent bf16x3 arithmetic of the rest of the path (three bf16 planes per operand, six
 // v_mfma_f32_16x16x32_bf16 per product, fp32 accumulation).
 //
@@ -42,6 +42,7 @@ struct ConvArgs {
   int dbg;                     // tuning aid (USF_CONV_DBG): 1 no staging, 2 no k loop, 4 no output stores, 8 no input loads
   const float* ctx; int ctx_stride;   // context channel (CTX instantiation only): ctx[b * ctx_stride], see usf_conv2d_same_ctx_f32
   const float* w_ctx;          // [cout][ks * ks] weights of the context channel
+  int pb;                      // K4 instantiations only: zeros before the image in each axis, 1 (torch's "same") or 2 (its mirror image)
 };
 
 __device__ __forceinline__ void cv_split(float x, __bf16& h, __bf16& m, __bf16& l) {
@@ -53,15 +54,16 @@ __device__ __forceinline__ void cv_split(float x, __bf16& h, __bf16& m, __bf16& 
 
 // CTX: the context channel's rank-1 term joins the bias in the epilogue (usf_conv2d_same_ctx_f32); false: the plain kernel
 // K5: the ks = 5 instantiations (their context mask is ctx_tapmask5); false: ks = 1 / 3, compiled as before ks = 5 existed
-template <bool CTX, bool K5 = false>
+// K4: the ks = 4 instantiations: the padded image is (H + 3) x (W + 3), a.pb of its zeros lie before the image; context mask ctx_tapmask4
+template <bool CTX, bool K5 = false, bool K4 = false>
 __global__ __launch_bounds__(512, 2) void conv2d_same_bf16x3_kernel(const ConvArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, lg = lane >> 4;
   const int HW = a.H * a.W;
-  const int pad = a.ks >> 1;
-  const int PW = a.W + 2 * pad, PP = (a.H + 2 * pad) * PW;         // padded image
+  const int pad = K4 ? a.pb : a.ks >> 1;
+  const int PW = K4 ? a.W + 3 : a.W + 2 * pad, PP = (K4 ? a.H + 3 : a.H + 2 * pad) * PW;   // padded image
   const int taps = a.ks * a.ks;
   const int wrow = a.ws16 * 16, xrow = a.xs16 * 16;                // bytes per LDS row
   const int wplane = a.coutp * wrow, xplane = a.S * PP * xrow;      // bytes per plane
@@ -232,7 +234,8 @@ __global__ __launch_bounds__(512, 2) void conv2d_same_bf16x3_kernel(const ConvAr
           if constexpr (CTX) {
             const int py = p / a.W;
             cx = a.ctx[(size_t)(s0 + sl) * a.ctx_stride];
-            cmask = K5 ? ctx_tapmask5(py, p - py * a.W, a.H, a.W) : ctx_tapmask(py, p - py * a.W, a.H, a.W, a.ks);
+            cmask = K4 ? ctx_tapmask4(py, p - py * a.W, a.H, a.W)
+                       : K5 ? ctx_tapmask5(py, p - py * a.W, a.H, a.W) : ctx_tapmask(py, p - py * a.W, a.H, a.W, a.ks);
           }
           if (PC == 2 && a.gateC > 0) {
             // gated mode: the patch's two tiles are (value, gate) of the same 16 channels (rows interleaved at pack time):
@@ -286,29 +289,32 @@ static int odd16(int units) { return units | 1; }
 // fourth kernel (usf_conv_stream.hip)
 int conv2d_same_stream(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, const void* wplanes,
                        const float* bias, const float* in_mul, int32_t in_act, float in_slope, int32_t out_act, float out_slope,
-                       const float* ctx, int64_t ctx_stride, const float* w_ctx, const ConvSPlan& pl, hipStream_t stream);
+                       const float* ctx, int64_t ctx_stride, const float* w_ctx, const ConvSPlan& pl, hipStream_t stream, int ks = 5,
+                       int pad_before = 2);
 
 // LDS bytes of a launch with S samples per group; the layout the kernel derives from the same numbers
 static int64_t conv_lds_bytes(int cin, int cout, int H, int W, int ks, int S, int* xs16, int* ws16, int* cp_, int* kp_, int* coutp_) {
   const int cp = (cin + 7) / 8 * 8, taps = ks * ks, kp = (taps * cp + 31) / 32 * 32, coutp = (cout + 15) / 16 * 16;
-  const int pad = ks / 2, PP = (H + 2 * pad) * (W + 2 * pad);
+  const int PP = (H + ks - 1) * (W + ks - 1);                       // (ks = 4: three zeros per axis, in either placement)
   *xs16 = odd16(cp / 8); *ws16 = odd16(kp / 8); *cp_ = cp; *kp_ = kp; *coutp_ = coutp;
   return 3LL * coutp * (*ws16) * 16 + 3LL * S * PP * (*xs16) * 16;
 }
 
 // elements ([3][coutp][kp] bf16) of the weight planes usf_conv2d_same_f32 expects for these sizes
 int64_t conv2d_weight_elems(int64_t cin, int64_t cout, int64_t ks) {
-  if (cin <= 0 || cout <= 0 || (ks != 1 && ks != 3 && ks != 5)) return -1;
+  if (cin <= 0 || cout <= 0 || (ks != 1 && ks != 3 && ks != 4 && ks != 5)) return -1;
   const int64_t cp = (cin + 7) / 8 * 8, kp = (ks * ks * cp + 31) / 32 * 32, coutp = (cout + 15) / 16 * 16;
   return 3 * coutp * kp;
 }
 
+static int conv_k45_route(int cin, int cout, int H, int W, int ks, bool gated, int* S_best);
+
 // samples per group the kernel would use for these sizes (the LDS decides); 0: the shape is not served
 int conv2d_same_fits(int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks) {
-  if (cin <= 0 || cout <= 0 || H <= 0 || W <= 0 || cin > 64 || cout > 64 || H * W > 256 || (ks != 1 && ks != 3 && ks != 5)) return 0;
-  if (ks == 5) {
+  if (cin <= 0 || cout <= 0 || H <= 0 || W <= 0 || cin > 64 || cout > 64 || H * W > 256 || (ks != 1 && ks != 3 && ks != 4 && ks != 5)) return 0;
+  if (ks == 4 || ks == 5) {
     int S = 0;
-    return conv_k5_route((int)cin, (int)cout, (int)H, (int)W, false, &S) ? S : 0;
+    return conv_k45_route((int)cin, (int)cout, (int)H, (int)W, (int)ks, false, &S) ? S : 0;
   }
   int xs, ws, cp, kp, coutp;
   for (int S = 8; S >= 1; --S)
@@ -342,17 +348,19 @@ int conv_first_plan(int64_t B, int cin, int cout, int H, int W, int ks, int cus,
   return 0;
 }
 
-// ks = 5: the first kernel where its weights and two samples fit the LDS, otherwise the streamed kernel (no gated mode there),
-// otherwise the first kernel with one sample
-int conv_k5_route(int cin, int cout, int H, int W, bool gated, int* S_best) {
+// ks = 4 / 5: the first kernel where its weights and two samples fit the LDS, otherwise the streamed kernel (no gated mode
+// there), otherwise the first kernel with one sample.  Neither plan looks at the placement of a 4 x 4 kernel's zeros.
+static int conv_k45_route(int cin, int cout, int H, int W, int ks, bool gated, int* S_best) {
   ConvPlan p1;
-  const int s1 = conv_first_plan(1 << 20, cin, cout, H, W, 5, 1, &p1) == 0 ? p1.S : 0;
+  const int s1 = conv_first_plan(1 << 20, cin, cout, H, W, ks, 1, &p1) == 0 ? p1.S : 0;
   ConvSPlan ps;
-  const int ss = gated ? 0 : (conv_stream_plan(1 << 20, cin, cout, H, W, 1, &ps) == 0 ? ps.S : 0);
+  const int ss = gated ? 0 : (conv_stream_plan(1 << 20, cin, cout, H, W, 1, &ps, ks) == 0 ? ps.S : 0);
   if (s1 >= 2 || ss < 1) { *S_best = s1; return s1 >= 1 ? 1 : 0; }
   *S_best = ss;
   return 4;
 }
+int conv_k5_route(int cin, int cout, int H, int W, bool gated, int* S_best) { return conv_k45_route(cin, cout, H, W, 5, gated, S_best); }
+int conv_k4_route(int cin, int cout, int H, int W, bool gated, int* S_best) { return conv_k45_route(cin, cout, H, W, 4, gated, S_best); }
 
 // usf_conv2d_same_variant: the plans above, asked instead of launched (no pointer is looked at, nothing is launched)
 int conv2d_same_variant(const usf_conv_variant_query* q, usf_conv_variant* o) {
@@ -364,7 +372,7 @@ int conv2d_same_variant(const usf_conv_variant_query* q, usf_conv_variant* o) {
   if (e < USF_CONV_ENTRY_PLAIN || e > USF_CONV_ENTRY_GATED) { set_error("usf_conv2d_same_variant: bad entry"); return -2; }
   if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0 || B > 0x7fffffff) return 0;
   const bool fused = e == USF_CONV_ENTRY_RES || e == USF_CONV_ENTRY_GATE_MUL || e == USF_CONV_ENTRY_GATE_ADD;
-  const bool first_ok = !(cin > 64 || cout > 64 || H * W > 256 || (ks != 1 && ks != 3 && ks != 5));   // conv2d_same's size rule
+  const bool first_ok = !(cin > 64 || cout > 64 || H * W > 256 || (ks != 1 && ks != 3 && ks != 4 && ks != 5));   // conv2d_same's size rule
   if (fused ? ks != 3 : !first_ok) return 0;
   if (e == USF_CONV_ENTRY_GATED && cout % 32 != 0) return 0;
   const int cus = q->cus > 0 ? q->cus : device_cu_count();
@@ -385,13 +393,13 @@ int conv2d_same_variant(const usf_conv_variant_query* q, usf_conv_variant* o) {
     }
   }
   if (fused) return 0;                                     // the fused forms live on the second / third kernel only
-  if (ks == 5) {
+  if (ks == 4 || ks == 5) {
     int sb = 0;
-    const int route = conv_k5_route((int)cin, (int)cout, (int)H, (int)W, e == USF_CONV_ENTRY_GATED, &sb);
+    const int route = conv_k45_route((int)cin, (int)cout, (int)H, (int)W, (int)ks, e == USF_CONV_ENTRY_GATED, &sb);
     if (route == 0) return 0;
     if (route == 4) {
       ConvSPlan sp;
-      if (conv_stream_plan(B, (int)cin, (int)cout, (int)H, (int)W, cus, &sp) != 0) return 0;
+      if (conv_stream_plan(B, (int)cin, (int)cout, (int)H, (int)W, cus, &sp, (int)ks) != 0) return 0;
       o->kernel = 4; o->S = sp.S; o->grid = sp.grid; o->groups = sp.groups; o->lds_bytes = sp.lds;
       o->NB = sp.KS / 32; o->CP = sp.cp; o->NCT = sp.depth; o->CTX = e == USF_CONV_ENTRY_CTX;
       o->PC_full = o->PC_last = 2; o->PR_full = o->PR_last = sp.NR;
@@ -412,10 +420,19 @@ int conv2d_same_variant(const usf_conv_variant_query* q, usf_conv_variant* o) {
 int conv2d_same(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
                 const void* wplanes, const float* bias, const float* in_mul, int32_t in_act, float in_slope,
                 int32_t out_act, float out_slope, const float* gate_x, int64_t gate_channels, hipStream_t stream,
-                const float* ctx, int64_t ctx_stride, const float* w_ctx) {
-  if (B < 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0 || cin > 64 || cout > 64 || H * W > 256 || (ks != 1 && ks != 3 && ks != 5) ||
+                const float* ctx, int64_t ctx_stride, const float* w_ctx, int pad_before) {
+  if (pad_before < 0) pad_before = (int)((ks - 1) / 2);             // the public entry points: torch's "same" placement
+  if (B < 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0 || cin > 64 || cout > 64 || H * W > 256 || (ks != 1 && ks != 3 && ks != 4 && ks != 5) ||
       B > 0x7fffffff) {
-    set_error("usf_conv2d_same_f32: unsupported sizes (channels 1..64, H * W <= 256, kernel 1, 3 or 5)");
+    set_error("usf_conv2d_same_f32: unsupported sizes (channels 1..64, H * W <= 256, kernel 1, 3, 4 or 5)");
+    return -2;
+  }
+  if (pad_before != (ks - 1) / 2 && pad_before != ks / 2) {
+    set_error("usf_conv2d_same_pad_f32: pad_before must be (ks - 1) / 2 or, at an even ks, ks / 2");
+    return -2;
+  }
+  if (pad_before != (ks - 1) / 2 && (ctx || gate_x)) {
+    set_error("usf_conv2d_same_pad_f32: the mirrored placement has no context or gated form");
     return -2;
   }
   if (B == 0) return 0;
@@ -438,17 +455,17 @@ int conv2d_same(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, 
                                     nullptr, 0.f, 0, stream, ctx, ctx_stride, w_ctx);
     if (rc != 0) return rc < 0 ? rc : 0;
   }
-  if (ks == 5) {
+  if (ks == 4 || ks == 5) {
     int sb = 0;
-    const int route = conv_k5_route((int)cin, (int)cout, (int)H, (int)W, gate_x != nullptr, &sb);
+    const int route = conv_k45_route((int)cin, (int)cout, (int)H, (int)W, (int)ks, gate_x != nullptr, &sb);
     if (route == 4) {
       ConvSPlan sp;
-      if (conv_stream_plan(B, (int)cin, (int)cout, (int)H, (int)W, 0, &sp) != 0) {
+      if (conv_stream_plan(B, (int)cin, (int)cout, (int)H, (int)W, 0, &sp, (int)ks) != 0) {
         set_error("usf_conv2d_same_f32: no streamed plan");
         return -3;
       }
       return conv2d_same_stream(x, y, B, cin, cout, H, W, wplanes, bias, in_mul, in_act, in_slope, out_act, out_slope, ctx, ctx_stride,
-                                w_ctx, sp, stream);
+                                w_ctx, sp, stream, (int)ks, pad_before);
     }
   }
   ConvArgs a;
@@ -458,6 +475,7 @@ int conv2d_same(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, 
   a.dbg = (int)tuning("conv_dbg", 0);
   a.gate_x = gate_x; a.gateC = (int)gate_channels;
   a.ctx = ctx; a.ctx_stride = (int)ctx_stride; a.w_ctx = w_ctx;
+  a.pb = pad_before;
   ConvPlan pl;
   if (conv_first_plan(B, a.cin, a.cout, a.H, a.W, a.ks, 0, &pl) != 0) {
     set_error("usf_conv2d_same_f32: one sample does not fit the LDS / staging registers (%lld bytes)", (long long)pl.lds);
@@ -466,10 +484,12 @@ int conv2d_same(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, 
   const int64_t lds = pl.lds;
   a.xs16 = pl.xs16; a.ws16 = pl.ws16; a.cp = pl.cp; a.kp = pl.kp; a.coutp = pl.coutp;
   a.S = pl.S;
-  static bool attr_done_dev[4][USF_MAX_DEVICES] = {{false}};   // (the attribute belongs to the device and the instantiation)
-  const bool k5 = ks == 5;
-  bool& attr_done = attr_done_dev[(ctx ? 1 : 0) + (k5 ? 2 : 0)][current_device_slot()];
-  const void* kfn = k5 ? (ctx ? reinterpret_cast<const void*>(&conv2d_same_bf16x3_kernel<true, true>)
+  static bool attr_done_dev[6][USF_MAX_DEVICES] = {{false}};   // (the attribute belongs to the device and the instantiation)
+  const bool k5 = ks == 5, k4 = ks == 4;
+  bool& attr_done = attr_done_dev[(ctx ? 1 : 0) + (k5 ? 2 : 0) + (k4 ? 4 : 0)][current_device_slot()];
+  const void* kfn = k4 ? (ctx ? reinterpret_cast<const void*>(&conv2d_same_bf16x3_kernel<true, false, true>)
+                              : reinterpret_cast<const void*>(&conv2d_same_bf16x3_kernel<false, false, true>))
+                  : k5 ? (ctx ? reinterpret_cast<const void*>(&conv2d_same_bf16x3_kernel<true, true>)
                               : reinterpret_cast<const void*>(&conv2d_same_bf16x3_kernel<false, true>))
                        : (ctx ? reinterpret_cast<const void*>(&conv2d_same_bf16x3_kernel<true>)
                               : reinterpret_cast<const void*>(&conv2d_same_bf16x3_kernel<false>));
@@ -481,7 +501,9 @@ int conv2d_same(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, 
     attr_done = true;
   }
   const unsigned grid = pl.grid;
-  if (k5 && ctx) hipLaunchKernelGGL((conv2d_same_bf16x3_kernel<true, true>), dim3(grid), dim3(512), (size_t)lds, stream, a);
+  if (k4 && ctx) hipLaunchKernelGGL((conv2d_same_bf16x3_kernel<true, false, true>), dim3(grid), dim3(512), (size_t)lds, stream, a);
+  else if (k4) hipLaunchKernelGGL((conv2d_same_bf16x3_kernel<false, false, true>), dim3(grid), dim3(512), (size_t)lds, stream, a);
+  else if (k5 && ctx) hipLaunchKernelGGL((conv2d_same_bf16x3_kernel<true, true>), dim3(grid), dim3(512), (size_t)lds, stream, a);
   else if (k5) hipLaunchKernelGGL((conv2d_same_bf16x3_kernel<false, true>), dim3(grid), dim3(512), (size_t)lds, stream, a);
   else if (ctx) hipLaunchKernelGGL(conv2d_same_bf16x3_kernel<true>, dim3(grid), dim3(512), (size_t)lds, stream, a);
   else hipLaunchKernelGGL(conv2d_same_bf16x3_kernel<false>, dim3(grid), dim3(512), (size_t)lds, stream, a);

@@ -51,7 +51,7 @@ struct ConvWQuery {
   int cus;                      // compute units to plan for
 };
 
-// fourth kernel (conv2d_same_k5_stream_kernel, usf_conv_stream.hip): 5 x 5, weights streamed through an LDS ring
+// fourth kernel (conv2d_same_stream_kernel, usf_conv_stream.hip): 5 x 5 and 4 x 4, weights streamed through an LDS ring
 struct ConvSPlan {
   int S;                        // samples per group, clipped to B (0: not even one sample fits)
   int S_best;                   // ... of a batch that does not clip it
@@ -67,10 +67,13 @@ struct ConvSPlan {
 inline int conv_stage_iters(int cin, int HW, int S) { return ((S * ((cin + 1) / 2) + 7) / 8) * ((HW + 63) / 64); }
 
 int conv_first_plan(int64_t B, int cin, int cout, int H, int W, int ks, int cus, ConvPlan* p);
-int conv_stream_plan(int64_t B, int cin, int cout, int H, int W, int cus, ConvSPlan* p);
+int conv_stream_plan(int64_t B, int cin, int cout, int H, int W, int cus, ConvSPlan* p, int ks = 5);
 // which kernel serves ks = 5 for these sizes: 1 (weights resident: its best S >= 2, or nothing else fits), 4 (streamed), 0 (none);
 // *S_best = samples per group of a batch that does not clip them
 int conv_k5_route(int cin, int cout, int H, int W, bool gated, int* S_best);
+// the same rule for ks = 4; one answer serves both placements of its zeros (1 before / 2 after, and the mirror image): the padded
+// image is (H + 3) x (W + 3) either way
+int conv_k4_route(int cin, int cout, int H, int W, bool gated, int* S_best);
 void conv_wreg_launch_plan(const ConvWQuery& q, ConvWPlan* p);
 
 }  // namespace usf

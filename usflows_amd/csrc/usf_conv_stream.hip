@@ -1,6 +1,8 @@
 // Fourth kernel of the "same" convolution: 5 x 5 taps with the weights STREAMED (usf_conv2d_same_f32 / _ctx_f32 at ks = 5 where
 // the first kernel cannot keep three weight planes of 25 taps and two padded samples in the LDS: 32 -> 32 channels alone is
-// 155 136 B of planes).  Operands, K order and arithmetic are the first kernel's (usf_conv.hip): planes [3][coutp][kp] bf16,
+// 155 136 B of planes), and the 4 x 4 instantiations of the same kernel (KSZ = 4: 16 taps, K = 16 cp is a whole number of
+// slabs; a (H + 3) x (W + 3) image with a.pb zeros before it in each axis -- 1: torch's "same", 2: its mirror image).
+// Operands, K order and arithmetic are the first kernel's (usf_conv.hip): planes [3][coutp][kp] bf16,
 // tap-major / channel-minor K, six v_mfma_f32_16x16x32_bf16 per product, fp32 accumulation, in_act / in_mul / bias / out_act.
 //
 // Data flow of a 512-thread block (persistent over groups of S samples):
@@ -35,8 +37,14 @@ struct ConvSArgs {
   unsigned mcp;                // floor(2^20 / cp) + 1: k / cp == (k * mcp) >> 20 for k < 2^14
   int in_act, out_act; float in_slope, out_slope;
   const float* ctx; int ctx_stride;
-  const float* w_ctx;          // [cout][25]
+  const float* w_ctx;          // [cout][KSZ * KSZ]
 };
+// the 4 x 4 instantiations' arguments: the placement behind the 5 x 5 ones' (whose kernel arguments stay what they were)
+struct ConvSArgs4 : ConvSArgs {
+  int pb;                      // zeros before the image in each axis (1: torch's "same", 2: its mirror image)
+};
+template <int KSZ> struct ConvSArgsOf { typedef ConvSArgs type; };
+template <> struct ConvSArgsOf<4> { typedef ConvSArgs4 type; };
 
 __device__ __forceinline__ void cs_split(float x, __bf16& h, __bf16& m, __bf16& l) {
   h = (__bf16)x;
@@ -45,15 +53,19 @@ __device__ __forceinline__ void cs_split(float x, __bf16& h, __bf16& m, __bf16& 
   l = (__bf16)(r - (float)m);
 }
 
-template <int NR, bool CTX>
-__global__ __launch_bounds__(512) void conv2d_same_k5_stream_kernel(const ConvSArgs a) {
+template <int NR, bool CTX, int KSZ>
+__global__ __launch_bounds__(512) void conv2d_same_stream_kernel(const typename ConvSArgsOf<KSZ>::type a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int PAD = 2, TAPS = 25;
+  static_assert(KSZ == 4 || KSZ == 5, "5 x 5 or 4 x 4");
+  constexpr int TAPS = KSZ * KSZ;
+  int PAD = 2;                                                       // (a constant of the 5 x 5 instantiations)
+  if constexpr (KSZ == 4) PAD = a.pb;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, lg = lane >> 4;
   const int HW = a.H * a.W;
-  const int PW = a.W + 2 * PAD, PP = (a.H + 2 * PAD) * PW;          // padded image
+  constexpr int PADT = KSZ - 1;                                      // zeros per axis, before and after
+  const int PW = a.W + PADT, PP = (a.H + PADT) * PW;                 // padded image
   const int xrow = a.xs16 * 16, srow = a.ss16 * 16;                  // bytes per LDS row
   const int xplane = a.S * PP * xrow, splane = a.coutp * srow;       // bytes per plane
   unsigned char* const Xl = smem;
@@ -204,7 +216,7 @@ __global__ __launch_bounds__(512) void conv2d_same_k5_stream_kernel(const ConvSA
           int tap = (int)(((unsigned)kflat * a.mcp) >> 20);
           const int c = kflat - tap * a.cp;
           tap = min(tap, TAPS - 1);                                  // K padding: weights are zero there
-          const int dy = tap / 5, dx = tap - dy * 5;
+          const int dy = tap / KSZ, dx = tap - dy * KSZ;
           const int xoff = (dy * PW + dx) * xrow + 2 * c;
           const int woff = 2 * kin;
           cs_bf16x8 w[2][3];
@@ -242,7 +254,8 @@ __global__ __launch_bounds__(512) void conv2d_same_k5_stream_kernel(const ConvSA
         if constexpr (CTX) {
           const int py = p / a.W;
           cx = a.ctx[(size_t)(s0 + sl) * a.ctx_stride];
-          cmask = ctx_tapmask5(py, p - py * a.W, a.H, a.W);
+          if constexpr (KSZ == 5) cmask = ctx_tapmask5(py, p - py * a.W, a.H, a.W);
+          else cmask = ctx_tapmask4(py, p - py * a.W, a.H, a.W);
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -252,7 +265,8 @@ __global__ __launch_bounds__(512) void conv2d_same_k5_stream_kernel(const ConvSA
             const int co = co0 + 16 * i + 4 * lg + j;
             if (co < a.cout) {
               float v = acc[i][b][j] + (a.bias ? a.bias[co] : 0.f);
-              if constexpr (CTX) v += cx * ctx_tapsum(a.w_ctx + co * TAPS, TAPS, cmask);
+              if constexpr (CTX && KSZ == 5) v += cx * ctx_tapsum(a.w_ctx + co * TAPS, TAPS, cmask);
+              if constexpr (CTX && KSZ == 4) v += cx * ctx_tapsum4(a.w_ctx + co * TAPS, cmask);
               yb[(size_t)co * HW] = act_apply(v, a.out_act, a.out_slope);
             }
           }
@@ -266,39 +280,39 @@ __global__ __launch_bounds__(512) void conv2d_same_k5_stream_kernel(const ConvSA
 static int cs_odd16(int units) { return units | 1; }
 
 // LDS bytes / layout of a launch with S samples per group and slabs of KS
-static int64_t conv_stream_lds(int cin, int cout, int H, int W, int S, int KS, ConvSPlan* p) {
+static int64_t conv_stream_lds(int cin, int cout, int H, int W, int ks, int S, int KS, ConvSPlan* p) {
   p->cp = (cin + 7) / 8 * 8;
-  p->kp = (25 * p->cp + 31) / 32 * 32;
+  p->kp = (ks * ks * p->cp + 31) / 32 * 32;
   p->coutp = (cout + 15) / 16 * 16;
   p->xs16 = cs_odd16(p->cp / 8);
   p->ss16 = cs_odd16(KS / 8);
-  const int PP = (H + 4) * (W + 4);
+  const int PP = (H + ks - 1) * (W + ks - 1);
   return 3LL * S * PP * p->xs16 * 16 + 2LL * 3 * p->coutp * p->ss16 * 16;
 }
 
 // largest S (<= cap) of a launch with slabs of KS: the LDS (158 KB, as the first kernel), the staging registers and four row
 // tiles per wave decide; 0: not one sample fits
-static int conv_stream_best_s(int cin, int cout, int H, int W, int KS, int cap) {
+static int conv_stream_best_s(int cin, int cout, int H, int W, int ks, int KS, int cap) {
   ConvSPlan p;
   const int coutp = (cout + 15) / 16 * 16, wpc = 8 / ((coutp + 31) / 32);
   for (int S = cap < 8 ? cap : 8; S >= 1; --S)
-    if (conv_stream_lds(cin, cout, H, W, S, KS, &p) <= 158 * 1024 && conv_stage_iters(cin, H * W, S) <= 16 &&
+    if (conv_stream_lds(cin, cout, H, W, ks, S, KS, &p) <= 158 * 1024 && conv_stage_iters(cin, H * W, S) <= 16 &&
         (S * H * W + 15) / 16 <= 4 * wpc) return S;
   return 0;
 }
 
-// The streamed kernel's launch for B samples (ks = 5, sizes inside conv2d_same's rule): slabs of 64 K values unless only
+// The streamed kernel's launch for B samples (ks = 5 or 4, sizes inside conv2d_same's rule): slabs of 64 K values unless only
 // slabs of 32 bring a second sample into the LDS; S clipped to B; NR = row tiles per wave, rounded up to an instantiation.
-int conv_stream_plan(int64_t B, int cin, int cout, int H, int W, int cus, ConvSPlan* p) {
+int conv_stream_plan(int64_t B, int cin, int cout, int H, int W, int cus, ConvSPlan* p, int ks) {
   const int cap = B < 8 ? (int)B : 8;
-  const int s64 = conv_stream_best_s(cin, cout, H, W, 64, 8), s32 = conv_stream_best_s(cin, cout, H, W, 32, 8);
+  const int s64 = conv_stream_best_s(cin, cout, H, W, ks, 64, 8), s32 = conv_stream_best_s(cin, cout, H, W, ks, 32, 8);
   const int KS = (s64 < 2 && s32 > s64) ? 32 : 64;
   const int best = KS == 64 ? s64 : s32;
   *p = ConvSPlan();
   p->KS = KS; p->depth = 2; p->S_best = best;
-  if (best < 1) { p->lds = conv_stream_lds(cin, cout, H, W, 1, KS, p); p->S = 0; return -3; }
+  if (best < 1) { p->lds = conv_stream_lds(cin, cout, H, W, ks, 1, KS, p); p->S = 0; return -3; }
   const int S = best < cap ? best : cap;
-  p->lds = conv_stream_lds(cin, cout, H, W, S, KS, p);
+  p->lds = conv_stream_lds(cin, cout, H, W, ks, S, KS, p);
   p->S = S;
   p->nslab = (p->kp + KS - 1) / KS;
   const int wpc = 8 / ((p->coutp + 31) / 32), per = ((S * H * W + 15) / 16 + wpc - 1) / wpc;
@@ -309,26 +323,30 @@ int conv_stream_plan(int64_t B, int cin, int cout, int H, int W, int cus, ConvSP
   return 0;
 }
 
-template <int NR, bool CTX>
-static int conv_stream_launch(const ConvSArgs& a, const ConvSPlan& pl, hipStream_t stream) {
+template <int NR, bool CTX, int KSZ>
+static int conv_stream_launch(const ConvSArgs& a5, int pad_before, const ConvSPlan& pl, hipStream_t stream) {
+  typename ConvSArgsOf<KSZ>::type a;
+  static_cast<ConvSArgs&>(a) = a5;
+  if constexpr (KSZ == 4) a.pb = pad_before;
   static bool attr_done[USF_MAX_DEVICES] = {false};
   bool& done = attr_done[current_device_slot()];
   if (!done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_same_k5_stream_kernel<NR, CTX>),
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_same_stream_kernel<NR, CTX, KSZ>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
       set_error("usf_conv2d_same_f32: cannot raise the LDS limit");
       return -4;
     }
     done = true;
   }
-  hipLaunchKernelGGL((conv2d_same_k5_stream_kernel<NR, CTX>), dim3(pl.grid), dim3(512), (size_t)pl.lds, stream, a);
+  hipLaunchKernelGGL((conv2d_same_stream_kernel<NR, CTX, KSZ>), dim3(pl.grid), dim3(512), (size_t)pl.lds, stream, a);
   return check_launch(CTX ? "usf_conv2d_same_ctx_f32" : "usf_conv2d_same_f32");
 }
 
 // arguments as conv2d_same has checked them (usf_conv.hip); pl from conv_stream_plan for the same sizes
 int conv2d_same_stream(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, const void* wplanes,
                        const float* bias, const float* in_mul, int32_t in_act, float in_slope, int32_t out_act, float out_slope,
-                       const float* ctx, int64_t ctx_stride, const float* w_ctx, const ConvSPlan& pl, hipStream_t stream) {
+                       const float* ctx, int64_t ctx_stride, const float* w_ctx, const ConvSPlan& pl, hipStream_t stream, int ks,
+                       int pad_before) {
   ConvSArgs a;
   a.x = x; a.y = y; a.wp = reinterpret_cast<const __bf16*>(wplanes); a.bias = bias; a.in_mul = in_mul;
   a.B = (int)B; a.cin = (int)cin; a.cout = (int)cout; a.H = (int)H; a.W = (int)W;
@@ -336,15 +354,23 @@ int conv2d_same_stream(const float* x, float* y, int64_t B, int64_t cin, int64_t
   a.mcp = (1u << 20) / (unsigned)pl.cp + 1u;
   a.in_act = in_act; a.out_act = out_act; a.in_slope = in_slope; a.out_slope = out_slope;
   a.ctx = ctx; a.ctx_stride = (int)ctx_stride; a.w_ctx = w_ctx;
-  if (pl.S < 1 || pl.coutp > 64 || pl.KS > 64 || pl.lds > 158 * 1024) { set_error("usf_conv2d_same_f32: bad streamed plan"); return -4; }
-  if (ctx) {
-    if (pl.NR == 1) return conv_stream_launch<1, true>(a, pl, stream);
-    if (pl.NR == 2) return conv_stream_launch<2, true>(a, pl, stream);
-    return conv_stream_launch<4, true>(a, pl, stream);
+  if ((ks != 4 && ks != 5) || pad_before < 1 || pad_before > 2 || (ks == 5 && pad_before != 2) || pl.kp != (ks * ks * pl.cp + 31) / 32 * 32) {
+    set_error("usf_conv2d_same_f32: bad streamed call");
+    return -4;
   }
-  if (pl.NR == 1) return conv_stream_launch<1, false>(a, pl, stream);
-  if (pl.NR == 2) return conv_stream_launch<2, false>(a, pl, stream);
-  return conv_stream_launch<4, false>(a, pl, stream);
+  if (pl.S < 1 || pl.coutp > 64 || pl.KS > 64 || pl.lds > 158 * 1024) { set_error("usf_conv2d_same_f32: bad streamed plan"); return -4; }
+#define USF_CS_LAUNCH(KSZ_)                                                              \
+  if (ctx) {                                                                             \
+    if (pl.NR == 1) return conv_stream_launch<1, true, KSZ_>(a, pad_before, pl, stream);             \
+    if (pl.NR == 2) return conv_stream_launch<2, true, KSZ_>(a, pad_before, pl, stream);             \
+    return conv_stream_launch<4, true, KSZ_>(a, pad_before, pl, stream);                             \
+  }                                                                                      \
+  if (pl.NR == 1) return conv_stream_launch<1, false, KSZ_>(a, pad_before, pl, stream);              \
+  if (pl.NR == 2) return conv_stream_launch<2, false, KSZ_>(a, pad_before, pl, stream);              \
+  return conv_stream_launch<4, false, KSZ_>(a, pad_before, pl, stream)
+  if (ks == 5) { USF_CS_LAUNCH(5); }
+  USF_CS_LAUNCH(4);
+#undef USF_CS_LAUNCH
 }
 
 }  // namespace usf

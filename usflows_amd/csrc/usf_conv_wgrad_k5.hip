@@ -16,12 +16,15 @@
 // slot past the block's last tile repeats the wave's first tile and is never written).  The accumulators live across the
 // block's samples and leave once, to the partial slot (tap row, block) owns; a fixed-order sum over each tap row's slots
 // follows: same bits on every run, no atomics.
+//
+// usf_conv_wgrad_k4_f32 is the same kernel at KSZ = 4: four tap rows of four taps in torch's "same" placement (tap (ty, tx) reads
+// p + (ty - 1, tx - 1)), 64 -> 64 channels 4 * (4 * 4 + 1) = 68 tiles in tap row 0.  The LDS geometry is the 5 x 5 one: offsets
+// -1 .. +2 stay inside the two zero rows and pad columns that -2 .. +2 needs.
 #include "usf_common.h"
 
 namespace usf {
 namespace {
 
-constexpr int kTapRows = 5, kRowTaps = 5;
 
 struct W5Args {
   const float* x;
@@ -37,8 +40,10 @@ struct W5Args {
 
 __device__ __forceinline__ int w5_div(int e, unsigned magic) { return magic ? (int)__umulhi((unsigned)e, magic) : e; }
 
-template <int NT>
+// KSZ: the kernel size (5 or 4): KSZ tap rows (grid.y) of KSZ taps, the first tap (KSZ - 1) / 2 positions before the pixel
+template <int NT, int KSZ>
 __global__ __launch_bounds__(256) void conv_wgrad_k5_kernel(const W5Args a) {
+  constexpr int kRowTaps = KSZ, kPadB = (KSZ - 1) / 2;
   extern __shared__ __attribute__((aligned(16))) float w5_lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -68,7 +73,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_k5_kernel(const W5Args a) {
         pb[k] = cinp * a.CSx + (lane >> 4);                     // the bias tile: B = ones, D[co][*] = sum dy[co]
       } else {
         const int cit = rem / kRowTaps, t = rem - cit * kRowTaps;
-        pb[k] = cit * 16 * a.CSx + a.q0 + (trow - 2) * a.S + (t - 2) + lb;
+        pb[k] = cit * 16 * a.CSx + a.q0 + (trow - kPadB) * a.S + (t - kPadB) + lb;
       }
     }
   }
@@ -143,9 +148,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_k5_kernel(const W5Args a) {
 // blockIdx.z = tap row.  out[j] = the sum over the row's partial slots [by * per, min((by + 1) * per, nparts)) in a fixed order:
 // four interleaved chains, then ((0 + 1) + 2) + 3 -- the order of usf_conv_wgrad_wide_f32's sum.  mode 0: row `by` of the tap
 // row's scratch.  mode 1: the slot layout above -> dW [cout][cin][25] and db [cout] (the padded channels are dropped).
+template <int KSZ>
 __global__ __launch_bounds__(256) void conv_wgrad_k5_sum_kernel(const float* __restrict__ part, int64_t row_stride, int nparts, int per, int n,
                                                                 float* __restrict__ out, int64_t out_row_stride, float* __restrict__ out2,
                                                                 int mode, int cin, int cout, int CIT, int COT) {
+  constexpr int kTapRows = KSZ, kRowTaps = KSZ;
   __shared__ float red[4][64];
   const int jj = threadIdx.x & 63, g = threadIdx.x >> 6;
   const int j = blockIdx.x * 64 + jj, by = blockIdx.y, trow = blockIdx.z;
@@ -204,9 +211,12 @@ struct W5Plan {
   int CIT, COT, S, q0, nch, CSx, CSy, ntiles, NT, nacc, lds_floats, lds_bytes, blocks, slots, per_cu, cus;
 };
 
+// KSZ: the entry point's kernel size; ks: what the caller asked for (anything else is not served)
+template <int KSZ>
 bool k5_plan(int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks, int cus, int blocks_per_cu, W5Plan& pl) {
+  constexpr int kTapRows = KSZ, kRowTaps = KSZ;
   if (B <= 0 || B > 0x7fffffff || cin <= 0 || cout <= 0 || cin > 64 || cout > 64 || H <= 0 || W <= 0 || H > 256 || W > 256 ||
-      H * W > 256 || ks != 5)
+      H * W > 256 || ks != KSZ)
     return false;
   pl.CIT = (int)(cin + 15) / 16;
   pl.COT = (int)(cout + 15) / 16;
@@ -238,13 +248,17 @@ bool k5_plan(int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t
   return true;
 }
 
+template <int KSZ> constexpr const char* k5_name() { return KSZ == 5 ? "usf_conv_wgrad_k5" : "usf_conv_wgrad_k4"; }
+
 }  // namespace
 
+template <int KSZ>
 int conv_wgrad_k5_variant(const usf_conv_wgrad_query* q, usf_conv_wgrad_wide_info* o) {
-  if (!q || !o) { set_error("usf_conv_wgrad_k5_variant: null pointer"); return -1; }
+  constexpr int kTapRows = KSZ, kRowTaps = KSZ;
+  if (!q || !o) { set_error("%s_variant: null pointer", k5_name<KSZ>()); return -1; }
   *o = usf_conv_wgrad_wide_info();
   W5Plan pl;
-  if (!k5_plan(q->B, q->cin, q->cout, q->H, q->W, q->ks, q->cus, q->blocks_per_cu, pl)) return 0;
+  if (!k5_plan<KSZ>(q->B, q->cin, q->cout, q->H, q->W, q->ks, q->cus, q->blocks_per_cu, pl)) return 0;
   o->served = 1;
   o->CIT = pl.CIT; o->COT = pl.COT; o->T = kRowTaps; o->tiles = pl.ntiles; o->tiles_per_wave = pl.NT; o->wave_groups = 4;
   o->position_parts = kTapRows; o->blocks = pl.blocks; o->lds_bytes = pl.lds_bytes; o->S = pl.S; o->q0 = pl.q0; o->CSx = pl.CSx;
@@ -259,22 +273,26 @@ int conv_wgrad_k5_variant(const usf_conv_wgrad_query* q, usf_conv_wgrad_wide_inf
   return 0;
 }
 
+template <int KSZ>
 int64_t conv_wgrad_k5_workspace(int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks) {
+  constexpr int kTapRows = KSZ;
   W5Plan pl;
-  if (!k5_plan(B, cin, cout, H, W, ks, 0, 0, pl)) return 0;
+  if (!k5_plan<KSZ>(B, cin, cout, H, W, ks, 0, 0, pl)) return 0;
   return (int64_t)kTapRows * ((int64_t)pl.slots + kReduceRows) * pl.nacc;
 }
 
+template <int KSZ>
 int conv_wgrad_k5(const float* x, const float* dy, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
                   const float* in_mul, const float* pre_sub, int32_t in_act, float in_slope, float* dW, float* db, float* workspace,
                   int64_t workspace_floats, hipStream_t stream) {
+  constexpr int kTapRows = KSZ;
   W5Plan pl;
-  if (B <= 0) { set_error("usf_conv_wgrad_k5_f32: %s", B == 0 ? "empty batch" : "bad sizes"); return -2; }
-  if (!k5_plan(B, cin, cout, H, W, ks, 0, 0, pl)) return 1;     // shape not served
-  if (!x || !dy || !dW || !workspace) { set_error("usf_conv_wgrad_k5_f32: null pointer"); return -1; }
-  if (in_act != USF_ACT_NONE && in_act != USF_ACT_LEAKY_RELU) { set_error("usf_conv_wgrad_k5_f32: bad act"); return -2; }
+  if (B <= 0) { set_error("%s_f32: %s", k5_name<KSZ>(), B == 0 ? "empty batch" : "bad sizes"); return -2; }
+  if (!k5_plan<KSZ>(B, cin, cout, H, W, ks, 0, 0, pl)) return 1;     // shape not served
+  if (!x || !dy || !dW || !workspace) { set_error("%s_f32: null pointer", k5_name<KSZ>()); return -1; }
+  if (in_act != USF_ACT_NONE && in_act != USF_ACT_LEAKY_RELU) { set_error("%s_f32: bad act", k5_name<KSZ>()); return -2; }
   if (workspace_floats < (int64_t)kTapRows * ((int64_t)pl.slots + kReduceRows) * pl.nacc) {
-    set_error("usf_conv_wgrad_k5_f32: workspace too small");
+    set_error("%s_f32: workspace too small", k5_name<KSZ>());
     return -2;
   }
   W5Args a;
@@ -284,28 +302,28 @@ int conv_wgrad_k5(const float* x, const float* dy, int64_t B, int64_t cin, int64
   a.CIT = pl.CIT; a.COT = pl.COT; a.lds_floats = pl.lds_floats;
   a.m_hw = k5_magic(a.HW); a.m_w = k5_magic(a.W);
   a.slope_eff = (in_act == USF_ACT_LEAKY_RELU) ? in_slope : 1.f;
-  static bool attr_done[USF_MAX_DEVICES][22];
+  static bool attr_done[USF_MAX_DEVICES][22];                  // (one table per KSZ: this function is a template)
   const int dev = current_device_slot();
   bool launched = false;
 #define USF_W5(NT_)                                                                                                          \
   if (pl.NT == NT_) {                                                                                                        \
-    const void* fn = reinterpret_cast<const void*>(&conv_wgrad_k5_kernel<NT_>);                                              \
+    const void* fn = reinterpret_cast<const void*>(&conv_wgrad_k5_kernel<NT_, KSZ>);                                         \
     if (!attr_done[dev][NT_]) {                                                                                              \
       if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax) != hipSuccess) {                      \
         (void)hipGetLastError();                                                                                             \
-        set_error("usf_conv_wgrad_k5_f32: cannot raise the kernel's LDS limit");                                            \
+        set_error("%s_f32: cannot raise the kernel's LDS limit", k5_name<KSZ>());                                           \
         return -3;                                                                                                           \
       }                                                                                                                      \
       attr_done[dev][NT_] = true;                                                                                            \
     }                                                                                                                        \
-    hipLaunchKernelGGL((conv_wgrad_k5_kernel<NT_>), dim3((unsigned)pl.blocks, (unsigned)kTapRows), dim3(256), (size_t)pl.lds_bytes, \
+    hipLaunchKernelGGL((conv_wgrad_k5_kernel<NT_, KSZ>), dim3((unsigned)pl.blocks, (unsigned)kTapRows), dim3(256), (size_t)pl.lds_bytes, \
                        stream, a);                                                                                           \
     launched = true;                                                                                                         \
   }
   USF_W5_INSTANCES(USF_W5)
 #undef USF_W5
-  if (!launched) { set_error("usf_conv_wgrad_k5_f32: no kernel instance for %d tiles per wave", pl.NT); return -3; }
-  int rc = check_launch("usf_conv_wgrad_k5_f32");
+  if (!launched) { set_error("%s_f32: no kernel instance for %d tiles per wave", k5_name<KSZ>(), pl.NT); return -3; }
+  int rc = check_launch(KSZ == 5 ? "usf_conv_wgrad_k5_f32" : "usf_conv_wgrad_k4_f32");
   if (rc) return rc;
   const unsigned gx = (unsigned)((pl.nacc + 63) / 64);
   const float* src = workspace;
@@ -313,15 +331,15 @@ int conv_wgrad_k5(const float* x, const float* dy, int64_t B, int64_t cin, int64
   int nparts = pl.slots, per, used;
   if (k5_rounds(nparts, per, used) == 2) {
     float* scratch = workspace + (int64_t)kTapRows * pl.slots * pl.nacc;
-    hipLaunchKernelGGL(conv_wgrad_k5_sum_kernel, dim3(gx, (unsigned)used, (unsigned)kTapRows), dim3(256), 0, stream, src, src_stride, nparts,
+    hipLaunchKernelGGL(conv_wgrad_k5_sum_kernel<KSZ>, dim3(gx, (unsigned)used, (unsigned)kTapRows), dim3(256), 0, stream, src, src_stride, nparts,
                        per, pl.nacc, scratch, (int64_t)kReduceRows * pl.nacc, (float*)nullptr, 0, 0, 0, pl.CIT, pl.COT);
     src = scratch;
     src_stride = (int64_t)kReduceRows * pl.nacc;
     nparts = used;
   }
-  hipLaunchKernelGGL(conv_wgrad_k5_sum_kernel, dim3(gx, 1u, (unsigned)kTapRows), dim3(256), 0, stream, src, src_stride, nparts, nparts,
+  hipLaunchKernelGGL(conv_wgrad_k5_sum_kernel<KSZ>, dim3(gx, 1u, (unsigned)kTapRows), dim3(256), 0, stream, src, src_stride, nparts, nparts,
                      pl.nacc, dW, (int64_t)0, db, 1, (int)cin, (int)cout, pl.CIT, pl.COT);
-  return check_launch("usf_conv_wgrad_k5_f32 (sum)");
+  return check_launch(KSZ == 5 ? "usf_conv_wgrad_k5_f32 (sum)" : "usf_conv_wgrad_k4_f32 (sum)");
 }
 
 // the instantiations the kernel file has (tiles per wave), for usf_conv_wgrad_k5_variant's coverage test
@@ -341,14 +359,25 @@ int conv_wgrad_k5_instances(int32_t* out, int32_t cap) {
 
 extern "C" {
 int64_t usf_conv_wgrad_k5_workspace(int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks) {
-  return usf::conv_wgrad_k5_workspace(B, cin, cout, H, W, ks);
+  return usf::conv_wgrad_k5_workspace<5>(B, cin, cout, H, W, ks);
 }
 int usf_conv_wgrad_k5_f32(const float* x, const float* dy, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
                           const float* in_mul, const float* pre_sub, int32_t in_act, float in_slope, float* dW, float* db,
                           float* workspace, int64_t workspace_floats, usf_stream_t stream) {
-  return usf::conv_wgrad_k5(x, dy, B, cin, cout, H, W, ks, in_mul, pre_sub, in_act, in_slope, dW, db, workspace, workspace_floats,
-                            (hipStream_t)stream);
+  return usf::conv_wgrad_k5<5>(x, dy, B, cin, cout, H, W, ks, in_mul, pre_sub, in_act, in_slope, dW, db, workspace, workspace_floats,
+                               (hipStream_t)stream);
 }
-int usf_conv_wgrad_k5_variant(const usf_conv_wgrad_query* q, usf_conv_wgrad_wide_info* out) { return usf::conv_wgrad_k5_variant(q, out); }
+int usf_conv_wgrad_k5_variant(const usf_conv_wgrad_query* q, usf_conv_wgrad_wide_info* out) { return usf::conv_wgrad_k5_variant<5>(q, out); }
 int usf_conv_wgrad_k5_instances(int32_t* out, int32_t cap) { return usf::conv_wgrad_k5_instances(out, cap); }
+int64_t usf_conv_wgrad_k4_workspace(int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks) {
+  return usf::conv_wgrad_k5_workspace<4>(B, cin, cout, H, W, ks);
+}
+int usf_conv_wgrad_k4_f32(const float* x, const float* dy, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
+                          const float* in_mul, const float* pre_sub, int32_t in_act, float in_slope, float* dW, float* db,
+                          float* workspace, int64_t workspace_floats, usf_stream_t stream) {
+  return usf::conv_wgrad_k5<4>(x, dy, B, cin, cout, H, W, ks, in_mul, pre_sub, in_act, in_slope, dW, db, workspace, workspace_floats,
+                               (hipStream_t)stream);
+}
+int usf_conv_wgrad_k4_variant(const usf_conv_wgrad_query* q, usf_conv_wgrad_wide_info* out) { return usf::conv_wgrad_k5_variant<4>(q, out); }
+int usf_conv_wgrad_k4_instances(int32_t* out, int32_t cap) { return usf::conv_wgrad_k5_instances(out, cap); }
 }

@@ -993,7 +993,7 @@ __global__ __launch_bounds__(256) void conv_weight_planes_pair_kernel(const floa
 }
 
 int conv2d_weight_planes(const float* w, void* planes, int64_t cin, int64_t cout, int64_t ks, int32_t transposed, hipStream_t stream) {
-  if (cin <= 0 || cout <= 0 || cin > 4096 || cout > 4096 || (ks != 1 && ks != 3 && ks != 5)) { set_error("usf_conv2d_weight_planes_f32: bad sizes"); return -2; }
+  if (cin <= 0 || cout <= 0 || cin > 4096 || cout > 4096 || (ks != 1 && ks != 3 && ks != 4 && ks != 5)) { set_error("usf_conv2d_weight_planes_f32: bad sizes"); return -2; }
   if (!w || !planes) { set_error("usf_conv2d_weight_planes_f32: null pointer"); return -1; }
   if (transposed < 0 || transposed > 2) { set_error("usf_conv2d_weight_planes_f32: transposed must be 0, 1 or 2 (both)"); return -2; }
   // rows / cols of the packed matrix: the convolution the planes are FOR maps `cols` channels to `rows` channels
@@ -1078,7 +1078,7 @@ int gated_residual_bwd(const float* dy, const float* vg, float* dvg, int64_t B, 
 //   dWc[co, t] = sum_b ctx[b] * sum over p with tap t of p inside the image of dy[b, co, p]
 // One block per output channel reads its dy plane once (HBM-bound); a thread walks a fixed set of (b, p) elements, the nine tap
 // sums are reduced over the wave by a fixed butterfly and over the block's waves in index order: the same bits on every run.
-// TAPS: 9 serves kernel 1 and 3, 25 kernel 5.
+// TAPS: 9 serves kernel 1 and 3, 25 kernel 5, 16 kernel 4 (torch's "same" placement: ctx_tapmask4).
 template <int TAPS>
 __global__ __launch_bounds__(256) void conv_ctx_wgrad_kernel(const float* __restrict__ dy, const float* __restrict__ ctx, int ctx_stride,
                                                              int B, int cout, int H, int W, int ks, float* __restrict__ dwc) {
@@ -1091,7 +1091,8 @@ __global__ __launch_bounds__(256) void conv_ctx_wgrad_kernel(const float* __rest
   for (int64_t e = tid; e < n; e += 256) {
     const int b = (int)(e / HW), p = (int)(e - (int64_t)b * HW);
     const int py = p / W;
-    const unsigned m = TAPS == 25 ? ctx_tapmask5(py, p - py * W, H, W) : ctx_tapmask(py, p - py * W, H, W, ks);
+    const unsigned m = TAPS == 16 ? ctx_tapmask4(py, p - py * W, H, W)
+                                  : TAPS == 25 ? ctx_tapmask5(py, p - py * W, H, W) : ctx_tapmask(py, p - py * W, H, W, ks);
     const float v = ctx[(size_t)b * ctx_stride] * dy[((size_t)b * cout + co) * HW + p];
 #pragma unroll
     for (int t = 0; t < TAPS; ++t) acc[t] += ((m >> t) & 1u) ? v : 0.f;
@@ -1108,13 +1109,16 @@ __global__ __launch_bounds__(256) void conv_ctx_wgrad_kernel(const float* __rest
 
 int conv_ctx_wgrad(const float* dy, const float* ctx, int64_t ctx_stride, int64_t B, int64_t cout, int64_t H, int64_t W, int64_t ks,
                    float* dw_ctx, hipStream_t stream) {
-  if (B < 0 || cout <= 0 || H <= 0 || W <= 0 || (ks != 1 && ks != 3 && ks != 5) || (ctx_stride != 0 && ctx_stride != 1) || B * H * W > 0x7fffffffLL) {
-    set_error("usf_conv_ctx_wgrad_f32: bad sizes (kernel 1, 3 or 5, ctx_stride 0 or 1)");
+  if (B < 0 || cout <= 0 || H <= 0 || W <= 0 || (ks != 1 && ks != 3 && ks != 4 && ks != 5) || (ctx_stride != 0 && ctx_stride != 1) || B * H * W > 0x7fffffffLL) {
+    set_error("usf_conv_ctx_wgrad_f32: bad sizes (kernel 1, 3, 4 or 5, ctx_stride 0 or 1)");
     return -2;
   }
   if (!dw_ctx) { set_error("usf_conv_ctx_wgrad_f32: null pointer"); return -1; }
   if (B > 0 && (!dy || !ctx)) { set_error("usf_conv_ctx_wgrad_f32: null pointer"); return -1; }
-  if (ks == 5)
+  if (ks == 4)
+    hipLaunchKernelGGL(conv_ctx_wgrad_kernel<16>, dim3((unsigned)cout), dim3(256), 0, stream, dy, ctx, (int)ctx_stride, (int)B, (int)cout,
+                       (int)H, (int)W, (int)ks, dw_ctx);
+  else if (ks == 5)
     hipLaunchKernelGGL(conv_ctx_wgrad_kernel<25>, dim3((unsigned)cout), dim3(256), 0, stream, dy, ctx, (int)ctx_stride, (int)B, (int)cout,
                        (int)H, (int)W, (int)ks, dw_ctx);
   else

@@ -54,16 +54,44 @@ def _narrow_wgrad_served(B: int, cin: int, cout: int, H: int, W: int, ks: int, m
 
 
 def _small_map_wide_served(B: int, cin: int, cout: int, H: int, W: int, ks: int) -> bool:
-    """under the knob ``conv_k5`` only: a kernel-1 / 3 weight gradient that usf_conv_wgrad_f32 refuses at up to 64 pixels (channel
+    """under the knobs ``conv_k5`` / ``conv_k4`` (either) only: a kernel-1 / 3 weight gradient that usf_conv_wgrad_f32 refuses at up to 64 pixels (channel
     counts that are no multiple of 16: the 8 hidden channels of the hyper-parameter search) goes to usf_conv_wgrad_wide_f32, which
     serves small maps at any channel counts with the same sums in another order.  Knob off: refused there, as ever"""
-    return (config.conv_k5 and config.wgrad_wide
+    return ((config.conv_k5 or config.conv_k4) and config.wgrad_wide
             and _ext.load().usf_conv_wgrad_wide_workspace(max(B, 1), cin, cout, H, W, ks) > 0)
 
 
 def train_kernel_sizes() -> tuple:
-    """kernel sizes of the convolutions the device training path takes: 1 and 3, and 5 under the knob ``conv_k5``"""
-    return (1, 3, 5) if config.conv_k5 else (1, 3)
+    """kernel sizes of the convolutions the device training path takes: 1 and 3, 4 under the knob ``conv_k4`` and 5 under the
+    knob ``conv_k5`` (kernel 4 only with padding="same": torch's placement, one zero before and two after)"""
+    return (1, 3) + ((4,) if config.conv_k4 else ()) + ((5,) if config.conv_k5 else ())
+
+
+def _same_padding(conv) -> bool:
+    """the convolution's padding is the "same" placement the kernels compute: the string, or k // 2 on both sides at an odd
+    kernel (at kernel 4 the integer padding (2, 2) yields H + 1 outputs: not "same")"""
+    k, pad = conv.kernel_size[0], conv.padding
+    return pad == "same" or (k % 2 == 1 and not isinstance(pad, str) and tuple(pad) == (k // 2, k // 2))
+
+
+def k4_wgrad_served(B: int, cin: int, cout: int, H: int, W: int) -> bool:
+    """does usf_conv_wgrad_k4_f32 serve this 4 x 4 call (one kernel for both forms, every pixel count up to 256)?"""
+    return config.conv_k4 and _ext.load().usf_conv_wgrad_k4_workspace(max(B, 1), cin, cout, H, W, 4) > 0
+
+
+def _dgrad_fits(cin: int, cout: int, H: int, W: int, ks: int) -> int:
+    """samples per group of the DATA-gradient convolution (cout -> cin channels): at an even kernel the mirrored placement's
+    plan (usf_conv2d_same_pad_fits; the same LDS footprint, so the same answer as the forward placement's)"""
+    lib = _ext.load()
+    return lib.usf_conv2d_same_pad_fits(cout, cin, H, W, ks, ks // 2) if ks % 2 == 0 else lib.usf_conv2d_same_fits(cout, cin, H, W, ks)
+
+
+def data_grad(dy, planes_t, cin: int, ks: int):
+    """the data gradient of a "same" convolution from the flipped, transposed weight planes: ``_ext.conv2d_same`` at an odd
+    kernel; at an even one the mirrored placement (``_ext.conv2d_same_pad``: two zeros before, one after at kernel 4)"""
+    if ks % 2 == 0:
+        return _ext.conv2d_same_pad(dy, planes_t, cin, ks, ks // 2)
+    return _ext.conv2d_same(dy, planes_t, cin, ks)
 
 
 def k5_wgrad_served(B: int, cin: int, cout: int, H: int, W: int) -> bool:
@@ -75,9 +103,11 @@ def wgrad_served(B: int, cin: int, cout: int, H: int, W: int, ks: int, masked: b
     """does a weight-gradient kernel serve this call -- with an input mask (in_mul) or without?  Up to 64 pixels
     usf_conv_wgrad_f32, whose two forms differ: 64 -> 64 channels at kernel 1 and 57 .. 64 pixels run without a mask only
     (usf_conv_wgrad_workspace > 0 says that ONE form is served); above, usf_conv_wgrad_wide_f32 (one kernel for both forms);
-    kernel 5: usf_conv_wgrad_k5_f32 at every pixel count"""
+    kernel 5: usf_conv_wgrad_k5_f32 at every pixel count; kernel 4: usf_conv_wgrad_k4_f32 likewise"""
     if ks == 5:
         return k5_wgrad_served(B, cin, cout, H, W)
+    if ks == 4:
+        return k4_wgrad_served(B, cin, cout, H, W)
     if H * W >= WIDE_MIN_PIXELS:
         return wide_wgrad_served(B, cin, cout, H, W, ks)
     return _narrow_wgrad_served(B, cin, cout, H, W, ks, masked) or _small_map_wide_served(B, cin, cout, H, W, ks)
@@ -93,13 +123,16 @@ def _wgrad_workspace_ok(B: int, cin: int, cout: int, H: int, W: int) -> bool:
 def conv_wgrad(x, dy, ks, in_mul=None, pre_sub=None, in_act=_ext.ACT_NONE, in_slope=0.0, want_bias=True, defer=False, owners=()):
     """(dW, db | None) of a convolution's backward, or None: ``_ext.conv_wgrad`` as ever; where it declines a feature map of
     more than 64 pixels, ``_ext.conv_wgrad_wide`` (never deferred: its sums run in stream order); kernel 5:
-    ``_ext.conv_wgrad_k5`` (never deferred either)"""
+    ``_ext.conv_wgrad_k5``, kernel 4: ``_ext.conv_wgrad_k4`` (never deferred either)"""
+    if ks == 4:
+        return _ext.conv_wgrad_k4(x, dy, in_mul=in_mul, pre_sub=pre_sub, in_act=in_act, in_slope=in_slope, want_bias=want_bias) \
+            if config.conv_k4 else None
     if ks == 5:
         return _ext.conv_wgrad_k5(x, dy, in_mul=in_mul, pre_sub=pre_sub, in_act=in_act, in_slope=in_slope, want_bias=want_bias) \
             if config.conv_k5 else None
     r = _ext.conv_wgrad(x, dy, ks, in_mul=in_mul, pre_sub=pre_sub, in_act=in_act, in_slope=in_slope, want_bias=want_bias,
                         defer=defer, owners=owners)
-    if r is None and config.wgrad_wide and (x.shape[2] * x.shape[3] >= WIDE_MIN_PIXELS or config.conv_k5):
+    if r is None and config.wgrad_wide and (x.shape[2] * x.shape[3] >= WIDE_MIN_PIXELS or config.conv_k5 or config.conv_k4):
         r = _ext.conv_wgrad_wide(x, dy, ks, in_mul=in_mul, pre_sub=pre_sub, in_act=in_act, in_slope=in_slope, want_bias=want_bias)
     return r
 
@@ -113,12 +146,11 @@ def conv_shape_ok(conv, B: int, H: int, W: int, masked: bool = False) -> bool:
     if k[0] != k[1] or k[0] not in train_kernel_sizes() or conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 \
             or conv.padding_mode != "zeros":
         return False
-    pad = conv.padding
-    if not (pad == "same" or (not isinstance(pad, str) and tuple(pad) == (k[0] // 2, k[0] // 2))):
+    if not _same_padding(conv):
         return False
     lib = _ext.load()
     cin, cout = conv.in_channels, conv.out_channels
-    return (lib.usf_conv2d_same_fits(cin, cout, H, W, k[0]) >= 2 and lib.usf_conv2d_same_fits(cout, cin, H, W, k[0]) >= 2
+    return (lib.usf_conv2d_same_fits(cin, cout, H, W, k[0]) >= 2 and _dgrad_fits(cin, cout, H, W, k[0]) >= 2
             and wgrad_served(B, cin, cout, H, W, k[0], masked))
 
 
@@ -148,7 +180,7 @@ _WSTATE = _WPlanesState()
 
 class batched_weight_planes:
     """context manager around one training pass of an image-shaped flow at a launch-bound batch: the bf16x3 plane pairs of ALL
-    3 x 3 (and, under ``conv_k5``, 5 x 5) convolution weights under ``layers`` from one launch (``_ext.WeightPlanesBatch``; the job table is kept on ``owner``
+    3 x 3 (and, under ``conv_k5`` / ``conv_k4``, 5 x 5 / 4 x 4) convolution weights under ``layers`` from one launch (``_ext.WeightPlanesBatch``; the job table is kept on ``owner``
     while the weights keep their addresses) instead of one per convolution and pass"""
 
     def __init__(self, owner, layers, device):
@@ -157,7 +189,7 @@ class batched_weight_planes:
     def __enter__(self):
         self.prev = _WSTATE.planes
         ws, srcs = [], []
-        sizes = ((3, 3), (5, 5)) if config.conv_k5 else ((3, 3),)
+        sizes = ((3, 3),) + (((4, 4),) if config.conv_k4 else ()) + (((5, 5),) if config.conv_k5 else ())
         for l in self.layers:
             for m in l.modules():
                 if isinstance(m, torch.nn.Conv2d) and m.kernel_size in sizes and m.weight.device == self.device \
@@ -254,7 +286,7 @@ class ConvSame(torch.autograd.Function):
                 # the input's (Leaky)ReLU and mask factors in the data-gradient convolution's output stream
                 dx = _ext.conv2d_same_gate(dy, planes_t, w.shape[1], ks, x, ia[1] if in_act is not None else 1.0, in_mul)
             if dx is None:
-                dx = _ext.conv2d_same(dy, planes_t, w.shape[1], ks)
+                dx = data_grad(dy, planes_t, w.shape[1], ks)
                 _gate_inplace(dx, x, in_act)
                 if in_mul is not None:
                     dx = _ext.masked_residual(None, dx, in_mul, 1.0)
@@ -302,7 +334,7 @@ class ConvSameRes(torch.autograd.Function):
             dW, db = r
         if ctx.needs_input_grad[0]:
             planes_t = ctx.planes_t if ctx.planes_t is not None else _ext.conv2d_weight_planes(w, transposed=True)
-            dx = _ext.conv2d_same(dt, planes_t, w.shape[1], ks)
+            dx = data_grad(dt, planes_t, w.shape[1], ks)
         return dx, dW, db, dy, None, None
 
 
@@ -352,7 +384,7 @@ class ConvSameFork(torch.autograd.Function):
                 if in_act is not None or in_mul is not None:
                     dx = _ext.conv2d_same_gate(dy, planes_t, w.shape[1], ks, x, ia[1] if in_act is not None else 1.0, in_mul)
                 if dx is None:
-                    dx = _ext.conv2d_same(dy, planes_t, w.shape[1], ks)
+                    dx = data_grad(dy, planes_t, w.shape[1], ks)
                     _gate_inplace(dx, x, in_act)
                     if in_mul is not None:
                         dx = _ext.masked_residual(None, dx, in_mul, 1.0)
@@ -405,7 +437,7 @@ class ConvSameCtxFork(torch.autograd.Function):
             if dxs is not None and in_mul is not None:
                 dx = _ext.conv2d_same_res(dy, planes_t, C, ks, dxs, in_mul, 1.0)
             if dx is None:
-                dx = _ext.conv2d_same(dy, planes_t, C, ks)
+                dx = data_grad(dy, planes_t, C, ks)
                 if in_mul is not None:
                     dx = _ext.masked_residual(None, dx, in_mul, 1.0)
                 if dxs is not None:
@@ -422,14 +454,13 @@ def conv_ctx_shape_ok(conv, B: int, H: int, W: int) -> bool:
     if k[0] != k[1] or k[0] not in train_kernel_sizes() or conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 \
             or conv.padding_mode != "zeros":
         return False
-    pad = conv.padding
-    if not (pad == "same" or (not isinstance(pad, str) and tuple(pad) == (k[0] // 2, k[0] // 2))):
+    if not _same_padding(conv):
         return False
     lib = _ext.load()
     C, cout = conv.in_channels - 1, conv.out_channels
-    return (lib.usf_conv2d_same_fits(C, cout, H, W, k[0]) >= 2 and lib.usf_conv2d_same_fits(cout, C, H, W, k[0]) >= 2
-            and (_narrow_wgrad_served(B, C, cout, H, W, k[0], True) if k[0] != 5 else
-                 (H * W < WIDE_MIN_PIXELS and k5_wgrad_served(B, C, cout, H, W))))    # (the first convolution: it may be handed the coupling's mask;
+    return (lib.usf_conv2d_same_fits(C, cout, H, W, k[0]) >= 2 and _dgrad_fits(C, cout, H, W, k[0]) >= 2
+            and (_narrow_wgrad_served(B, C, cout, H, W, k[0], True) if k[0] not in (4, 5) else
+                 (H * W < WIDE_MIN_PIXELS and wgrad_served(B, C, cout, H, W, k[0], True))))    # (the first convolution: it may be handed the coupling's mask;
                                                                        # above 64 pixels conditional conditioners stay declined)
 
 
@@ -481,10 +512,10 @@ def pointwise_shape_ok(conv, B: int, H: int, W: int) -> bool:
 
 
 def gate_halves_ok(conv, B: int, H: int, W: int) -> bool:
-    """under the knob ``conv_k5`` only: GatedConv's 1 x 1 convolution C -> 2 C with more than the kernels' 64 output channels
+    """under the knobs ``conv_k5`` / ``conv_k4`` (either) only: GatedConv's 1 x 1 convolution C -> 2 C with more than the kernels' 64 output channels
     (C = 33 .. 64: the 64 hidden channels of the hyper-parameter search) runs as TWO convolutions C -> C, the value rows and the
     gate rows of its weight (``gate_halves``), each with a device forward, data gradient and weight gradient"""
-    if not (config.conv_k5 and isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
+    if not ((config.conv_k5 or config.conv_k4) and isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
             and conv.groups == 1 and conv.out_channels == 2 * conv.in_channels and 64 < conv.out_channels <= 128):
         return False
     pad = conv.padding

@@ -420,8 +420,15 @@ def _relu_kind(m):
 
 
 def _conv_kernel_sizes() -> tuple:
-    """kernel sizes of the "same" convolution's device path: 1 and 3, and 5 under the knob ``conv_k5``"""
-    return (1, 3, 5) if config.conv_k5 else (1, 3)
+    """kernel sizes of the "same" convolution's device path: 1 and 3, 4 under the knob ``conv_k4`` (padding="same" only: torch's
+    placement, one zero before and two after), 5 under the knob ``conv_k5``"""
+    return (1, 3) + ((4,) if config.conv_k4 else ()) + ((5,) if config.conv_k5 else ())
+
+
+def _same_padding(conv) -> bool:
+    """the string "same", or k // 2 on both sides at an odd kernel (at kernel 4 the integer padding (2, 2) is not "same")"""
+    k, pad = conv.kernel_size[0], conv.padding
+    return pad == "same" or (k % 2 == 1 and not isinstance(pad, str) and tuple(pad) == (k // 2, k // 2))
 
 
 def _conv_same_shaped(conv, x) -> bool:
@@ -435,8 +442,7 @@ def _conv_same_shaped(conv, x) -> bool:
     if k[0] != k[1] or k[0] not in _conv_kernel_sizes() or conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 \
             or conv.padding_mode != "zeros" or x.shape[1] != conv.in_channels:
         return False
-    pad = conv.padding
-    return pad == "same" or (not isinstance(pad, str) and tuple(pad) == (k[0] // 2, k[0] // 2))
+    return _same_padding(conv)
 
 
 def _conv_hip_ok(conv, x) -> bool:
@@ -516,8 +522,7 @@ def _conv_ctx_ok(conv, x) -> bool:
     if k[0] != k[1] or k[0] not in _conv_kernel_sizes() or conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 \
             or conv.padding_mode != "zeros":
         return False
-    pad = conv.padding
-    if not (pad == "same" or (not isinstance(pad, str) and tuple(pad) == (k[0] // 2, k[0] // 2))):
+    if not _same_padding(conv):
         return False
     from . import _ext
     return _ext.load().usf_conv2d_same_fits(x.shape[1], conv.out_channels, x.shape[2], x.shape[3], k[0]) >= 2
