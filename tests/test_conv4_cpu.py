@@ -276,7 +276,7 @@ def test_the_knob_gates_training_at_kernel_size_4(monkeypatch):
     monkeypatch.setattr(config, "conv_k5", False)
     monkeypatch.setattr(config, "conv_k4", False)
     assert not it.conv_shape_ok(conv, 32, 7, 7) and not it.conv_ctx_shape_ok(cond, 32, 7, 7) and not it.wgrad_served(32, 16, 32, 7, 7, 4, False)
-    assert not it.gate_halves_ok(torch.nn.Conv2d(64, 128, 1), 32, 7, 7) and not it._small_map_wide_served(32, 8, 8, 7, 7, 1)
+    assert not it.gate_halves_ok(torch.nn.Conv2d(64, 128, 1), 32, 7, 7) and it.wgrad_route(32, 8, 8, 7, 7, 1, False) is None
     monkeypatch.setattr(config, "conv_k5", True)                      # the other knob does not open kernel 4
     assert not it.conv_shape_ok(conv, 32, 7, 7) and not it.wgrad_served(32, 16, 32, 7, 7, 4, False)
     monkeypatch.setattr(config, "conv_k5", False)
@@ -296,7 +296,7 @@ def test_the_knob_gates_training_at_kernel_size_4(monkeypatch):
     assert not it.conv_shape_ok(torch.nn.Conv2d(16, 32, 5, padding="same"), 32, 7, 7)
     assert it.conv_shape_ok(torch.nn.Conv2d(16, 32, 3, padding=1), 32, 7, 7)                  # (odd kernels keep their integer form)
     # the two side routes open under either knob
-    assert it.gate_halves_ok(torch.nn.Conv2d(64, 128, 1), 32, 7, 7) and it._small_map_wide_served(32, 8, 8, 7, 7, 1)
+    assert it.gate_halves_ok(torch.nn.Conv2d(64, 128, 1), 32, 7, 7) and it.wgrad_route(32, 8, 8, 7, 7, 1, False) == "wide"
 
 
 def test_the_inference_rules_take_kernel_4_as_the_string_same_only(monkeypatch):

@@ -344,24 +344,9 @@ INTERNAL_SYMBOLS = {
     "usf_conv_wgrad_variant": (C.c_int, [C.POINTER(ConvWgradQuery), C.POINTER(ConvWgradInfo)]),
     "usf_layernorm_channels_bwd_variant": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(LnBwdInfo)]),
     "usf_conv_wgrad_workspace": (C.c_int64, [C.c_int64] * 6),
-    "usf_conv_wgrad_wide_workspace": (C.c_int64, [C.c_int64] * 6),
-    "usf_conv_wgrad_wide_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [_fp, _fp, C.c_int32, C.c_float, _fp, _fp, _fp, C.c_int64,
-                                          C.c_void_p]),
-    "usf_conv_wgrad_wide_variant": (C.c_int, [C.POINTER(ConvWgradQuery), C.POINTER(ConvWgradWideInfo)]),
-    "usf_conv_wgrad_wide_instances": (C.c_int, [C.POINTER(C.c_int32), C.c_int32]),
-    "usf_conv_wgrad_k5_workspace": (C.c_int64, [C.c_int64] * 6),
-    "usf_conv_wgrad_k5_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [_fp, _fp, C.c_int32, C.c_float, _fp, _fp, _fp, C.c_int64,
-                                        C.c_void_p]),
-    "usf_conv_wgrad_k5_variant": (C.c_int, [C.POINTER(ConvWgradQuery), C.POINTER(ConvWgradWideInfo)]),
-    "usf_conv_wgrad_k5_instances": (C.c_int, [C.POINTER(C.c_int32), C.c_int32]),
     "usf_conv2d_same_pad_fits": (C.c_int, [C.c_int64] * 6),
     "usf_conv2d_same_pad_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 7 + [_fp, _fp, _fp, C.c_int32, C.c_float, C.c_int32, C.c_float, _fp,
                                           C.c_int64, C.c_void_p]),
-    "usf_conv_wgrad_k4_workspace": (C.c_int64, [C.c_int64] * 6),
-    "usf_conv_wgrad_k4_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [_fp, _fp, C.c_int32, C.c_float, _fp, _fp, _fp, C.c_int64,
-                                        C.c_void_p]),
-    "usf_conv_wgrad_k4_variant": (C.c_int, [C.POINTER(ConvWgradQuery), C.POINTER(ConvWgradWideInfo)]),
-    "usf_conv_wgrad_k4_instances": (C.c_int, [C.POINTER(C.c_int32), C.c_int32]),
     "usf_conv_wgrad_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [_fp, _fp, C.c_int32, C.c_float, _fp, _fp, _fp, C.c_int64,
                                      C.c_void_p]),
     "usf_conv_wgrad_deferred_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [_fp, _fp, C.c_int32, C.c_float, _fp, _fp, _fp, C.c_int64,
@@ -421,4 +406,10 @@ INTERNAL_SYMBOLS = {
     "usf_affine_prep_bwd_f32": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_int32,
                                           C.c_int32, _fp, _fp, _fp, _fp, C.c_void_p]),
 }
+for _stem in ("usf_conv_wgrad_wide", "usf_conv_wgrad_k5", "usf_conv_wgrad_k4"):      # the stream-ordered weight-gradient kernels: one block of signatures
+    INTERNAL_SYMBOLS.update({
+        _stem + "_workspace": (C.c_int64, [C.c_int64] * 6),
+        _stem + "_f32": INTERNAL_SYMBOLS["usf_conv_wgrad_f32"],
+        _stem + "_variant": (C.c_int, [C.POINTER(ConvWgradQuery), C.POINTER(ConvWgradWideInfo)]),
+        _stem + "_instances": (C.c_int, [C.POINTER(C.c_int32), C.c_int32])})
 SYMBOLS = {**PUBLIC_SYMBOLS, **INTERNAL_SYMBOLS}

@@ -627,22 +627,54 @@ def conv_wgrad_variant(B, cin, cout, H, W, ks=3, masked=False, cus=0, blocks_per
     return {name: int(getattr(out, name)) for name, _ in ConvWgradInfo._fields_ if name != "reserved"}
 
 
-def conv_wgrad_wide_variant(B, cin, cout, H, W, ks=3, cus=0, blocks_per_cu=0) -> dict:
-    """usf_conv_wgrad_wide_variant: the plan usf_conv_wgrad_wide_f32 launches from for these sizes, as a dict of the answer's
-    fields (served 0: the call returns 1); cus / blocks_per_cu > 0 plan for that device answer (cus > 0: no GPU needed)"""
+def conv_wgrad_kernel(B, cin, cout, H, W, ks, masked) -> int:
+    """conv_wgrad_variant(...)["kernel"] on the device's own answer, without the dict: the training path asks it per layer and pass"""
+    q = ConvWgradQuery(B, cin, cout, H, W, ks, 1 if masked else 0, 0, 0, 0)
+    out = ConvWgradInfo()
+    check(load().usf_conv_wgrad_variant(C.byref(q), C.byref(out)), "usf_conv_wgrad_variant")
+    return out.kernel
+
+
+def _conv_wgrad_direct_variant(stem, B, cin, cout, H, W, ks, cus, blocks_per_cu) -> dict:
+    """<stem>_variant of one of the three stream-ordered weight-gradient kernels (wide, k5, k4: one plan structure): the plan
+    <stem>_f32 launches from for these sizes, as a dict of the answer's fields (served 0: the call returns 1); cus /
+    blocks_per_cu > 0 plan for that device answer (cus > 0: no GPU needed)"""
     q = ConvWgradQuery(int(B), int(cin), int(cout), int(H), int(W), int(ks), 0, int(cus), int(blocks_per_cu), 0)
     out = ConvWgradWideInfo()
-    check(load().usf_conv_wgrad_wide_variant(C.byref(q), C.byref(out)), "usf_conv_wgrad_wide_variant")
+    check(getattr(load(), stem + "_variant")(C.byref(q), C.byref(out)), stem + "_variant")
     return {name: int(getattr(out, name)) for name, _ in ConvWgradWideInfo._fields_ if name != "reserved"}
 
 
-def conv_wgrad_wide_instances() -> list:
-    """usf_conv_wgrad_wide_instances: the tiles-per-wave values usf_conv_wgrad_wide.hip instantiates its kernel for"""
-    lib = load()
-    n = lib.usf_conv_wgrad_wide_instances(None, 0)
-    buf = (C.c_int32 * n)()
-    lib.usf_conv_wgrad_wide_instances(buf, n)
+def _conv_wgrad_direct_instances(stem) -> list:
+    """<stem>_instances: the tiles-per-wave values the kernel file instantiates its kernel for (k4 and k5 share one file)"""
+    fn = getattr(load(), stem + "_instances")
+    buf = (C.c_int32 * fn(None, 0))()
+    fn(buf, len(buf))
     return list(buf)
+
+
+def conv_wgrad_wide_variant(B, cin, cout, H, W, ks=3, cus=0, blocks_per_cu=0) -> dict:
+    return _conv_wgrad_direct_variant("usf_conv_wgrad_wide", B, cin, cout, H, W, ks, cus, blocks_per_cu)
+
+
+def conv_wgrad_k5_variant(B, cin, cout, H, W, ks=5, cus=0, blocks_per_cu=0) -> dict:
+    return _conv_wgrad_direct_variant("usf_conv_wgrad_k5", B, cin, cout, H, W, ks, cus, blocks_per_cu)
+
+
+def conv_wgrad_k4_variant(B, cin, cout, H, W, ks=4, cus=0, blocks_per_cu=0) -> dict:
+    return _conv_wgrad_direct_variant("usf_conv_wgrad_k4", B, cin, cout, H, W, ks, cus, blocks_per_cu)
+
+
+def conv_wgrad_wide_instances() -> list:
+    return _conv_wgrad_direct_instances("usf_conv_wgrad_wide")
+
+
+def conv_wgrad_k5_instances() -> list:
+    return _conv_wgrad_direct_instances("usf_conv_wgrad_k5")
+
+
+def conv_wgrad_k4_instances() -> list:
+    return _conv_wgrad_direct_instances("usf_conv_wgrad_k4")
 
 
 def channel_affine_bwd_variant(B, C_, P, aligned=True, want_bias=True, grid_cap=0) -> dict:
@@ -989,87 +1021,36 @@ def conv_wgrad(x, dy, ks, in_mul=None, pre_sub=None, in_act=ACT_NONE, in_slope=0
     return dW, db
 
 
-def conv_wgrad_wide(x, dy, ks, in_mul=None, pre_sub=None, in_act=ACT_NONE, in_slope=0.0, want_bias=True):
-    """usf_conv_wgrad_wide_f32: conv_wgrad's (dW, db | None) for feature maps of up to 256 pixels and any channel counts up to 64;
-    None when the shape is not served.  Never deferred or queued: its launches follow each other in the current stream with no
-    host synchronisation, so a captured training step replays them"""
+def _conv_wgrad_direct(entry, x, dy, ks, in_mul=None, pre_sub=None, in_act=ACT_NONE, in_slope=0.0, want_bias=True):
+    """conv_wgrad's (dW [cout, cin, ks, ks], db | None) from one of the three stream-ordered kernels, `entry` =
+    usf_conv_wgrad_{wide,k5,k4}_f32; None when the shape is not served.  Never deferred or queued: the launches follow each other
+    in the current stream with no host synchronisation, so a captured training step replays them"""
     B, cin, H, W = x.shape
     cout = dy.shape[1]
-    ws_n = load().usf_conv_wgrad_wide_workspace(B, cin, cout, H, W, ks)
+    ws_n = getattr(load(), entry[:-len("f32")] + "workspace")(B, cin, cout, H, W, ks)
     if ws_n <= 0:
         return None
     ws = torch.empty(ws_n, dtype=torch.float32, device=x.device)
     dW = torch.empty(cout, cin, ks, ks, dtype=torch.float32, device=x.device)
     db = torch.empty(cout, dtype=torch.float32, device=x.device) if want_bias else None
-    rc = _launch("usf_conv_wgrad_wide_f32", (x.data_ptr(), dy.data_ptr(), B, cin, cout, H, W, ks, ptr(in_mul), ptr(pre_sub), int(in_act),
+    rc = _launch(entry, (x.data_ptr(), dy.data_ptr(), B, cin, cout, H, W, ks, ptr(in_mul), ptr(pre_sub), int(in_act),
                  float(in_slope), dW.data_ptr(), ptr(db), ws.data_ptr(), ws_n, current_stream(x.device)), tape=False, unserved_ok=True)
     return None if rc else (dW, db)
 
 
-def conv_wgrad_k5(x, dy, in_mul=None, pre_sub=None, in_act=ACT_NONE, in_slope=0.0, want_bias=True):
-    """usf_conv_wgrad_k5_f32: conv_wgrad's (dW [cout, cin, 5, 5], db | None) of a 5 x 5 "same" convolution; None when the shape is
-    not served.  Never deferred or queued, as conv_wgrad_wide: a captured training step replays its launches"""
-    B, cin, H, W = x.shape
-    cout = dy.shape[1]
-    ws_n = load().usf_conv_wgrad_k5_workspace(B, cin, cout, H, W, 5)
-    if ws_n <= 0:
-        return None
-    ws = torch.empty(ws_n, dtype=torch.float32, device=x.device)
-    dW = torch.empty(cout, cin, 5, 5, dtype=torch.float32, device=x.device)
-    db = torch.empty(cout, dtype=torch.float32, device=x.device) if want_bias else None
-    rc = _launch("usf_conv_wgrad_k5_f32", (x.data_ptr(), dy.data_ptr(), B, cin, cout, H, W, 5, ptr(in_mul), ptr(pre_sub), int(in_act),
-                 float(in_slope), dW.data_ptr(), ptr(db), ws.data_ptr(), ws_n, current_stream(x.device)), tape=False, unserved_ok=True)
-    return None if rc else (dW, db)
+def conv_wgrad_wide(x, dy, ks, **transforms):
+    """usf_conv_wgrad_wide_f32: feature maps of up to 256 pixels and any channel counts up to 64, kernel 1 and 3"""
+    return _conv_wgrad_direct("usf_conv_wgrad_wide_f32", x, dy, ks, **transforms)
 
 
-def conv_wgrad_k4(x, dy, in_mul=None, pre_sub=None, in_act=ACT_NONE, in_slope=0.0, want_bias=True):
-    """usf_conv_wgrad_k4_f32: conv_wgrad's (dW [cout, cin, 4, 4], db | None) of a 4 x 4 "same" convolution in torch's placement
-    (one zero before, two after); None when the shape is not served.  Never deferred or queued, as conv_wgrad_k5"""
-    B, cin, H, W = x.shape
-    cout = dy.shape[1]
-    ws_n = load().usf_conv_wgrad_k4_workspace(B, cin, cout, H, W, 4)
-    if ws_n <= 0:
-        return None
-    ws = torch.empty(ws_n, dtype=torch.float32, device=x.device)
-    dW = torch.empty(cout, cin, 4, 4, dtype=torch.float32, device=x.device)
-    db = torch.empty(cout, dtype=torch.float32, device=x.device) if want_bias else None
-    rc = _launch("usf_conv_wgrad_k4_f32", (x.data_ptr(), dy.data_ptr(), B, cin, cout, H, W, 4, ptr(in_mul), ptr(pre_sub), int(in_act),
-                 float(in_slope), dW.data_ptr(), ptr(db), ws.data_ptr(), ws_n, current_stream(x.device)), tape=False, unserved_ok=True)
-    return None if rc else (dW, db)
+def conv_wgrad_k5(x, dy, **transforms):
+    """usf_conv_wgrad_k5_f32: a 5 x 5 "same" convolution"""
+    return _conv_wgrad_direct("usf_conv_wgrad_k5_f32", x, dy, 5, **transforms)
 
 
-def conv_wgrad_k4_variant(B, cin, cout, H, W, ks=4, cus=0, blocks_per_cu=0) -> dict:
-    """usf_conv_wgrad_k4_variant: the plan usf_conv_wgrad_k4_f32 launches from, as a dict (served 0: the call returns 1)"""
-    q = ConvWgradQuery(int(B), int(cin), int(cout), int(H), int(W), int(ks), 0, int(cus), int(blocks_per_cu), 0)
-    out = ConvWgradWideInfo()
-    check(load().usf_conv_wgrad_k4_variant(C.byref(q), C.byref(out)), "usf_conv_wgrad_k4_variant")
-    return {name: int(getattr(out, name)) for name, _ in ConvWgradWideInfo._fields_ if name != "reserved"}
-
-
-def conv_wgrad_k4_instances() -> list:
-    """usf_conv_wgrad_k4_instances: the tiles-per-wave values the shared kernel file instantiates (usf_conv_wgrad_k5_instances')"""
-    lib = load()
-    n = lib.usf_conv_wgrad_k4_instances(None, 0)
-    buf = (C.c_int32 * n)()
-    lib.usf_conv_wgrad_k4_instances(buf, n)
-    return list(buf)
-
-
-def conv_wgrad_k5_variant(B, cin, cout, H, W, ks=5, cus=0, blocks_per_cu=0) -> dict:
-    """usf_conv_wgrad_k5_variant: the plan usf_conv_wgrad_k5_f32 launches from, as a dict (served 0: the call returns 1)"""
-    q = ConvWgradQuery(int(B), int(cin), int(cout), int(H), int(W), int(ks), 0, int(cus), int(blocks_per_cu), 0)
-    out = ConvWgradWideInfo()
-    check(load().usf_conv_wgrad_k5_variant(C.byref(q), C.byref(out)), "usf_conv_wgrad_k5_variant")
-    return {name: int(getattr(out, name)) for name, _ in ConvWgradWideInfo._fields_ if name != "reserved"}
-
-
-def conv_wgrad_k5_instances() -> list:
-    """usf_conv_wgrad_k5_instances: the tiles-per-wave values usf_conv_wgrad_k5.hip instantiates its kernel for"""
-    lib = load()
-    n = lib.usf_conv_wgrad_k5_instances(None, 0)
-    buf = (C.c_int32 * n)()
-    lib.usf_conv_wgrad_k5_instances(buf, n)
-    return list(buf)
+def conv_wgrad_k4(x, dy, **transforms):
+    """usf_conv_wgrad_k4_f32: a 4 x 4 "same" convolution in torch's placement (one zero before, two after)"""
+    return _conv_wgrad_direct("usf_conv_wgrad_k4_f32", x, dy, 4, **transforms)
 
 
 def layernorm_channels_bwd(x, dy, gamma, eps, act=ACT_NONE, slope=0.0):

@@ -6,8 +6,8 @@ Each ``torch.autograd.Function`` here is one device pass of the inference path w
 
 * data gradients reuse the forward kernels on the transposed (and, for 3 x 3, flipped) weight:
   ``usf_conv2d_same_f32``, ``usf_pointwise_conv_f32``, ``usf_channel_affine_f32``;
-* weight / bias gradients come from ``usf_conv_wgrad_f32`` (exact fp32 on the f32 matrix instruction, deterministic) and, for
-  feature maps of 65 .. 256 pixels, from ``usf_conv_wgrad_wide_f32`` (same contract; knob ``wgrad_wide``);
+* weight / bias gradients come from ``usf_conv_wgrad_f32`` (exact fp32 on the f32 matrix instruction, deterministic) or one of
+  its three siblings of the same contract; which one is stated once, in ``image_rules.wgrad_kernels``;
 * an affine block of up to 12 channels takes its whole backward (dx, dW, db) from ONE launch of
   ``usf_channel_affine_bwd_f32`` (knob ``affine_small_c``);
 * ``usf_layernorm_channels_bwd_f32``, ``usf_gated_residual_bwd_f32``, ``usf_act_grad_f32``, ``usf_masked_residual_f32`` and
@@ -24,6 +24,12 @@ import torch
 
 from . import _ext
 from .config import config
+# which kernel serves which convolution is stated in image_rules.py; the names stay importable from here
+from .image_rules import (WIDE_MIN_PIXELS, conv_ctx_shape_ok, conv_kernel_sizes, conv_shape_ok, conv_wgrad,  # noqa: F401
+                          gate_halves_ok, pointwise_geometry, pointwise_shape_ok, wgrad_kernels, wgrad_route, wgrad_served,
+                          wide_wgrad_served)
+
+train_kernel_sizes = conv_kernel_sizes
 
 
 def _act(a):
@@ -39,119 +45,12 @@ def _gate_inplace(d: torch.Tensor, h: torch.Tensor, act) -> None:
     _ext.act_grad(d, h, M=B, H=n, ldd=n, ldh=n, act=act[0], slope=act[1])
 
 
-WIDE_MIN_PIXELS = 65      # feature maps of 65 .. 256 pixels: usf_conv_wgrad_f32 refuses them, usf_conv_wgrad_wide_f32 serves them
-
-
-def wide_wgrad_served(B: int, cin: int, cout: int, H: int, W: int, ks: int) -> bool:
-    """does usf_conv_wgrad_wide_f32 take over this call?  Only above 64 pixels (below, usf_conv_wgrad_f32 alone decides, as it
-    always did) and only while the knob ``config.wgrad_wide`` is on"""
-    return (config.wgrad_wide and H * W >= WIDE_MIN_PIXELS
-            and _ext.load().usf_conv_wgrad_wide_workspace(max(B, 1), cin, cout, H, W, ks) > 0)
-
-
-def _narrow_wgrad_served(B: int, cin: int, cout: int, H: int, W: int, ks: int, masked: bool) -> bool:
-    return _ext.conv_wgrad_variant(max(B, 1), cin, cout, H, W, ks, masked)["kernel"] != 0
-
-
-def _small_map_wide_served(B: int, cin: int, cout: int, H: int, W: int, ks: int) -> bool:
-    """under the knobs ``conv_k5`` / ``conv_k4`` (either) only: a kernel-1 / 3 weight gradient that usf_conv_wgrad_f32 refuses at up to 64 pixels (channel
-    counts that are no multiple of 16: the 8 hidden channels of the hyper-parameter search) goes to usf_conv_wgrad_wide_f32, which
-    serves small maps at any channel counts with the same sums in another order.  Knob off: refused there, as ever"""
-    return ((config.conv_k5 or config.conv_k4) and config.wgrad_wide
-            and _ext.load().usf_conv_wgrad_wide_workspace(max(B, 1), cin, cout, H, W, ks) > 0)
-
-
-def train_kernel_sizes() -> tuple:
-    """kernel sizes of the convolutions the device training path takes: 1 and 3, 4 under the knob ``conv_k4`` and 5 under the
-    knob ``conv_k5`` (kernel 4 only with padding="same": torch's placement, one zero before and two after)"""
-    return (1, 3) + ((4,) if config.conv_k4 else ()) + ((5,) if config.conv_k5 else ())
-
-
-def _same_padding(conv) -> bool:
-    """the convolution's padding is the "same" placement the kernels compute: the string, or k // 2 on both sides at an odd
-    kernel (at kernel 4 the integer padding (2, 2) yields H + 1 outputs: not "same")"""
-    k, pad = conv.kernel_size[0], conv.padding
-    return pad == "same" or (k % 2 == 1 and not isinstance(pad, str) and tuple(pad) == (k // 2, k // 2))
-
-
-def k4_wgrad_served(B: int, cin: int, cout: int, H: int, W: int) -> bool:
-    """does usf_conv_wgrad_k4_f32 serve this 4 x 4 call (one kernel for both forms, every pixel count up to 256)?"""
-    return config.conv_k4 and _ext.load().usf_conv_wgrad_k4_workspace(max(B, 1), cin, cout, H, W, 4) > 0
-
-
-def _dgrad_fits(cin: int, cout: int, H: int, W: int, ks: int) -> int:
-    """samples per group of the DATA-gradient convolution (cout -> cin channels): at an even kernel the mirrored placement's
-    plan (usf_conv2d_same_pad_fits; the same LDS footprint, so the same answer as the forward placement's)"""
-    lib = _ext.load()
-    return lib.usf_conv2d_same_pad_fits(cout, cin, H, W, ks, ks // 2) if ks % 2 == 0 else lib.usf_conv2d_same_fits(cout, cin, H, W, ks)
-
-
 def data_grad(dy, planes_t, cin: int, ks: int):
     """the data gradient of a "same" convolution from the flipped, transposed weight planes: ``_ext.conv2d_same`` at an odd
     kernel; at an even one the mirrored placement (``_ext.conv2d_same_pad``: two zeros before, one after at kernel 4)"""
     if ks % 2 == 0:
         return _ext.conv2d_same_pad(dy, planes_t, cin, ks, ks // 2)
     return _ext.conv2d_same(dy, planes_t, cin, ks)
-
-
-def k5_wgrad_served(B: int, cin: int, cout: int, H: int, W: int) -> bool:
-    """does usf_conv_wgrad_k5_f32 serve this 5 x 5 call (one kernel for both forms, every pixel count up to 256)?"""
-    return config.conv_k5 and _ext.load().usf_conv_wgrad_k5_workspace(max(B, 1), cin, cout, H, W, 5) > 0
-
-
-def wgrad_served(B: int, cin: int, cout: int, H: int, W: int, ks: int, masked: bool) -> bool:
-    """does a weight-gradient kernel serve this call -- with an input mask (in_mul) or without?  Up to 64 pixels
-    usf_conv_wgrad_f32, whose two forms differ: 64 -> 64 channels at kernel 1 and 57 .. 64 pixels run without a mask only
-    (usf_conv_wgrad_workspace > 0 says that ONE form is served); above, usf_conv_wgrad_wide_f32 (one kernel for both forms);
-    kernel 5: usf_conv_wgrad_k5_f32 at every pixel count; kernel 4: usf_conv_wgrad_k4_f32 likewise"""
-    if ks == 5:
-        return k5_wgrad_served(B, cin, cout, H, W)
-    if ks == 4:
-        return k4_wgrad_served(B, cin, cout, H, W)
-    if H * W >= WIDE_MIN_PIXELS:
-        return wide_wgrad_served(B, cin, cout, H, W, ks)
-    return _narrow_wgrad_served(B, cin, cout, H, W, ks, masked) or _small_map_wide_served(B, cin, cout, H, W, ks)
-
-
-def _wgrad_workspace_ok(B: int, cin: int, cout: int, H: int, W: int) -> bool:
-    """the kernel-1 weight gradient of a pointwise convolution / an affine block is served (either kernel's workspace > 0)"""
-    if H * W >= WIDE_MIN_PIXELS:
-        return wide_wgrad_served(B, cin, cout, H, W, 1)
-    return _ext.load().usf_conv_wgrad_workspace(max(B, 1), cin, cout, H, W, 1) > 0 or _small_map_wide_served(B, cin, cout, H, W, 1)
-
-
-def conv_wgrad(x, dy, ks, in_mul=None, pre_sub=None, in_act=_ext.ACT_NONE, in_slope=0.0, want_bias=True, defer=False, owners=()):
-    """(dW, db | None) of a convolution's backward, or None: ``_ext.conv_wgrad`` as ever; where it declines a feature map of
-    more than 64 pixels, ``_ext.conv_wgrad_wide`` (never deferred: its sums run in stream order); kernel 5:
-    ``_ext.conv_wgrad_k5``, kernel 4: ``_ext.conv_wgrad_k4`` (never deferred either)"""
-    if ks == 4:
-        return _ext.conv_wgrad_k4(x, dy, in_mul=in_mul, pre_sub=pre_sub, in_act=in_act, in_slope=in_slope, want_bias=want_bias) \
-            if config.conv_k4 else None
-    if ks == 5:
-        return _ext.conv_wgrad_k5(x, dy, in_mul=in_mul, pre_sub=pre_sub, in_act=in_act, in_slope=in_slope, want_bias=want_bias) \
-            if config.conv_k5 else None
-    r = _ext.conv_wgrad(x, dy, ks, in_mul=in_mul, pre_sub=pre_sub, in_act=in_act, in_slope=in_slope, want_bias=want_bias,
-                        defer=defer, owners=owners)
-    if r is None and config.wgrad_wide and (x.shape[2] * x.shape[3] >= WIDE_MIN_PIXELS or config.conv_k5 or config.conv_k4):
-        r = _ext.conv_wgrad_wide(x, dy, ks, in_mul=in_mul, pre_sub=pre_sub, in_act=in_act, in_slope=in_slope, want_bias=want_bias)
-    return r
-
-
-def conv_shape_ok(conv, B: int, H: int, W: int, masked: bool = False) -> bool:
-    """forward, data gradient (the transposed shape) and weight gradient of this nn.Conv2d at [B, cin, H, W] are all served;
-    masked: the layer may be handed an input mask (the first convolution of a coupling's conditioner)"""
-    if not isinstance(conv, torch.nn.Conv2d):
-        return False
-    k = conv.kernel_size
-    if k[0] != k[1] or k[0] not in train_kernel_sizes() or conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 \
-            or conv.padding_mode != "zeros":
-        return False
-    if not _same_padding(conv):
-        return False
-    lib = _ext.load()
-    cin, cout = conv.in_channels, conv.out_channels
-    return (lib.usf_conv2d_same_fits(cin, cout, H, W, k[0]) >= 2 and _dgrad_fits(cin, cout, H, W, k[0]) >= 2
-            and wgrad_served(B, cin, cout, H, W, k[0], masked))
 
 
 def _weight_planes(w, want_transposed: bool, param=None):
@@ -180,7 +79,7 @@ _WSTATE = _WPlanesState()
 
 class batched_weight_planes:
     """context manager around one training pass of an image-shaped flow at a launch-bound batch: the bf16x3 plane pairs of ALL
-    3 x 3 (and, under ``conv_k5`` / ``conv_k4``, 5 x 5 / 4 x 4) convolution weights under ``layers`` from one launch (``_ext.WeightPlanesBatch``; the job table is kept on ``owner``
+    convolution weights above kernel 1 (``conv_kernel_sizes()``) under ``layers`` from one launch (``_ext.WeightPlanesBatch``; the job table is kept on ``owner``
     while the weights keep their addresses) instead of one per convolution and pass"""
 
     def __init__(self, owner, layers, device):
@@ -189,7 +88,7 @@ class batched_weight_planes:
     def __enter__(self):
         self.prev = _WSTATE.planes
         ws, srcs = [], []
-        sizes = ((3, 3),) + (((4, 4),) if config.conv_k4 else ()) + (((5, 5),) if config.conv_k5 else ())
+        sizes = tuple((k, k) for k in conv_kernel_sizes() if k > 1)
         for l in self.layers:
             for m in l.modules():
                 if isinstance(m, torch.nn.Conv2d) and m.kernel_size in sizes and m.weight.device == self.device \
@@ -246,8 +145,47 @@ def _takeable(params) -> bool:
                              and not getattr(q, "_post_accumulate_grad_hooks", None)) for q in params)
 
 
+def _weight_grads(ctx, x, dy, ks, has_bias=True, *, in_mul=None, pre_sub=None, in_act=None, defer=None):
+    """(dW, db | None) of the convolution node `ctx` from input x and output gradient dy, (None, None) when neither is asked
+    for.  defer None: the last sum may be queued if the engine will take the gradients of ``ctx.params`` as handed over
+    (``_takeable``), the Parameters own the sums; True / False: as told, the node owns them.  Which kernels are tried:
+    ``image_rules.wgrad_kernels``; the layer's predicate (conv_shape_ok and its kin) said that one of them serves"""
+    if not (ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2])):
+        return None, None
+    if defer is None:
+        defer, owners = _takeable(ctx.params), tuple(id(q) for q in ctx.params if q is not None)
+    else:
+        owners = (id(ctx),) if defer else ()
+    ia = _act(in_act)
+    r = conv_wgrad(x, dy, ks, in_mul=in_mul, pre_sub=pre_sub, in_act=ia[0], in_slope=ia[1], want_bias=has_bias, defer=defer, owners=owners)
+    if r is None:
+        raise RuntimeError(f"usflows_amd: none of the weight-gradient kernels {wgrad_kernels(ks, x.shape[2] * x.shape[3])} serves a "
+                           f"{ks} x {ks} convolution to {dy.shape[1]} channels on {tuple(x.shape)}, "
+                           f"{'with' if in_mul is not None else 'without'} an input mask (conv_shape_ok was not consulted)")
+    return r
+
+
+def _planes_t(ctx, w):
+    """the flipped, transposed weight planes of the data gradient: the forward's, or made now"""
+    return ctx.planes_t if ctx.planes_t is not None else _ext.conv2d_weight_planes(w, transposed=True)
+
+
+def _input_grad(dy, planes_t, cin, ks, x, in_act, in_mul):
+    """the data gradient with the input's (Leaky)ReLU and mask factors: in the data-gradient convolution's output stream where
+    usf_conv2d_same_gate_f32 takes the shape, else as passes behind the plain one"""
+    dx = None
+    if in_act is not None or in_mul is not None:
+        dx = _ext.conv2d_same_gate(dy, planes_t, cin, ks, x, in_act[1] if in_act is not None else 1.0, in_mul)
+    if dx is None:
+        dx = data_grad(dy, planes_t, cin, ks)
+        _gate_inplace(dx, x, in_act)
+        if in_mul is not None:
+            dx = _ext.masked_residual(None, dx, in_mul, 1.0)
+    return dx
+
+
 class ConvSame(torch.autograd.Function):
-    """out_act(bias + conv(in_act(x) * in_mul)) on usf_conv2d_same_f32 (kernel 1 or 3, stride 1, "same")"""
+    """out_act(bias + conv(in_act(x) * in_mul)) on usf_conv2d_same_f32 (a convolution ``image_rules.same_conv_ks`` takes)"""
 
     @staticmethod
     def forward(ctx, x, weight, bias, in_mul, in_act, out_act):
@@ -271,25 +209,8 @@ class ConvSame(torch.autograd.Function):
         if out_act is not None:
             dy = dy.clone()
             _gate_inplace(dy, y, out_act)
-        ia = _act(in_act)
-        dW = db = dx = None
-        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            r = conv_wgrad(x, dy, ks, in_mul=in_mul, in_act=ia[0], in_slope=ia[1], want_bias=has_bias,
-                                defer=_takeable(ctx.params), owners=tuple(id(q) for q in ctx.params if q is not None))
-            if r is None:
-                raise RuntimeError("usflows_amd: neither usf_conv_wgrad_f32 nor usf_conv_wgrad_wide_f32 serves this shape (conv_shape_ok was not consulted)")
-            dW, db = r
-        if ctx.needs_input_grad[0]:
-            planes_t = ctx.planes_t if ctx.planes_t is not None else _ext.conv2d_weight_planes(w, transposed=True)
-            dx = None
-            if in_act is not None or in_mul is not None:
-                # the input's (Leaky)ReLU and mask factors in the data-gradient convolution's output stream
-                dx = _ext.conv2d_same_gate(dy, planes_t, w.shape[1], ks, x, ia[1] if in_act is not None else 1.0, in_mul)
-            if dx is None:
-                dx = data_grad(dy, planes_t, w.shape[1], ks)
-                _gate_inplace(dx, x, in_act)
-                if in_mul is not None:
-                    dx = _ext.masked_residual(None, dx, in_mul, 1.0)
+        dW, db = _weight_grads(ctx, x, dy, ks, has_bias, in_mul=in_mul, in_act=in_act)
+        dx = _input_grad(dy, _planes_t(ctx, w), w.shape[1], ks, x, in_act, in_mul) if ctx.needs_input_grad[0] else None
         return dx, dW, db, None, None, None
 
 
@@ -325,16 +246,8 @@ class ConvSameRes(torch.autograd.Function):
         ks, has_bias, sign = ctx.cfg
         dy = dy.contiguous()
         dt = _ext.masked_residual(None, dy, om, sign)
-        dW = db = dx = None
-        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            r = conv_wgrad(x, dt, ks, want_bias=has_bias, defer=_takeable(ctx.params),
-                                owners=tuple(id(q) for q in ctx.params if q is not None))
-            if r is None:
-                raise RuntimeError("usflows_amd: neither usf_conv_wgrad_f32 nor usf_conv_wgrad_wide_f32 serves this shape")
-            dW, db = r
-        if ctx.needs_input_grad[0]:
-            planes_t = ctx.planes_t if ctx.planes_t is not None else _ext.conv2d_weight_planes(w, transposed=True)
-            dx = data_grad(dt, planes_t, w.shape[1], ks)
+        dW, db = _weight_grads(ctx, x, dt, ks, has_bias)
+        dx = data_grad(dt, _planes_t(ctx, w), w.shape[1], ks) if ctx.needs_input_grad[0] else None
         return dx, dW, db, dy, None, None
 
 
@@ -364,30 +277,18 @@ class ConvSameFork(torch.autograd.Function):
         x, w, in_mul = ctx.saved_tensors
         ks, in_act, has_bias = ctx.cfg
         dy = dy.contiguous()
-        ia = _act(in_act)
-        dW = db = dx = None
-        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            r = conv_wgrad(x, dy, ks, in_mul=in_mul, in_act=ia[0], in_slope=ia[1], want_bias=has_bias,
-                                defer=_takeable(ctx.params), owners=tuple(id(q) for q in ctx.params if q is not None))
-            if r is None:
-                raise RuntimeError("usflows_amd: neither usf_conv_wgrad_f32 nor usf_conv_wgrad_wide_f32 serves this shape")
-            dW, db = r
+        dW, db = _weight_grads(ctx, x, dy, ks, has_bias, in_mul=in_mul, in_act=in_act)
+        dx = None
         if ctx.needs_input_grad[0]:
-            planes_t = ctx.planes_t if ctx.planes_t is not None else _ext.conv2d_weight_planes(w, transposed=True)
+            planes_t = _planes_t(ctx, w)
             dxs = None if dxs is None else dxs.contiguous()
             if dxs is not None and in_mul is not None and in_act is None:
                 # dx = dxs + mask * dgrad: the residual form of the convolution
                 dx = _ext.conv2d_same_res(dy, planes_t, w.shape[1], ks, dxs, in_mul, 1.0)
             elif dxs is not None and in_mul is None:
-                dx = _ext.conv2d_same_gate(dy, planes_t, w.shape[1], ks, x, ia[1] if in_act is not None else 1.0, gate_add=dxs)
+                dx = _ext.conv2d_same_gate(dy, planes_t, w.shape[1], ks, x, in_act[1] if in_act is not None else 1.0, gate_add=dxs)
             if dx is None:
-                if in_act is not None or in_mul is not None:
-                    dx = _ext.conv2d_same_gate(dy, planes_t, w.shape[1], ks, x, ia[1] if in_act is not None else 1.0, in_mul)
-                if dx is None:
-                    dx = data_grad(dy, planes_t, w.shape[1], ks)
-                    _gate_inplace(dx, x, in_act)
-                    if in_mul is not None:
-                        dx = _ext.masked_residual(None, dx, in_mul, 1.0)
+                dx = _input_grad(dy, planes_t, w.shape[1], ks, x, in_act, in_mul)
                 if dxs is not None:
                     dx = dx + dxs
         return dx, dW, db, None, None
@@ -422,14 +323,11 @@ class ConvSameCtxFork(torch.autograd.Function):
         ks, has_bias = ctx.cfg
         cout, C = w.shape[0], w.shape[1] - 1
         dy = dy.contiguous()
-        dW = db = dx = None
-        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            # (not deferred: the data columns are joined with the context column here, in this pass)
-            r = conv_wgrad(x, dy, ks, in_mul=in_mul, want_bias=has_bias)
-            if r is None:
-                raise RuntimeError("usflows_amd: neither usf_conv_wgrad_f32 nor usf_conv_wgrad_wide_f32 serves this shape")
-            dWd, db = r
-            dW = torch.cat([dWd, _ext.conv_ctx_wgrad(dy, ctx_rows, ks).view(cout, 1, ks, ks)], 1)
+        dx = None
+        # (not deferred: the data columns are joined with the context column here, in this pass)
+        dW, db = _weight_grads(ctx, x, dy, ks, has_bias, in_mul=in_mul, defer=False)
+        if dW is not None:
+            dW = torch.cat([dW, _ext.conv_ctx_wgrad(dy, ctx_rows, ks).view(cout, 1, ks, ks)], 1)
         if ctx.needs_input_grad[0]:
             planes_t = ctx.planes_t if ctx.planes_t is not None else \
                 _ext.conv2d_weight_planes(w[:, :C].contiguous(), transposed=True)
@@ -443,25 +341,6 @@ class ConvSameCtxFork(torch.autograd.Function):
                 if dxs is not None:
                     dx = dx + dxs
         return dx, dW, db, None, None
-
-
-def conv_ctx_shape_ok(conv, B: int, H: int, W: int) -> bool:
-    """the first convolution of a conditional conditioner (C + 1 input channels, the last one the context) has a device forward,
-    data gradient and weight gradient at [B, C, H, W]"""
-    if not isinstance(conv, torch.nn.Conv2d) or conv.in_channels < 2:
-        return False
-    k = conv.kernel_size
-    if k[0] != k[1] or k[0] not in train_kernel_sizes() or conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 \
-            or conv.padding_mode != "zeros":
-        return False
-    if not _same_padding(conv):
-        return False
-    lib = _ext.load()
-    C, cout = conv.in_channels - 1, conv.out_channels
-    return (lib.usf_conv2d_same_fits(C, cout, H, W, k[0]) >= 2 and _dgrad_fits(C, cout, H, W, k[0]) >= 2
-            and (_narrow_wgrad_served(B, C, cout, H, W, k[0], True) if k[0] not in (4, 5) else
-                 (H * W < WIDE_MIN_PIXELS and wgrad_served(B, C, cout, H, W, k[0], True))))    # (the first convolution: it may be handed the coupling's mask;
-                                                                       # above 64 pixels conditional conditioners stay declined)
 
 
 class Pointwise(torch.autograd.Function):
@@ -484,12 +363,10 @@ class Pointwise(torch.autograd.Function):
         in_act, has_bias, wshape = ctx.cfg
         dy = dy.contiguous()
         ia = _act(in_act)
-        dW = db = dx = None
-        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            r = conv_wgrad(x, dy, 1, in_act=ia[0], in_slope=ia[1], want_bias=has_bias, defer=_takeable(ctx.params), owners=tuple(id(q) for q in ctx.params if q is not None))
-            if r is None:
-                raise RuntimeError("usflows_amd: neither usf_conv_wgrad_f32 nor usf_conv_wgrad_wide_f32 serves this shape")
-            dW, db = r[0].reshape(wshape), r[1]
+        dx = None
+        dW, db = _weight_grads(ctx, x, dy, 1, has_bias, in_act=in_act)
+        if dW is not None:
+            dW = dW.reshape(wshape)
         if ctx.needs_input_grad[0]:
             if in_act is not None and ia[0] == _ext.ACT_LEAKY_RELU:
                 # the derivative of the input's (Leaky)ReLU rides in the data-gradient pass
@@ -497,32 +374,6 @@ class Pointwise(torch.autograd.Function):
             else:
                 dx = _ext.pointwise_conv(dy, w2.t().contiguous())
         return dx, dW, db, None
-
-
-def pointwise_shape_ok(conv, B: int, H: int, W: int) -> bool:
-    """a kernel-1 nn.Conv2d whose forward and data gradient run on usf_pointwise_conv_f32"""
-    if not (isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.groups == 1):
-        return False
-    pad = conv.padding
-    if not (pad == "same" or (not isinstance(pad, str) and tuple(pad) == (0, 0))):
-        return False
-    cin, cout = conv.in_channels, conv.out_channels
-    return (_ext.pointwise_conv_supported(cin, cout, False) and _ext.pointwise_conv_supported(cout, cin, False)
-            and _wgrad_workspace_ok(B, cin, cout, H, W))
-
-
-def gate_halves_ok(conv, B: int, H: int, W: int) -> bool:
-    """under the knobs ``conv_k5`` / ``conv_k4`` (either) only: GatedConv's 1 x 1 convolution C -> 2 C with more than the kernels' 64 output channels
-    (C = 33 .. 64: the 64 hidden channels of the hyper-parameter search) runs as TWO convolutions C -> C, the value rows and the
-    gate rows of its weight (``gate_halves``), each with a device forward, data gradient and weight gradient"""
-    if not ((config.conv_k5 or config.conv_k4) and isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
-            and conv.groups == 1 and conv.out_channels == 2 * conv.in_channels and 64 < conv.out_channels <= 128):
-        return False
-    pad = conv.padding
-    if not (pad == "same" or (not isinstance(pad, str) and tuple(pad) == (0, 0))):
-        return False
-    C = conv.in_channels
-    return _ext.load().usf_conv2d_same_fits(C, C, H, W, 1) >= 2 and wgrad_served(B, C, C, H, W, 1, False)
 
 
 def gate_halves(h, conv, in_act):
@@ -555,11 +406,7 @@ class GatedResidual(torch.autograd.Function):
 def gated_tail_ok(conv2, x, ln=None) -> bool:
     """GatedConv's 1 x 1 convolution `conv2` (C -> 2 C) with the gate, the skip connection [and the (Leaky)ReLU + LayerNormChannels
     that follow] as ONE differentiable launch each way (usf_gated_tail_f32 / usf_gated_tail_bwd_f32) at this input"""
-    if not (config.gated_tail and isinstance(conv2, torch.nn.Conv2d) and conv2.kernel_size == (1, 1) and conv2.stride == (1, 1)
-            and conv2.groups == 1 and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
-        return False
-    pad = conv2.padding
-    if not (pad == "same" or (not isinstance(pad, str) and tuple(pad) == (0, 0))):
+    if not (config.gated_tail and pointwise_geometry(conv2) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
         return False
     B, Cc, H, W = x.shape
     wide = H * W >= WIDE_MIN_PIXELS
@@ -690,12 +537,11 @@ class ChannelAffine(torch.autograd.Function):
             if ctx.pre_sub:
                 db = -(Wd.t() @ db)
             return dx, dW, db, None, None, None
-        if want_w:
-            r = conv_wgrad(x, dy, 1, pre_sub=bd if ctx.pre_sub else None, want_bias=True, defer=ctx.defer, owners=(id(ctx),))
-            if r is None:
-                raise RuntimeError("usflows_amd: neither usf_conv_wgrad_f32 nor usf_conv_wgrad_wide_f32 serves this channel count")
-            dW = r[0].reshape(Wd.shape)
-            db = -(Wd.t() @ r[1]) if ctx.pre_sub else r[1]
+        dW, db = _weight_grads(ctx, x, dy, 1, pre_sub=bd if ctx.pre_sub else None, defer=ctx.defer)
+        if dW is not None:
+            dW = dW.reshape(Wd.shape)
+            if ctx.pre_sub:
+                db = -(Wd.t() @ db)
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(dy)
             _ext.channel_affine(dy, dx, Wt if Wt is not None else Wd.t().contiguous())
@@ -721,10 +567,10 @@ def channel_affine_train_ok(x, C) -> bool:
         return False
     B, H, W = x.shape[0], x.shape[2], x.shape[3]
     if C in (16, 32, 48, 64):
-        return _wgrad_workspace_ok(B, C, C, H, W)
+        return wgrad_served(B, C, C, H, W, 1, False)
     if C <= AFFINE_SMALL_C_MAX:
         return affine_small_c_served(B, C, H * W)
-    return H * W >= WIDE_MIN_PIXELS and wide_wgrad_served(B, C, C, H, W, 1)
+    return wide_wgrad_served(B, C, C, H, W, 1)
 
 
 class BaseLogProb(torch.autograd.Function):

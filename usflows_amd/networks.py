@@ -22,6 +22,8 @@ from typing import List, Optional, Sequence
 import torch
 
 from .config import config  # noqa: E402
+from .image_rules import (conv_kernel_sizes as _conv_kernel_sizes, gate_conv_route, same_conv_ks,  # noqa: F401
+                          same_padding as _same_padding)
 from torch import nn
 
 
@@ -419,30 +421,14 @@ def _relu_kind(m):
     return None
 
 
-def _conv_kernel_sizes() -> tuple:
-    """kernel sizes of the "same" convolution's device path: 1 and 3, 4 under the knob ``conv_k4`` (padding="same" only: torch's
-    placement, one zero before and two after), 5 under the knob ``conv_k5``"""
-    return (1, 3) + ((4,) if config.conv_k4 else ()) + ((5,) if config.conv_k5 else ())
-
-
-def _same_padding(conv) -> bool:
-    """the string "same", or k // 2 on both sides at an odd kernel (at kernel 4 the integer padding (2, 2) is not "same")"""
-    k, pad = conv.kernel_size[0], conv.padding
-    return pad == "same" or (k % 2 == 1 and not isinstance(pad, str) and tuple(pad) == (k // 2, k // 2))
-
-
 def _conv_same_shaped(conv, x) -> bool:
-    """an nn.Conv2d call the device kernels can express: stride 1, "same" zero padding, kernel 1 or 3 (5 under the knob
-    ``conv_k5``), fp32 on a ROCm device, nothing to differentiate"""
+    """an nn.Conv2d call the device kernels can express (``image_rules.same_conv_ks``), fp32 on a ROCm device, nothing to
+    differentiate"""
     if not (isinstance(conv, nn.Conv2d) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
         return False
     if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad):
         return False
-    k = conv.kernel_size
-    if k[0] != k[1] or k[0] not in _conv_kernel_sizes() or conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 \
-            or conv.padding_mode != "zeros" or x.shape[1] != conv.in_channels:
-        return False
-    return _same_padding(conv)
+    return x.shape[1] == conv.in_channels and same_conv_ks(conv) > 0
 
 
 def _conv_hip_ok(conv, x) -> bool:
@@ -511,21 +497,16 @@ def _conv_hip(conv, x, in_act=None, in_mul=None, out_act=None, residual=None):
 
 def _conv_ctx_ok(conv, x) -> bool:
     """conv is the first convolution of a conditional conditioner (one input channel more than x: the context plane) and
-    usf_conv2d_same_ctx_f32 serves it on x: stride 1, "same" zero padding, kernel 1 or 3 (5 under the knob ``conv_k5``), fp32 on a
-    ROCm device, nothing to differentiate, at least two samples per LDS group"""
+    usf_conv2d_same_ctx_f32 serves it on x: a convolution ``image_rules.same_conv_ks`` takes, fp32 on a ROCm device, nothing to
+    differentiate, at least two samples per LDS group"""
     if not (isinstance(conv, nn.Conv2d) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
             and conv.in_channels == x.shape[1] + 1 and conv.weight.dtype == torch.float32):
         return False
     if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad):
         return False
-    k = conv.kernel_size
-    if k[0] != k[1] or k[0] not in _conv_kernel_sizes() or conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 \
-            or conv.padding_mode != "zeros":
-        return False
-    if not _same_padding(conv):
-        return False
+    ks = same_conv_ks(conv)
     from . import _ext
-    return _ext.load().usf_conv2d_same_fits(x.shape[1], conv.out_channels, x.shape[2], x.shape[3], k[0]) >= 2
+    return ks > 0 and _ext.load().usf_conv2d_same_fits(x.shape[1], conv.out_channels, x.shape[2], x.shape[3], ks) >= 2
 
 
 def _conv_hip_ctx(conv, x, ctx_rows, in_mul=None, out_act=None):
@@ -627,7 +608,7 @@ class GatedConv(nn.Module):
         return (_relu_kind(n[0]) is not None and _relu_kind(n[2]) is not None and isinstance(n[1], nn.Conv2d)
                 and isinstance(n[3], nn.Conv2d) and n[1].in_channels == C and n[3].out_channels == 2 * C
                 and n[3].in_channels == n[1].out_channels and it.conv_shape_ok(n[1], B, H, W)
-                and (it.pointwise_shape_ok(n[3], B, H, W) or it.conv_shape_ok(n[3], B, H, W) or it.gate_halves_ok(n[3], B, H, W)))
+                and gate_conv_route(n[3], B, H, W) is not None)
 
     def forward_train_device(self, x, post=None):
         """the block as differentiable device passes: 3 x 3 convolution, then -- few pixels (image_training.gated_tail_ok) -- ONE
@@ -642,9 +623,10 @@ class GatedConv(nn.Module):
             pa, lnm = post if post is not None else (None, None)
             return it.GatedTail.apply(h, x, n[3].weight, n[3].bias, None if lnm is None else lnm.gamma,
                                       None if lnm is None else lnm.beta, a2, pa, 0.0 if lnm is None else lnm.eps)
-        if it.pointwise_shape_ok(n[3], x.shape[0], x.shape[2], x.shape[3]):
+        route = gate_conv_route(n[3], x.shape[0], x.shape[2], x.shape[3])
+        if route == "pointwise":
             vg = it.Pointwise.apply(h, n[3].weight, n[3].bias, a2)
-        elif not it.conv_shape_ok(n[3], x.shape[0], x.shape[2], x.shape[3]) and it.gate_halves_ok(n[3], x.shape[0], x.shape[2], x.shape[3]):
+        elif route == "halves":
             vg = it.gate_halves(h, n[3], a2)                       # (2 C > 64 output channels: value rows and gate rows apart)
         else:
             vg = it.ConvSame.apply(h, n[3].weight, n[3].bias, None, a2, None)
