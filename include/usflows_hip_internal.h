@@ -72,7 +72,8 @@ int usf_internal_version(void);
  * usf_sizeof_desc(kind) also reports sizeof(usf_mt_chunk|usf_grad_job|usf_psum_job) for kind 8|11|12 and
  * sizeof(usf_gated_norm_bwd_desc|usf_wgrad_job|usf_wreduce_job|usf_wplanes_job) for kind 13|14|15|16 and
  * sizeof(usf_adam_chunk|usf_grad_chunk|usf_conv_variant_query|usf_conv_variant) for kind 17|18|19|20 and
- * sizeof(usf_conv_wgrad_query|usf_conv_wgrad_info|usf_ln_bwd_info) for kind 21|22|23.
+ * sizeof(usf_conv_wgrad_query|usf_conv_wgrad_info|usf_ln_bwd_info) for kind 21|22|23 and
+ * sizeof(usf_conv_band_query|usf_conv_band_info) for kind 27|28.
  */
 
 /*
@@ -573,6 +574,44 @@ typedef struct usf_conv_variant {
   int32_t max_mHW, max_mW, max_mSE, max_mSO;
 } usf_conv_variant;
 int usf_conv2d_same_variant(const usf_conv_variant_query* q, usf_conv_variant* out);
+
+/*
+ * usf_conv2d_same_band_f32 (an addition: USF_INTERNAL_VERSION is unchanged): the "same" convolution of usf_conv2d_same_f32 /
+ * usf_conv2d_same_ctx_f32 (usflows_hip.h; ctx == NULL: the plain form, else ctx / ctx_stride / w_ctx as there) for feature maps
+ * of up to 4096 pixels, on a fifth kernel, conv2d_same_band_kernel<CTX> (usf_conv_band.hip): a group of a persistent block is a
+ * band of consecutive output rows of ONE sample, its LDS image (rows + ks - 1) x (W + ks - 1) positions beside the resident
+ * weight planes.  Same arithmetic (bf16x3, six matrix instructions per product, k-blocks in order) and the same weight planes,
+ * exactly as usf_conv2d_weight_planes_f32 makes them; an output element's bits depend on neither the band height nor the batch.
+ * Served: ks 1 or 3, stride 1, zero "same" padding, 1 <= cin, cout <= 64, W <= 64, H W <= 4096 (maps of 256 pixels and fewer
+ * included), B >= 1, the weight planes and a band within 158 KiB of LDS and 16 register-staged iterations per thread, and at
+ * ks = 3 a best band of at least 4 output rows (or the whole map).  No gated mode, no fused residual, no gate forms, inference
+ * only; no USF_FN_* id (a pass that calls it is not recorded as an op list).
+ * band_rows: 0 = the plan's band; > 0 caps the band at that many output rows (a measurement and test aid).
+ * Returns 0, 1 for a valid shape that is not served (nothing is launched), < 0 on bad arguments (usf_last_error()).
+ * usf_conv2d_same_band_fits (host only): output rows per band the plan would use, 0 = not served.
+ * usf_conv2d_same_band_variant (host only, nothing is launched): the plan of such a call.  Query: the sizes, ctx (1: the context
+ * form), band_rows as above, cus (0: ask the device; > 0: plan for that many compute units -- works without a GPU).  Answer:
+ * served 0 / 1; band_rows, bands per sample, last_rows (output rows of a sample's last band), groups = B * bands, grid blocks,
+ * lds_bytes, stage_iters (register-staged iterations per thread, at most 16), CTX, the patch shape (PC, PR) in 16-row tiles of a
+ * full band and of a last band; best_rows (the shape's band before the cap) and weight_bytes (LDS bytes of the weight planes)
+ * are filled for refused shapes too where the sizes are in range.  Returns 0 or -1 (null pointer).
+ * usf_sizeof_desc reports sizeof(usf_conv_band_query|usf_conv_band_info) for kind 27|28.
+ */
+typedef struct usf_conv_band_query {
+  int64_t B, cin, cout, H, W, ks;
+  int32_t ctx, band_rows, cus, reserved;
+} usf_conv_band_query;
+typedef struct usf_conv_band_info {
+  int32_t served, band_rows, bands, last_rows;
+  int64_t groups, grid, lds_bytes, weight_bytes;
+  int32_t stage_iters, CTX, PC_full, PR_full, PC_last, PR_last, best_rows, reserved;
+} usf_conv_band_info;
+int usf_conv2d_same_band_fits(int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks);
+int usf_conv2d_same_band_f32(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
+                             const void* w_planes, const float* bias, const float* in_mul, int32_t in_act, float in_slope,
+                             int32_t out_act, float out_slope, const float* ctx, int64_t ctx_stride, const float* w_ctx,
+                             int64_t band_rows, usf_stream_t stream);
+int usf_conv2d_same_band_variant(const usf_conv_band_query* q, usf_conv_band_info* out);
 
 /* which instantiation of usf_gemm_planes_bf16x3 serves the descriptor (nothing is launched): 5000 + 10 TN + (1: fp32 output, 0: planes output),
  * TN = column-block width in 32-feature blocks (4 or 5, whichever pads the output less); 0 for empty extents */

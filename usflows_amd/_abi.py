@@ -163,6 +163,19 @@ class ChannelAffineBwdInfo(C.Structure):
                                          "rows_used", "grid_cap", "reserved")]
 
 
+class ConvBandQuery(C.Structure):
+    """usf_conv_band_query: one call of usf_conv2d_same_band_f32, as usf_conv2d_same_band_variant is asked about it"""
+    _fields_ = [("B", C.c_int64), ("cin", C.c_int64), ("cout", C.c_int64), ("H", C.c_int64), ("W", C.c_int64), ("ks", C.c_int64),
+                ("ctx", C.c_int32), ("band_rows", C.c_int32), ("cus", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ConvBandInfo(C.Structure):
+    """usf_conv_band_info: the band height, bands per sample, grid, LDS bytes, staging iterations and patch shapes such a call launches"""
+    _fields_ = [("served", C.c_int32), ("band_rows", C.c_int32), ("bands", C.c_int32), ("last_rows", C.c_int32),
+                ("groups", C.c_int64), ("grid", C.c_int64), ("lds_bytes", C.c_int64), ("weight_bytes", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("stage_iters", "CTX", "PC_full", "PR_full", "PC_last", "PR_last", "best_rows", "reserved")]
+
+
 CONV_ENTRIES = {"plain": 0, "ctx": 1, "res": 2, "gate_mul": 3, "gate_add": 4, "gated": 5}   # USF_CONV_ENTRY_*
 
 
@@ -254,7 +267,7 @@ SIZEOF_KINDS = {OP_LINEAR: LinearDesc, OP_COUPLING: CouplingDesc, 0: Op, 3: LuPr
                 OP_GEMM_PLANES: GemmPlanesDesc, OP_COUPLING_PLANES: CouplingPlanesDesc, 8: MtChunk, OP_GATED_NORM: GatedNormDesc,
                 OP_CALL: CallDesc, 11: GradJob, 12: PsumJob, 13: GatedNormBwdDesc, 14: WgradJob, 15: WReduceJob, 16: WPlanesJob, 17: AdamChunk, 18: GradChunk,
                 19: ConvVariantQuery, 20: ConvVariant, 21: ConvWgradQuery, 22: ConvWgradInfo, 23: LnBwdInfo, 24: ConvWgradWideInfo,
-                25: ChannelAffineBwdQuery, 26: ChannelAffineBwdInfo}
+                25: ChannelAffineBwdQuery, 26: ChannelAffineBwdInfo, 27: ConvBandQuery, 28: ConvBandInfo}
 
 
 # every symbol include/usflows_hip.h declares (the stable public ABI): (restype, argtypes)
@@ -345,6 +358,10 @@ INTERNAL_SYMBOLS = {
     "usf_layernorm_channels_bwd_variant": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(LnBwdInfo)]),
     "usf_conv_wgrad_workspace": (C.c_int64, [C.c_int64] * 6),
     "usf_conv2d_same_pad_fits": (C.c_int, [C.c_int64] * 6),
+    "usf_conv2d_same_band_fits": (C.c_int, [C.c_int64] * 5),
+    "usf_conv2d_same_band_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [_fp, _fp, _fp, C.c_int32, C.c_float, C.c_int32, C.c_float, _fp,
+                                           C.c_int64, _fp, C.c_int64, C.c_void_p]),
+    "usf_conv2d_same_band_variant": (C.c_int, [C.POINTER(ConvBandQuery), C.POINTER(ConvBandInfo)]),
     "usf_conv2d_same_pad_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 7 + [_fp, _fp, _fp, C.c_int32, C.c_float, C.c_int32, C.c_float, _fp,
                                           C.c_int64, C.c_void_p]),
     "usf_conv_wgrad_f32": (C.c_int, [_fp, _fp] + [C.c_int64] * 6 + [_fp, _fp, C.c_int32, C.c_float, _fp, _fp, _fp, C.c_int64,

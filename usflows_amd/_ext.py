@@ -24,7 +24,7 @@ from ._abi import (  # noqa: E402,F401  -- the declarations, re-exported: caller
     BASE_LPNORM1, BASE_LPNORM2, BASE_LPNORMINF, BASE_ROWSUM, NORM_LOGNORMAL, NORM_GAMMA, NORM_RAW_PARAMS, NORM_WEIBULL, NORM_HALFNORMAL, NORM_CHI, RADIAL_MAX_K, OP_LINEAR,
     OP_COUPLING, OP_PACK_PLANES, OP_GEMM_PLANES, OP_COUPLING_PLANES, OP_GATED_NORM, OP_CALL, PLANES_BF16X3, PLANES_F16X2, CALL_FNS,
     FN_COUPLING_PLANES_CTX, FN_COUPLING_VCTX, FN_GEMM_PLANES_SIDE, FN_COUPLING_PLANES_SIDE, VCTX_MAX,
-    _fp, LinearDesc, CouplingDesc, PackPlanesDesc, GemmPlanesDesc, CouplingPlanesDesc, MtChunk, AdamChunk, GradChunk, ConvVariantQuery, ConvVariant, ConvWgradQuery, ConvWgradInfo, ConvWgradWideInfo, ChannelAffineBwdQuery, ChannelAffineBwdInfo, LnBwdInfo, CONV_ENTRIES, GatedNormDesc, GatedNormBwdDesc,
+    _fp, LinearDesc, CouplingDesc, PackPlanesDesc, GemmPlanesDesc, CouplingPlanesDesc, MtChunk, AdamChunk, GradChunk, ConvVariantQuery, ConvVariant, ConvBandQuery, ConvBandInfo, ConvWgradQuery, ConvWgradInfo, ConvWgradWideInfo, ChannelAffineBwdQuery, ChannelAffineBwdInfo, LnBwdInfo, CONV_ENTRIES, GatedNormDesc, GatedNormBwdDesc,
     CallDesc, _OpUnion, Op, LuPrepDesc, PackJob, PsumJob, WgradJob, WReduceJob, WPlanesJob, GradJob, SIZEOF_KINDS, PUBLIC_SYMBOLS,
     INTERNAL_SYMBOLS, SYMBOLS)
 
@@ -616,6 +616,34 @@ def conv2d_same_variant(entry, B, cin, cout, H, W, ks=3, aligned=True, cus=0) ->
     out = ConvVariant()
     check(load().usf_conv2d_same_variant(C.byref(q), C.byref(out)), "usf_conv2d_same_variant")
     return {name: int(getattr(out, name)) for name, _ in ConvVariant._fields_}
+
+
+def conv2d_same_band(x, planes, cout, ks, ctx=None, w_ctx=None, bias=None, in_mul=None, in_act=ACT_NONE, in_slope=0.0, out_act=ACT_NONE,
+                     out_slope=0.0, band_rows=0):
+    """usf_conv2d_same_band_f32: conv2d_same / conv2d_same_ctx (ctx, w_ctx given: as there) on the row-banded kernel, feature maps
+    of up to 4096 pixels, kernel 1 or 3 -> new [B, cout, H, W] tensor, or None when the shape is not served.  band_rows > 0 caps
+    the band's output rows (tests, measurements).  The call has no op-list form: a recording pass is marked bad by it"""
+    B, cin, H, W = x.shape
+    stride = 0
+    if ctx is not None:
+        n = ctx.numel()
+        assert ctx.is_cuda and ctx.dtype == torch.float32 and ctx.is_contiguous() and n in (1, B), (ctx.shape, B)
+        assert w_ctx.dtype == torch.float32 and w_ctx.is_contiguous() and w_ctx.numel() == cout * ks * ks
+        stride = 1 if (n == B and B > 1) else 0
+    y = torch.empty(B, cout, H, W, dtype=torch.float32, device=x.device)
+    rc = _launch("usf_conv2d_same_band_f32", (x.data_ptr(), y.data_ptr(), B, cin, cout, H, W, ks, planes.data_ptr(), ptr(bias),
+                                              ptr(in_mul), int(in_act), float(in_slope), int(out_act), float(out_slope), ptr(ctx), stride,
+                                              ptr(w_ctx), int(band_rows), current_stream(x.device)), tape=False, unserved_ok=True)
+    return None if rc else y
+
+
+def conv2d_same_band_variant(B, cin, cout, H, W, ks=3, ctx=False, band_rows=0, cus=0) -> dict:
+    """usf_conv2d_same_band_variant: the plan usf_conv2d_same_band_f32 launches from for these sizes, as a dict of the answer's
+    fields (served 0: refused); cus > 0 plans for that many compute units (no GPU needed), 0 asks the device"""
+    q = ConvBandQuery(int(B), int(cin), int(cout), int(H), int(W), int(ks), int(bool(ctx)), int(band_rows), int(cus), 0)
+    out = ConvBandInfo()
+    check(load().usf_conv2d_same_band_variant(C.byref(q), C.byref(out)), "usf_conv2d_same_band_variant")
+    return {name: int(getattr(out, name)) for name, _ in ConvBandInfo._fields_ if name != "reserved"}
 
 
 def conv_wgrad_variant(B, cin, cout, H, W, ks=3, masked=False, cus=0, blocks_per_cu=0) -> dict:

@@ -118,6 +118,11 @@ int conv2d_same(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, 
                 int32_t out_act, float out_slope, const float* gate_x, int64_t gate_channels, hipStream_t stream,
                 const float* ctx = nullptr, int64_t ctx_stride = 0, const float* w_ctx = nullptr, int pad_before = -1);
 int conv2d_same_variant(const usf_conv_variant_query* q, usf_conv_variant* out);
+int conv2d_same_band_fits(int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks);
+int conv2d_same_band_variant(const usf_conv_band_query* q, usf_conv_band_info* out);
+int conv2d_same_band(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
+                     const void* wplanes, const float* bias, const float* in_mul, int32_t in_act, float in_slope, int32_t out_act,
+                     float out_slope, const float* ctx, int64_t ctx_stride, const float* w_ctx, int64_t band_rows, hipStream_t stream);
 int conv_ctx_wgrad(const float* dy, const float* ctx, int64_t ctx_stride, int64_t B, int64_t cout, int64_t H, int64_t W, int64_t ks,
                    float* dw_ctx, hipStream_t stream);
 int conv2d_same_gate(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
@@ -256,6 +261,8 @@ int usf_sizeof_desc(int32_t kind) {
     case 24: return (int)sizeof(usf_conv_wgrad_wide_info);
     case 25: return (int)sizeof(usf_channel_affine_bwd_query);
     case 26: return (int)sizeof(usf_channel_affine_bwd_info);
+    case 27: return (int)sizeof(usf_conv_band_query);
+    case 28: return (int)sizeof(usf_conv_band_info);
     default: return -1;
   }
 }
@@ -514,6 +521,17 @@ int usf_gated_tail_bwd_f32(const float* h, const float* x, const float* dy, floa
 }
 int64_t usf_conv2d_weight_elems(int64_t cin, int64_t cout, int64_t ks) { return usf::conv2d_weight_elems(cin, cout, ks); }
 int usf_conv2d_same_variant(const usf_conv_variant_query* q, usf_conv_variant* out) { return usf::conv2d_same_variant(q, out); }
+int usf_conv2d_same_band_fits(int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks) {
+  return usf::conv2d_same_band_fits(cin, cout, H, W, ks);
+}
+int usf_conv2d_same_band_variant(const usf_conv_band_query* q, usf_conv_band_info* out) { return usf::conv2d_same_band_variant(q, out); }
+int usf_conv2d_same_band_f32(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
+                             const void* w_planes, const float* bias, const float* in_mul, int32_t in_act, float in_slope,
+                             int32_t out_act, float out_slope, const float* ctx, int64_t ctx_stride, const float* w_ctx,
+                             int64_t band_rows, usf_stream_t stream) {
+  return usf::conv2d_same_band(x, y, B, cin, cout, H, W, ks, w_planes, bias, in_mul, in_act, in_slope, out_act, out_slope, ctx,
+                               ctx_stride, w_ctx, band_rows, (hipStream_t)stream);
+}
 int usf_conv2d_same_fits(int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks) { return usf::conv2d_same_fits(cin, cout, H, W, ks); }
 int usf_conv2d_same_f32(const float* x, float* y, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
                         const void* w_planes, const float* bias, const float* in_mul, int32_t in_act, float in_slope,

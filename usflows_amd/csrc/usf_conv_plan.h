@@ -63,6 +63,22 @@ struct ConvSPlan {
   unsigned grid;
 };
 
+// fifth kernel (conv2d_same_band_kernel, usf_conv_band.hip): ks = 1 / 3 on maps of up to 4096 pixels, a group = a band of rows
+struct ConvBPlan {
+  int RB;                       // output rows per band of this launch (0: not served)
+  int RB_best;                  // ... the shape's own band, before the caller's cap
+  int nbands, last_rows;        // bands per sample, output rows of a sample's last band
+  int iters, npass;             // register-staged iterations per thread, 64-pixel passes over a full band's staged rows
+  int64_t lds, wbytes;          // dynamic LDS bytes of the launch, of which the weight planes
+  int xs16, ws16, cp, kp, coutp;
+  int64_t groups;               // B * nbands
+  unsigned grid;
+};
+// register-staged iterations per thread for a band whose image has `rows` rows (output rows + ks - 1) of W pixels
+inline int conv_band_stage_iters(int cin, int W, int rows) { return (((cin + 1) / 2 + 7) / 8) * ((rows * W + 63) / 64); }
+// 0: *p is the launch plan; 1: the shape is not served (p->RB_best / p->wbytes are still filled where the sizes are in range)
+int conv_band_plan(int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks, int band_rows, int cus, ConvBPlan* p);
+
 // register-staged iterations per thread for a group of S samples (the first and fourth kernel hold at most 16 pixel pairs per thread)
 inline int conv_stage_iters(int cin, int HW, int S) { return ((S * ((cin + 1) / 2) + 7) / 8) * ((HW + 63) / 64); }
 

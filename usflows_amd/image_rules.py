@@ -14,6 +14,7 @@ import torch
 from . import _ext
 from .config import config
 
+BAND_MIN_PIXELS = 257    # feature maps of 257 .. 4096 pixels: usf_conv2d_same_f32 refuses them, usf_conv2d_same_band_f32 serves them (inference)
 WIDE_MIN_PIXELS = 65      # feature maps of 65 .. 256 pixels: usf_conv_wgrad_f32 refuses them, usf_conv_wgrad_wide_f32 serves them
 
 
@@ -49,6 +50,15 @@ def pointwise_geometry(conv) -> bool:
     are not looked at (neither means anything at kernel 1 without padding; GatedConv hands its dilation to this convolution)"""
     return (isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.groups == 1
             and same_padding(conv))
+
+
+def band_conv_ok(cin: int, cout: int, H: int, W: int, ks: int) -> bool:
+    """inference only, under the knob ``conv_band``: a "same" convolution on a feature map too large for usf_conv2d_same_f32
+    (more than 256 pixels) that the row-banded kernel serves (usf_conv2d_same_band_f32: kernel 1 / 3, up to 64 channels, up to
+    4096 pixels, W <= 64, a band of at least 4 rows beside the weight planes in the LDS).  Training does not ask this rule:
+    no weight-gradient kernel serves such maps"""
+    return bool(config.conv_band) and H * W >= BAND_MIN_PIXELS and ks in (1, 3) and \
+        _ext.load().usf_conv2d_same_band_fits(cin, cout, H, W, ks) > 0
 
 
 # ---- the weight gradient's route ------------------------------------------------------------------------------------------------

@@ -22,7 +22,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from .config import config  # noqa: E402
-from .image_rules import (conv_kernel_sizes as _conv_kernel_sizes, gate_conv_route, same_conv_ks,  # noqa: F401
+from .image_rules import (band_conv_ok, conv_kernel_sizes as _conv_kernel_sizes, gate_conv_route, same_conv_ks,  # noqa: F401
                           same_padding as _same_padding)
 from torch import nn
 
@@ -433,11 +433,12 @@ def _conv_same_shaped(conv, x) -> bool:
 
 def _conv_hip_ok(conv, x) -> bool:
     """this nn.Conv2d call is served by usf_conv2d_same_f32: `_conv_same_shaped`, and at least two samples per LDS group
-    (below that torch's convolution is faster)"""
+    (below that torch's convolution is faster) -- or, above 256 pixels, by the row-banded kernel (``image_rules.band_conv_ok``)"""
     if not _conv_same_shaped(conv, x):
         return False
     from . import _ext
-    return _ext.load().usf_conv2d_same_fits(conv.in_channels, conv.out_channels, x.shape[2], x.shape[3], conv.kernel_size[0]) >= 2
+    shape = (conv.in_channels, conv.out_channels, x.shape[2], x.shape[3], conv.kernel_size[0])
+    return _ext.load().usf_conv2d_same_fits(*shape) >= 2 or band_conv_ok(*shape)
 
 
 def _pointwise_hip(conv, x, in_act=None, gate_x=None, post=None):
@@ -484,6 +485,14 @@ def _conv_hip(conv, x, in_act=None, in_mul=None, out_act=None, residual=None):
     ia, isl = in_act if in_act is not None else (_ext.ACT_NONE, 0.0)
     oa, osl = out_act if out_act is not None else (_ext.ACT_NONE, 0.0)
     bias = None if conv.bias is None else conv.bias.detach().to(torch.float32).contiguous()
+    if band_conv_ok(conv.in_channels, conv.out_channels, x.shape[2], x.shape[3], conv.kernel_size[0]):
+        # above 256 pixels: the row-banded kernel; the fused residual form does not exist there, the caller runs
+        # usf_masked_residual_f32 as a pass of its own (as whenever the fused form declines)
+        out = _ext.conv2d_same_band(x.contiguous(), cache[1], conv.out_channels, conv.kernel_size[0], bias=bias, in_mul=in_mul,
+                                    in_act=ia, in_slope=isl, out_act=oa, out_slope=osl)
+        if out is None:
+            raise RuntimeError("usf_conv2d_same_band_f32 refused a shape usf_conv2d_same_band_fits accepted")
+        return (out, False) if residual is not None else out
     if residual is not None and out_act is None and config.conv_res:
         rx, om, sign = residual
         y = _ext.conv2d_same_res(x.contiguous(), cache[1], conv.out_channels, conv.kernel_size[0], rx.contiguous(), om, sign,
@@ -506,7 +515,8 @@ def _conv_ctx_ok(conv, x) -> bool:
         return False
     ks = same_conv_ks(conv)
     from . import _ext
-    return ks > 0 and _ext.load().usf_conv2d_same_fits(x.shape[1], conv.out_channels, x.shape[2], x.shape[3], ks) >= 2
+    shape = (x.shape[1], conv.out_channels, x.shape[2], x.shape[3], ks)
+    return ks > 0 and (_ext.load().usf_conv2d_same_fits(*shape) >= 2 or band_conv_ok(*shape))
 
 
 def _conv_hip_ctx(conv, x, ctx_rows, in_mul=None, out_act=None):
@@ -523,6 +533,12 @@ def _conv_hip_ctx(conv, x, ctx_rows, in_mul=None, out_act=None):
         conv._usf_ctx_planes = cache
     oa, osl = out_act if out_act is not None else (_ext.ACT_NONE, 0.0)
     bias = None if conv.bias is None else conv.bias.detach().to(torch.float32).contiguous()
+    if band_conv_ok(x.shape[1], conv.out_channels, x.shape[2], x.shape[3], conv.kernel_size[0]):
+        out = _ext.conv2d_same_band(x.contiguous(), cache[1], conv.out_channels, conv.kernel_size[0], ctx=ctx_rows, w_ctx=cache[2],
+                                    bias=bias, in_mul=in_mul, out_act=oa, out_slope=osl)
+        if out is None:
+            raise RuntimeError("usf_conv2d_same_band_f32 refused a shape usf_conv2d_same_band_fits accepted")
+        return out
     return _ext.conv2d_same_ctx(x.contiguous(), cache[1], conv.out_channels, conv.kernel_size[0], ctx_rows, cache[2], bias=bias,
                                 in_mul=in_mul, out_act=oa, out_slope=osl)
 
