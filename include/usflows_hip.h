@@ -91,7 +91,9 @@ typedef struct usf_linear_desc {
   /* Optional split-precision copy of W for the bf16x3 path (fp32-equivalent accuracy on the bf16 matrix
    * cores): three bf16 planes W1+W2+W3 == W (round-to-nearest residual split), plane p at
    * W_split + p*split_plane_stride, each [N, ldw_split] bf16 with ldw_split >= ceil32(K), zero-padded.
-   * Used when non-NULL and the op has no residual / addend and K % 8 == 0; W must still be given. */
+   * Used when non-NULL, M > 64 (and above the small-batch kernel's limit), N > 64, K % 8 == 0, N % 4 == 0, ldc % 4 == 0 and
+   * C, W_split, post_mul, pre_div, pre_sub 16-byte aligned, ldw_split % 8 == 0; a residual, an addend or a gate goes along
+   * when it is 16-byte aligned with ldr / ldadd % 4 == 0 (else the exact-f32 kernels serve the op); W must still be given. */
   const void* W_split; int64_t ldw_split; int64_t split_plane_stride;
   /* Optional side output (ABI 32), used by the library's own training path (usflows_hip_internal.h); NULL: off. */
   void* A_planes_out; int64_t ldp_out; int64_t planes_out_stride;
