@@ -14,7 +14,7 @@ CASES = ["synth_d7_k3_hh0_laplace", "synth_d16_k3_densenn_relu", "synth_d7_k3_hh
          "synth_d16_k4_hh2_conj_laplace", "synth_d33_k3_lu2_hh1", "synth_d7_k3_soft_ctx", "synth_d64_k6_hh0_laplace",
          "init_d2_k4_hh0_laplace", "synth_d16_k3_hh0_radialinf", "synth_d16_k3_hh1_radial2",
          "synth_d16_k4_hh0_conj_radial1",
-         # the vector ConvNet conditioner with GatedMLP / LayerNormVector blocks (training.py: _coupling_backward_general)
+         # the vector ConvNet conditioner with GatedMLP / LayerNormVector blocks (training_rows.py: coupling_backward_general)
          "synth_d16_k3_convnet_gated_ln", "synth_d33_k2_convnet_gated_conj", "synth_d64_k3_convnet_ln", "init_d4_k2_convnet_default"]
 
 
@@ -237,7 +237,7 @@ def test_bound_flat_gradients_accumulate_like_autograd(name):
         assert torch.allclose(named[n].grad, g1[n], rtol=1e-6, atol=1e-7 * float(g1[n].abs().max())), n
 
 
-# ---- the training step on the planes pipeline (round 5): engine._build_plan_planes(train=True) + TrainPath._backward_body_planes ----
+# ---- the training step on the planes pipeline (round 5): engine._build_plan_planes(train=True) + training_planes.backward_body ----
 def _planes_flow(D, K, hidden, conj=False, hh=0, base="laplace", seed=3):
     from oracle.synth import ModelSpec, synth_state_dict
     spec = ModelSpec(dim=D, coupling_blocks=K, hidden_dims=hidden, householder=hh, affine_conjugation=conj, base=base)
@@ -278,6 +278,47 @@ def test_planes_training_path_gradients_match_oracle_autograd(D, K, hidden, conj
         assert err <= 2e-4 * ref.abs().max().item(), (pname, err, ref.abs().max().item())
         checked += 1
     assert checked >= 5
+
+
+def test_alternating_passes_of_two_flows_leave_nothing_to_each_other():
+    """Two flows through one process in the order A, B, A, B -- A on the planes training plan, B on the fp32-row plan with queued
+    gradient jobs, two Householder vectors per block and therefore the unbatched chain rule: every pass gives, bit for bit, the
+    gradients of a fresh TrainPath that ran its flow alone.  Whatever one backward pass knows (deferral, the reduce queue, the
+    LU row map, the touched set, ...) must not reach the next one."""
+    from usflows_amd import _ext, training
+
+    def flow_a():
+        spec, sd = _planes_flow(136, 3, [72], False, 0)
+        flow = build_flow(spec, sd)
+        eng = flow.engine()
+        eng.use_planes, eng.planes_min_rows, eng.fused_min_rows, eng.train_planes_min_rows = True, 0, 0, 0
+        g = torch.Generator().manual_seed(7)
+        return flow, TrainPath(flow), torch.rand(37, 136, generator=g), torch.randn(37, generator=g)
+
+    def flow_b():
+        spec, sd, a = load_case("synth_d16_k4_hh2_conj_laplace")
+        flow = build_flow(spec, sd)
+        return flow, TrainPath(flow), a["x"], torch.randn(a["x"].shape[0], generator=torch.Generator().manual_seed(1))
+
+    def step(flow, path, x, g_lp):
+        for p in flow.parameters():
+            p.grad = None
+        assert path.supported(x, None)
+        (training.log_prob_with_grad(path, x, None) * g_lp).sum().backward()
+        return {n: p.grad.clone() for n, p in flow.named_parameters() if p.grad is not None}
+
+    alone = [step(*make()) for make in (flow_a, flow_b)]
+    both = [flow_a(), flow_b()]
+    for rnd in (1, 2):
+        for k, (flow, path, x, g_lp) in enumerate(both):
+            got = step(flow, path, x, g_lp)
+            assert got.keys() == alone[k].keys() and len(got) >= 6
+            for n in got:
+                assert torch.equal(got[n], alone[k][n]), (rnd, "AB"[k], n)
+    plans = [next(p for p in flow.engine()._plans.values() if p.get("grad_arena") is not None) for flow, *_ in both]
+    assert plans[0].get("planes_train") and not plans[1].get("planes_train")
+    assert both[1][1].defer_small_grads and both[1][2].shape[0] <= _ext.GRAD_JOB_MAX_ROWS          # B's gradient jobs were queued
+    assert any(type(t).__name__ == "HouseholderTransform" and t.nvs == 2 for t in both[1][0].modules())
 
 
 @pytest.mark.parametrize("name", ["synth_d7_k3_hh0_laplace", "synth_d16_k4_hh2_conj_laplace", "synth_d16_k4_hh0_conj_radial1",

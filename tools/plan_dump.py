@@ -1,7 +1,8 @@
 """Canonical dumps of what the host side of the flat-flow path hands to the library, for comparing two checkouts on the CPU.
 
     python tools/plan_dump.py plans  > plans.txt     # one record per plan of a fixed list of configurations (--only NAME...: a part)
-    python tools/plan_dump.py trace  > trace.txt     # the call sequence of one log_prob_with_grad + backward per configuration
+    python tools/plan_dump.py trace  > trace.txt     # the call sequence of one log_prob_with_grad + backward per configuration,
+                                                     # and the gradient arena's hash after it and after a second pass
 
 Both run without a GPU under tests/emulator.py's emulation of the entry points (the library is loaded for its host-only
 answers).  Every pointer is written as (tensor it falls in, byte offset): a workspace tensor by its ``ws`` key, every other
@@ -430,7 +431,14 @@ class Trace:
         return out
 
 
-def trace_one(title, flow, eng, x, ctx, g_lp, emit, defer=True, fused=None, vctx=False):
+def _sha(t):
+    import torch
+    return hashlib.sha1(t.detach().contiguous().reshape(-1).view(torch.uint8).numpy().tobytes()).hexdigest()
+
+
+def trace_one(title, flow, eng, x, ctx, g_lp, emit, defer=True, fused=None, vctx=False, want_dx=False):
+    """one record: the calls of the first log_prob_with_grad + backward, then the gradient arena's hash after that pass and
+    after a second pass on the same path and input (want_dx: the input requires grad; its gradient is hashed as well)"""
     import emulator
     import emulator_ctx
     import emulator_vctx
@@ -455,10 +463,25 @@ def trace_one(title, flow, eng, x, ctx, g_lp, emit, defer=True, fused=None, vctx
         path.defer_small_grads = defer
         if fused is not None:
             eng.use_fused_coupling = fused
+        if want_dx:
+            x = x.clone().requires_grad_(True)
         assert path.supported(x, ctx)
-        lp = training.log_prob_with_grad(path, x, ctx)
-        (lp * g_lp).sum().backward()
-        plan = eng._plan("backward", x.shape[0], x.device, ctx is not None, "nat", train=True)
+        hashes = []
+        for nth in ("first", "second"):
+            x.grad = None
+            lp = training.log_prob_with_grad(path, x, ctx)
+            (lp * g_lp).sum().backward()
+            if nth == "first":
+                n_first = len(tr.calls)
+                keep = eng.use_train_planes
+                if want_dx:                        # (TrainPath.forward: the input's gradient leaves the fp32-row plan)
+                    eng.use_train_planes = False
+                plan = eng._plan("backward", x.shape[0], x.device, ctx is not None, "nat", train=True)
+                eng.use_train_planes = keep
+            hashes.append(f"arena after the {nth} backward: sha1 {_sha(plan['grad_arena']['flat'])}"
+                          + (f" dx {_sha(x.grad)}" if want_dx else ""))
+        hashes[1] += f" calls={len(tr.calls) - n_first}"
+        del tr.calls[n_first:]
         named = [(f"param:{k}", p) for k, p in flow.named_parameters()] + [("x", x), ("g_lp", g_lp)]
         if ctx is not None:
             named.append(("ctx", ctx))
@@ -468,9 +491,11 @@ def trace_one(title, flow, eng, x, ctx, g_lp, emit, defer=True, fused=None, vctx
         names = Names(plan["ws"], [plan["pk"], {k: v for k, v in vars(eng).items() if k not in ("_ws", "_plans")},
                                    {k: v for k, v in vars(path).items() if k not in ("flow", "eng", "_cur")}], named)
         flags = sorted({k for m in plan["meta"] for k in ("tiny", "hidden_saved", "hidden_saved_fused") if m.get(k)})
-        head = [f"== {title}: planes_train={bool(plan.get('planes_train'))} deferred={bool(getattr(path, '_defer', False))} "
+        ps = plan.get("bwd_pass")                  # the recorded backward's pass object (a tree from before it: the path's attribute)
+        deferred = ps.defer if ps is not None else getattr(path, "_defer", False)
+        head = [f"== {title}: planes_train={bool(plan.get('planes_train'))} deferred={bool(deferred)} "
                 f"flags={flags} calls={len(tr.calls)}"]
-        emit(head + tr.lines(names))
+        emit(head + tr.lines(names) + hashes)
     finally:
         patch.undo()
 
@@ -522,7 +547,30 @@ def dump_trace(emit):
     g_lp = torch.randn(a["x"].shape[0], generator=torch.Generator().manual_seed(1))
     trace_one(f"f32 general conditioner: synth_d16_k3_convnet_gated_ln B={a['x'].shape[0]}", flow, flow.engine(), a["x"].contiguous(),
               None, g_lp, emit)
-    return n + 2
+    n += 2
+    # fp32 rows: an input that requires grad (the first layer's data gradient; one case at a padded dim), a block of two LU
+    # factors (the unbatched chain rule through _to_leaves's torch graph), a DenseNN without a context layer
+    for title, name, want_dx in (("f32 input gradient", "synth_d7_k3_hh0_laplace", True),
+                                 ("f32 input gradient, padded dim", "init_d2_k4_hh0_laplace", True),
+                                 ("f32 two LU factors per block", "synth_d33_k3_lu2_hh1", False),
+                                 ("f32 DenseNN", "synth_d16_k3_densenn_relu", False)):
+        spec, sd, a = load_case(name)
+        flow = build_flow(spec, sd)
+        g_lp = torch.randn(a["x"].shape[0], generator=torch.Generator().manual_seed(1))
+        trace_one(f"{title}: {name} B={a['x'].shape[0]}", flow, flow.engine(), a["x"].contiguous(), None, g_lp, emit, want_dx=want_dx)
+        n += 1
+    # a trainable Normal / Laplace base (its parameter gradients: one pass over the latent), fp32 rows and planes
+    from golden_util import load_trainable_base_case
+    for name in ("tbase_d16_k3_hh0_normal_scalar_scale", "tbase_d160_k2_hh0_laplace"):
+        spec, sd, x = load_trainable_base_case(name)[:3]
+        flow = build_flow(spec, sd)
+        eng = flow.engine()
+        if spec.dim >= 128:
+            eng.use_planes, eng.planes_min_rows, eng.fused_min_rows, eng.train_planes_min_rows = True, 0, 0, 0
+        g_lp = torch.full((x.shape[0],), -1.0 / x.shape[0])
+        trace_one(f"trainable base: {name} B={x.shape[0]}", flow, eng, x.contiguous(), None, g_lp, emit)
+        n += 1
+    return n
 
 
 def main():

@@ -141,7 +141,7 @@ class FlatPlanMixin:
 
     def _tiny_served(self, pk, cp, op, ws, i, B, train, device, ctx_dim: int = 0) -> bool:
         """the library's own answer for a layer tiny_coupling() admits: the tiny-layer kernel serves the forward descriptor and,
-        for a training plan whose backward chain runs fused (training.py: _fused_cbwd), the backward one (usf_coupling_variant,
+        for a training plan whose backward chain runs fused (training_rows.py: fused_cbwd), the backward one (usf_coupling_variant,
         host-only).  Otherwise the layer takes the unfused ops: the f32 kernel rejects hidden_out / GATE"""
         lib = _ext.load()
         # (a vector context's LDS segments count against the kernel's budget: usf_coupling_additive_vctx_variant knows)

@@ -43,7 +43,7 @@ class PlanesPlanMixin:
         else:
             use = bool(self.use_planes)
         if train:
-            # the training step on the planes pipeline (round 5; training.py `_backward_planes`): log_prob plans in the bf16x3
+            # the training step on the planes pipeline (round 5; training_planes.py `backward_body`): log_prob plans in the bf16x3
             # format whose couplings all run as ONE fused launch (conditioners of <= 2 hidden layers up to 256 wide), from
             # train_planes_min_rows rows; every planes buffer below 2 GiB (usf_wgrad_blocked_f32's offsets)
             use = (self.use_train_planes and direction == "backward" and self.gemm_mode == "bf16x3" and self.use_fused_coupling
@@ -185,7 +185,7 @@ class PlanesPlanMixin:
             f["zeros"] = zeros
         return f
 
-    # ---- training on the planes pipeline: the backward launches' weight images (training.py `_backward_body_planes`) ----
+    # ---- training on the planes pipeline: the backward launches' weight images (training_planes.py `backward_body`) ----
     def planes_dgrad_image(self, pk, m) -> torch.Tensor:
         """weight planes of an affine layer's data gradient g_in = g_out W as a usf_gemm_planes_bf16x3 operand: rows = the
         positions of the layer's INPUT layout (segp), K axis = the slots of its OUTPUT layout"""
