@@ -617,6 +617,15 @@ int usf_conv2d_same_band_variant(const usf_conv_band_query* q, usf_conv_band_inf
  * TN = column-block width in 32-feature blocks (4 or 5, whichever pads the output less); 0 for empty extents */
 int usf_gemm_planes_variant(const usf_gemm_planes_desc* d);
 
+/* which instantiation of coupling_planes_kernel serves the descriptor as usf_coupling_planes (has_ctx == has_side == 0),
+ * usf_coupling_planes_ctx (has_ctx != 0) or usf_coupling_planes_side (has_side != 0) -- an ADDED entry point, as the pair above.
+ * Nothing is launched and no pointer is dereferenced (the descriptor's pointers are tested for NULL and alignment only):
+ *   70000 + 1000 NPL + 100 NH + 10 MODE + 2 CTX + SIDE
+ * NPL = 3 (USF_PLANES_BF16X3) or 2 (USF_PLANES_F16X2), NH = n_hidden, MODE = 0 inference / 1 hidden_out / 2 USF_ACT_GATE; the code
+ * comes from the very branches that launch.  0 for M == 0; the negative value the launch would return for a descriptor it
+ * rejects (usf_last_error set). */
+int usf_coupling_planes_variant(const usf_coupling_planes_desc* d, int32_t has_ctx, int32_t has_side);
+
 /* The backward twin of usf_gated_norm_rows_f32 (usflows_hip.h; ABI 34): what torch.autograd derives from GatedMLP's gate (networks.py:222-245) and LayerNormVector
  * (:206-219) in Flow.fit, rows of [M, C] fp32, r / mean / variance recomputed from (skip, vg) as the forward computes them:
  *     g = dy * gamma;  dr = (g - mean_c g - xh * mean_c(g xh)) / sqrt(var r + eps)        (gamma == NULL: dr = dy)

@@ -340,6 +340,7 @@ INTERNAL_SYMBOLS = {
     "usf_linear_variant": (C.c_int, [C.POINTER(LinearDesc)]),
     "usf_gemm_planes_variant": (C.c_int, [C.POINTER(GemmPlanesDesc)]),
     "usf_coupling_variant": (C.c_int, [C.POINTER(CouplingDesc)]),
+    "usf_coupling_planes_variant": (C.c_int, [C.POINTER(CouplingPlanesDesc), C.c_int32, C.c_int32]),
     "usf_radial_logprob_grad_workspace": (C.c_int64, [C.c_int64, C.c_int64]),
     "usf_radial_logprob_grad_f32": (C.c_int, [_fp, C.c_int64, _fp, _fp, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int32, C.c_int32,
                                               _fp, _fp, _fp, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_void_p]),

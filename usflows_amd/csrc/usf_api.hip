@@ -87,6 +87,7 @@ int gather_cols(const float* src, int64_t lds_, float* dst, int64_t ldd, int64_t
 int pack_planes(const usf_pack_planes_desc* d, hipStream_t stream);
 int gemm_planes(const usf_gemm_planes_desc* d, hipStream_t stream);
 int gemm_planes_variant(const usf_gemm_planes_desc* d);
+int coupling_planes_variant(const usf_coupling_planes_desc* d, int has_ctx, int has_side);
 int coupling_planes(const usf_coupling_planes_desc* d, hipStream_t stream);
 int coupling_planes_ctx(const usf_coupling_planes_desc* d, const float* ctx, int64_t ctx_stride, const float* w_ctx, const float* b_ctx,
                         hipStream_t stream);
@@ -297,6 +298,9 @@ int usf_coupling_planes_side(const usf_coupling_planes_desc* d, const void* side
   return usf::coupling_planes_side(d, side, side_nkb, (hipStream_t)stream);
 }
 int usf_gemm_planes_variant(const usf_gemm_planes_desc* d) { return usf::gemm_planes_variant(d); }
+int usf_coupling_planes_variant(const usf_coupling_planes_desc* d, int32_t has_ctx, int32_t has_side) {
+  return usf::coupling_planes_variant(d, has_ctx, has_side);
+}
 int usf_coupling_variant(const usf_coupling_desc* d) { return usf::coupling_variant(d); }
 int usf_coupling_additive_vctx_f32(const usf_coupling_desc* d, const float* ctx, int64_t ld_ctx, int32_t ctx_dim, const float* W_ctx_t,
                                    int64_t ldw_ctx, const float* b_ctx, usf_stream_t stream) {

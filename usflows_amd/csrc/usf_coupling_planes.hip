@@ -546,8 +546,17 @@ __global__ __launch_bounds__(512, 2) void coupling_planes_kernel(const CplPArgs 
 unsigned long long* g_cdbg = nullptr;
 #endif
 
+// one instantiation: launched (launch == true) or only named -- the code usf_coupling_planes_variant reports, from the very
+// branch that launches
+template <int NPL, int NH, int MODE, bool CTX, bool SIDE>
+static int coupling_planes_go(const CplPArgs& a, dim3 grid, hipStream_t stream, bool launch) {
+  if (launch) hipLaunchKernelGGL((coupling_planes_kernel<NPL, NH, MODE, CTX, SIDE>), grid, dim3(512), 0, stream, a);
+  return 70000 + 1000 * NPL + 100 * NH + 10 * MODE + 2 * (CTX ? 1 : 0) + (SIDE ? 1 : 0);
+}
+
+// launch == false: nothing is launched and no pointer is dereferenced; the return value is the instantiation's code
 static int coupling_planes_launch(const usf_coupling_planes_desc* d, const float* ctx, int64_t ctx_stride, const float* w_ctx,
-                                  const float* b_ctx, const void* side, int64_t side_nkb, hipStream_t stream) {
+                                  const float* b_ctx, const void* side, int64_t side_nkb, hipStream_t stream, bool launch = true) {
   if (!d) { set_error("usf_coupling_planes: null descriptor"); return -1; }
   if (ctx) {
     if (d->act == USF_ACT_GATE) { set_error("usf_coupling_planes_ctx: USF_ACT_GATE takes no context (the context enters no data gradient)"); return -2; }
@@ -645,20 +654,20 @@ static int coupling_planes_launch(const usf_coupling_planes_desc* d, const float
       a.hout[i] = reinterpret_cast<char*>(d->hidden_out[i]);
       a.gate[i] = reinterpret_cast<const char*>(gated ? d->gate[i] : nullptr);
     }
-    const dim3 block(512);
-#define USF_CPT(NH_, MODE_) hipLaunchKernelGGL((coupling_planes_kernel<3, NH_, MODE_>), grid, block, 0, stream, a)
-#define USF_CPTC(NH_) hipLaunchKernelGGL((coupling_planes_kernel<3, NH_, 1, true>), grid, block, 0, stream, a)
+    int code = 0;
+#define USF_CPT(NH_, MODE_) code = coupling_planes_go<3, NH_, MODE_, false, false>(a, grid, stream, launch)
+#define USF_CPTC(NH_) code = coupling_planes_go<3, NH_, 1, true, false>(a, grid, stream, launch)
     if (gated) { if (d->n_hidden == 1) USF_CPT(1, 2); else USF_CPT(2, 2); }
     else if (ctx) { if (d->n_hidden == 1) USF_CPTC(1); else USF_CPTC(2); }
     else { if (d->n_hidden == 1) USF_CPT(1, 1); else USF_CPT(2, 1); }
 #undef USF_CPTC
 #undef USF_CPT
-    return check_launch("usf_coupling_planes");
+    return launch ? check_launch("usf_coupling_planes") : code;
   }
-  const dim3 block(512);
-#define USF_CPL(NPL_, NH_) hipLaunchKernelGGL((coupling_planes_kernel<NPL_, NH_>), grid, block, 0, stream, a)
-#define USF_CPLC(NPL_, NH_) hipLaunchKernelGGL((coupling_planes_kernel<NPL_, NH_, 0, true>), grid, block, 0, stream, a)
-#define USF_CPLS(NPL_, NH_) hipLaunchKernelGGL((coupling_planes_kernel<NPL_, NH_, 0, false, true>), grid, block, 0, stream, a)
+  int code = 0;
+#define USF_CPL(NPL_, NH_) code = coupling_planes_go<NPL_, NH_, 0, false, false>(a, grid, stream, launch)
+#define USF_CPLC(NPL_, NH_) code = coupling_planes_go<NPL_, NH_, 0, true, false>(a, grid, stream, launch)
+#define USF_CPLS(NPL_, NH_) code = coupling_planes_go<NPL_, NH_, 0, false, true>(a, grid, stream, launch)
   if (side) {
     if (npl == 2) {
       switch (d->n_hidden) { case 1: USF_CPLS(2, 1); break; case 2: USF_CPLS(2, 2); break; default: USF_CPLS(2, 3); break; }
@@ -679,7 +688,15 @@ static int coupling_planes_launch(const usf_coupling_planes_desc* d, const float
 #undef USF_CPLS
 #undef USF_CPLC
 #undef USF_CPL
-  return check_launch("usf_coupling_planes");
+  return launch ? check_launch("usf_coupling_planes") : code;
+}
+
+// which instantiation serves the descriptor (usflows_hip_internal.h: usf_coupling_planes_variant).  The launch path itself with
+// the launches left out: stand-in addresses take the place of the context / side operands, which it only tests and aligns.
+int coupling_planes_variant(const usf_coupling_planes_desc* d, int has_ctx, int has_side) {
+  const float* const stand_in = reinterpret_cast<const float*>(uintptr_t(0x1000));
+  return coupling_planes_launch(d, has_ctx ? stand_in : nullptr, has_ctx ? 1 : 0, has_ctx ? stand_in : nullptr,
+                                has_ctx ? stand_in : nullptr, has_side ? stand_in : nullptr, (has_side && d) ? d->nk_t : 0, nullptr, false);
 }
 
 int coupling_planes_ctx(const usf_coupling_planes_desc* d, const float* ctx, int64_t ctx_stride, const float* w_ctx,
