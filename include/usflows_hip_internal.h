@@ -666,8 +666,12 @@ int usf_lu_grad_finish_f64(const double* dL, const double* dU, const double* TL,
  *   aligned (ld % 4 == 0).  workspace: at least usf_wgrad_workspace_floats(M,N,K) floats.  mode 0: exact-f32 MFMA;
  *   mode 1: the bf16x3 split of DESIGN.md 3.1b (fp32-equivalent accuracy on the bf16 matrix cores; used from M >= 2048;
  *   from 8192 rows with enough output tiles to fill the chip, and while (M + 448) * max(ldy, lda) * 4 < 2^32, the
- *   loader-wave kernel: it reads Y / A with 16-byte loads up to the end of the row extent ((M-1) * ld + N resp. K
- *   floats from the base pointer) -- the same memory the contract above names).
+ *   loader-wave kernel: it reads Y / A with 8-byte buffer loads bounded by the end of the row extent ((M-1) * ld + N resp.
+ *   K floats from the base pointer) -- the same memory the contract above names; with an odd N or K the pair that holds
+ *   the last column of row M - 1 straddles that bound and the hardware still returns its in-range half (the bound is
+ *   checked per dword: measured, tests/test_wgrad_kernels_gpu.py).  Rows >= M are never read; columns [N, ld) / [K, ld)
+ *   of rows < M may be read and only reach outputs that are not stored (a NaN there is harmless).  A row range may come
+ *   out EMPTY (usf_wgrad_plan): its partial image is all zeros.  The workspace need be no larger than reported.
  * usf_wgrad_variant: which kernel such a call launches -- 0 exact-f32, 1 bf16x3 (256 threads), 2 bf16x3 with loader
  *   waves (introspection for the parity tests).
  * usf_colsum_f32: out[n] = alpha * sum_m Y[m,n] + beta * out[n]           -- the bias gradient; workspace
@@ -678,6 +682,17 @@ int usf_wgrad_f32(const float* Y, int64_t ldy, const float* A, int64_t lda, int6
                   usf_stream_t stream);
 int64_t usf_wgrad_workspace_floats(int64_t M, int64_t N, int64_t K);
 int usf_wgrad_variant(int64_t M, int64_t N, int64_t K, int64_t ldy, int64_t lda, int32_t mode);
+/* usf_wgrad_plan (an addition: USF_INTERNAL_VERSION is unchanged; host only, launches nothing, needs no GPU): what a
+ * usf_wgrad_f32 (with_colsum = 0) or usf_wgrad_bias_f32 (with_colsum = 1) call of these sizes launches, answered from the code
+ * the call itself launches from (introspection for the parity tests).  Writes 8 values and returns 8 (cap >= 8), < 0 on bad
+ * arguments or where usf_wgrad_bias_ok refuses the column sums:
+ *   out[0] usf_wgrad_variant, out[1] row ranges, out[2] rows per range (a multiple of 32; the last range may be shorter, or
+ *   EMPTY -- its partial image is then all zeros), out[3] 1: one range written straight to G, no reduction launch,
+ *   out[4] grid blocks (tiles * row ranges rounded up to 8; surplus blocks leave at once), out[5] threads per block,
+ *   out[6] 1: a reduction launch follows, out[7] the workspace floats the call insists on (never more than
+ *   usf_wgrad_workspace_floats). */
+int usf_wgrad_plan(int64_t M, int64_t N, int64_t K, int64_t ldy, int64_t lda, int32_t mode, int32_t with_colsum, int64_t* out,
+                   int32_t cap);
 /* usf_wgrad_f32 and the layer's bias gradient in one pass (ABI 32): colsum_out[n] = cs_alpha * sum_m Y[m,n] + cs_beta *
  * colsum_out[n] (what usf_colsum_f32 computes), from the operand fragments the bf16x3 kernels hold anyway -- three more
  * MFMAs per fragment row against an operand of ones in the blocks of tile column 0; partial sums in a fixed order.  Only
@@ -697,7 +712,11 @@ int usf_colsum_f32(const float* Y, int64_t ldy, int64_t M, int64_t N, float* out
  * splits the layer input, the data-gradient GEMM the output gradient), or as usf_split_planes_f32 writes them:
  *   plane p of an operand at base + p * plane_stride elements, each [ceil32(M), ld] bf16 row-major, ld % 8 == 0,
  *   plane_stride % 8 == 0, plane_stride >= ceil32(M) * ld, 16-byte aligned base, rows [M, ceil32(M)) zero,
- *   the three planes of one operand below 4 GiB; x == p0 + p1 + p2 exactly (round-to-nearest residual split).
+ *   the three planes of one operand below 4 GiB; x == p0 + p1 + p2 (round-to-nearest residual split) -- bit for bit for
+ *   2^-110 <= |x| < 2^127 and for zeros (measured on the device, both load paths, tests/test_wgrad_kernels_gpu.py): below
+ *   2^-110 the third plane's bits fall under bf16's smallest subnormal 2^-133 and are rounded there (an error of at most
+ *   2^-134, absolute); from 2^127 a mantissa above 1.fe rounds the first plane to infinity.  Gradients and activations of
+ *   the training path lie inside the range or are flushed to it without harm (an absolute error of 2^-134 per value).
  * usf_wgrad_planes_f32: G[n,k] = alpha * sum_m Y[m, y_off + n] * A[m, a_off + k] + beta * G[n,k]  (y_off, a_off % 8 == 0)
  *   -- the same six products per value pair in the same order as usf_wgrad_f32 mode 1, one block per CU over row ranges
  *   of equal length, partial sums added in a fixed order (bitwise reproducible).  workspace: at least
@@ -717,6 +736,18 @@ int usf_wgrad_planes_f32(const void* Y_planes, int64_t ldyp, int64_t y_plane_str
 int64_t usf_wgrad_planes_workspace_floats(int64_t M, int64_t N, int64_t K);
 int usf_wgrad_planes_ok(int64_t M, int64_t N, int64_t K);
 int usf_wgrad_planes_colsum_ok(int64_t M, int64_t N, int64_t K);
+/* usf_wgrad_planes_plan (an addition: USF_INTERNAL_VERSION is unchanged; host only, launches nothing): the schedule a
+ * usf_wgrad_planes_f32 / usf_wgrad_blocked_f32 call with this workspace launches from, chosen by the code the calls choose with.
+ * workspace_floats < 0: the size usf_wgrad_planes_workspace_floats reports.  cus > 0: that many compute units instead of the
+ * device's (no GPU needed, as in usf_conv_wgrad_wide_variant); cus = 0: the device's.  Tile classes c = 3 * (type in n) + (type
+ * in k), types 0 normal (128 wide), 1 wide (128 + a folded remainder of up to 16), 2 edge (the remainder alone); class 4 does not
+ * exist.  Writes 35 values and returns 35 (cap >= 35), < 0 on bad arguments / no schedule:
+ *   out[0] 1 balanced, 0 plain grid; out[1], out[2] the remainder of N, of K rides in the last normal tile; out[3] grid blocks;
+ *   out[4] items; out[5] the workspace floats the call insists on (with_colsum: the partial column sums included); out[6] partial
+ *   images; out[7 + c] tiles, out[16 + c] row ranges (= partials), out[25 + c] rows per range of class c; out[34] the workspace
+ *   the answer assumed. */
+int usf_wgrad_planes_plan(int64_t M, int64_t N, int64_t K, int64_t workspace_floats, int32_t with_colsum, int32_t cus, int64_t* out,
+                          int32_t cap);
 int usf_split_planes_f32(const float* X, int64_t ldx, int64_t M, int64_t N, void* planes, int64_t ldp, int64_t plane_stride,
                          usf_stream_t stream);
 /* The same weight gradient with both operands in the BLOCKED planes format of the planes pipeline (ABI 33) -- the buffers the

@@ -182,6 +182,8 @@ int wgrad(const float* Y, int64_t ldy, const float* A, int64_t lda, int64_t M, i
           int64_t ldg, float alpha, float beta, int32_t mode, float* workspace, int64_t workspace_floats,
           hipStream_t stream, float* colsum_out = nullptr, float cs_alpha = 0.f, float cs_beta = 0.f);
 int wgrad_bias_ok(int64_t M, int64_t N, int64_t K, int64_t ldy, int64_t lda, int32_t mode);
+int wgrad_plan(int64_t M, int64_t N, int64_t K, int64_t ldy, int64_t lda, int32_t mode, int32_t with_colsum, int64_t* out, int32_t cap);
+int wgrad_planes_plan(int64_t M, int64_t N, int64_t K, int64_t workspace_floats, int32_t with_colsum, int32_t cus, int64_t* out, int32_t cap);
 int affine_prep(const float* Lr, const float* Ur, const float* bias, const float* vk, const float* w0, int64_t n, int32_t C,
                 int32_t nvs, float* M, float* Minv, float* b, float* cvec, float* ladj, float* save, hipStream_t stream);
 int affine_prep_bwd(const float* save, const float* bias, const float* vk, const float* w0, const float* Minv, const float* b,
@@ -584,6 +586,13 @@ int usf_wgrad_bias_ok(int64_t M, int64_t N, int64_t K, int64_t ldy, int64_t lda,
 }
 int usf_wgrad_variant(int64_t M, int64_t N, int64_t K, int64_t ldy, int64_t lda, int32_t mode) {
   return usf::wgrad_variant(M, N, K, ldy, lda, mode);
+}
+int usf_wgrad_plan(int64_t M, int64_t N, int64_t K, int64_t ldy, int64_t lda, int32_t mode, int32_t with_colsum, int64_t* out, int32_t cap) {
+  return usf::wgrad_plan(M, N, K, ldy, lda, mode, with_colsum, out, cap);
+}
+int usf_wgrad_planes_plan(int64_t M, int64_t N, int64_t K, int64_t workspace_floats, int32_t with_colsum, int32_t cus, int64_t* out,
+                          int32_t cap) {
+  return usf::wgrad_planes_plan(M, N, K, workspace_floats, with_colsum, cus, out, cap);
 }
 int64_t usf_wgrad_workspace_floats(int64_t M, int64_t N, int64_t K) {
   int64_t out = 0;

@@ -864,6 +864,38 @@ int wgrad_bias_ok(int64_t M, int64_t N, int64_t K, int64_t ldy, int64_t lda, int
   return (wgrad_variant(M, N, K, ldy, lda, mode) >= 1 && K >= 64) ? 1 : 0;     // either bf16x3 kernel
 }
 
+// what a usf_wgrad_f32 / usf_wgrad_bias_f32 call launches: wgrad() launches from this, usf_wgrad_plan reports it
+struct WgPlan {
+  int variant, splits, rows, direct, reduce, threads;
+  unsigned grid;
+  int64_t tiles, need;         // need: workspace floats the call asks for
+};
+static WgPlan wg_plan(int64_t M, int64_t N, int64_t K, int64_t ldy, int64_t lda, int32_t mode, bool cs) {
+  WgPlan p;
+  p.tiles = wg_tiles(N, K);
+  p.variant = wgrad_variant(M, N, K, ldy, lda, mode);
+  p.splits = pick_splits(M, p.tiles, p.variant == 2);
+  p.need = (int64_t)p.splits * N * (K + (cs ? 1 : 0));
+  int rows = (int)((M + p.splits - 1) / p.splits);
+  rows = (rows + WB_S - 1) / WB_S * WB_S;
+  p.rows = rows > 0 ? rows : WB_S;
+  p.direct = (p.splits == 1 && !cs) ? 1 : 0;
+  p.reduce = (p.splits > 1 || cs) ? 1 : 0;
+  p.grid = (unsigned)(p.tiles * ((p.splits + 7) / 8) * 8);
+  p.threads = p.variant == 2 ? 768 : 256;
+  return p;
+}
+
+// usf_wgrad_plan: see include/usflows_hip_internal.h
+int wgrad_plan(int64_t M, int64_t N, int64_t K, int64_t ldy, int64_t lda, int32_t mode, int32_t with_colsum, int64_t* out, int32_t cap) {
+  if (M < 0 || N <= 0 || K <= 0 || !out || cap < 8 || (mode != 0 && mode != 1)) { set_error("usf_wgrad_plan: bad arguments"); return -1; }
+  if (with_colsum && !wgrad_bias_ok(M, N, K, ldy, lda, mode)) { set_error("usf_wgrad_plan: no column sums for this call (usf_wgrad_bias_ok)"); return -2; }
+  const WgPlan p = wg_plan(M, N, K, ldy, lda, mode, with_colsum != 0);
+  out[0] = p.variant; out[1] = p.splits; out[2] = p.rows; out[3] = p.direct; out[4] = p.grid; out[5] = p.threads; out[6] = p.reduce;
+  out[7] = p.need;
+  return 8;
+}
+
 int wgrad(const float* Y, int64_t ldy, const float* A, int64_t lda, int64_t M, int64_t N, int64_t K, float* G,
           int64_t ldg, float alpha, float beta, int32_t mode, float* workspace, int64_t workspace_floats,
           hipStream_t stream, float* colsum_out, float cs_alpha, float cs_beta) {
@@ -882,28 +914,27 @@ int wgrad(const float* Y, int64_t ldy, const float* A, int64_t lda, int64_t M, i
   }
   if (mode != 0 && mode != 1) { set_error("usf_wgrad_f32: mode must be 0 (exact f32) or 1 (bf16x3)"); return -2; }
   // the split-precision kernels pay off once the chip has real work (the operand split costs VALU per slab)
-  const int64_t tiles = wg_tiles(N, K);
-  const int variant = wgrad_variant(M, N, K, ldy, lda, mode);
+  const WgPlan pl = wg_plan(M, N, K, ldy, lda, mode, colsum_out != nullptr);
+  const int64_t tiles = pl.tiles;
+  const int variant = pl.variant;
   const bool lw = variant == 2;
-  const int splits = pick_splits(M, tiles, lw);
-  if (workspace_floats < (int64_t)splits * N * (K + (colsum_out ? 1 : 0))) {
+  const int splits = pl.splits;
+  if (workspace_floats < pl.need) {
     set_error("usf_wgrad_f32: workspace too small (%lld < %lld floats)", (long long)workspace_floats,
               (long long)splits * N * (K + 1));
     return -4;
   }
-  int rows = (int)((M + splits - 1) / splits);
-  rows = (rows + WB_S - 1) / WB_S * WB_S;
-  WgradArgs a{Y, ldy, A, lda, workspace, (int)M, (int)N, (int)K, rows > 0 ? rows : WB_S, G, ldg, alpha, beta,
-              (splits == 1 && !colsum_out) ? 1 : 0, (int)tiles, splits, nullptr, nullptr};
+  WgradArgs a{Y, ldy, A, lda, workspace, (int)M, (int)N, (int)K, pl.rows, G, ldg, alpha, beta,
+              pl.direct, (int)tiles, splits, nullptr, nullptr};
   if (colsum_out) a.cs_part = workspace + (int64_t)splits * N * K;
 #ifdef USF_STAMP
   a.dbg = g_wdbg;
 #endif
-  const unsigned grid = (unsigned)(tiles * ((splits + 7) / 8) * 8);
+  const unsigned grid = pl.grid;
   if (lw) wgrad_lw_kernel<<<grid, 768, 0, stream>>>(a);
   else if (variant == 1) wgrad_bf16x3_kernel<<<grid, 256, 0, stream>>>(a);
   else wgrad_kernel<<<grid, 256, 0, stream>>>(a);
-  if (splits > 1 || colsum_out) {
+  if (pl.reduce) {
     int64_t rb = (N * K + 255) / 256;
     if (rb > 4096) rb = 4096;
     reduce_partials_kernel<<<(unsigned)rb, 256, 0, stream>>>(workspace, splits, N, K, G, ldg, alpha, beta, a.cs_part, colsum_out,

@@ -583,9 +583,10 @@ int wp_env(const char* name, int dflt) { return (int)tuning(name, dflt); }
 
 // balanced = false: the plain grid -- no folding, every tile cut into the same `plain_splits` row ranges (the partial sums
 // are then those of usf_wgrad_f32's loader-wave kernel, bit for bit)
-bool wp_schedule(int64_t M, int64_t N, int64_t K, bool balanced, int plain_splits, WpSched& sc) {
+// cus_in > 0: that many compute units instead of the device's (usf_wgrad_planes_plan: no GPU needed)
+bool wp_schedule(int64_t M, int64_t N, int64_t K, bool balanced, int plain_splits, WpSched& sc, int cus_in = 0) {
   memset(&sc, 0, sizeof(sc));
-  const int cus = wp_cus();
+  const int cus = cus_in > 0 ? ((cus_in & ~7) < 8 ? 8 : (cus_in & ~7)) : wp_cus();
   const int S = (int)((M + WP_S - 1) / WP_S);                  // slabs
   sc.per_xcd = cus / 8;
   sc.fN = (int)(N / WP_T); sc.fK = (int)(K / WP_T);
@@ -718,6 +719,35 @@ int64_t wgrad_planes_workspace_floats(int64_t M, int64_t N, int64_t K) {
 // column sums ride along where the first wave column of tile column 0 is full (64 columns: the instantiations that carry them)
 int wgrad_planes_colsum_ok(int64_t M, int64_t N, int64_t K) { return (M > 0 && N > 0 && K >= 64) ? 1 : 0; }
 
+// the schedule a usf_wgrad_planes_f32 / usf_wgrad_blocked_f32 call launches from (both calls and usf_wgrad_planes_plan choose here):
+// 1 balanced, 0 the plain grid, -1 none
+static int wp_choose(int64_t M, int64_t N, int64_t K, int64_t workspace_floats, WpSched& sc, int cus = 0) {
+  const bool balanced = wp_env("wgrad_sched", 1) != 0 && wp_schedule(M, N, K, true, 0, sc, cus) &&
+                        (int64_t)wp_max_parts(sc) * N * (K + 1) <= workspace_floats;
+  if (!balanced && !wp_schedule(M, N, K, false, wp_plain_splits(M, N, K), sc, cus)) return -1;
+  return balanced ? 1 : 0;
+}
+
+// usf_wgrad_planes_plan: see include/usflows_hip_internal.h
+int wgrad_planes_plan(int64_t M, int64_t N, int64_t K, int64_t workspace_floats, int32_t with_colsum, int32_t cus, int64_t* out, int32_t cap) {
+  if (M <= 0 || N <= 0 || K <= 0 || !out || cap < 35) { set_error("usf_wgrad_planes_plan: bad arguments"); return -1; }
+  WpSched sc;
+  int64_t ws = workspace_floats;
+  if (ws < 0) {                                 // usf_wgrad_planes_workspace_floats at `cus` compute units
+    int m = wp_plain_splits(M, N, K);
+    if (wp_schedule(M, N, K, true, 0, sc, cus) && wp_max_parts(sc) > m) m = wp_max_parts(sc);
+    ws = (int64_t)m * N * (K + 1);
+  }
+  const int kind = wp_choose(M, N, K, ws, sc, cus);
+  if (kind < 0) { set_error("usf_wgrad_planes_plan: no schedule for M=%lld N=%lld K=%lld", (long long)M, (long long)N, (long long)K); return -2; }
+  out[0] = kind; out[1] = sc.foldN; out[2] = sc.foldK; out[3] = sc.per_xcd * 8; out[4] = sc.items;
+  out[5] = (int64_t)wp_max_parts(sc) * N * (K + (with_colsum ? 1 : 0));
+  out[6] = wp_max_parts(sc);
+  for (int c = 0; c < 9; ++c) { out[7 + c] = sc.T[c]; out[16 + c] = sc.nseg[c]; out[25 + c] = sc.rows[c]; }
+  out[34] = ws;
+  return 35;
+}
+
 int wgrad_planes(const void* Yp, int64_t ldyp, int64_t ystride, int64_t y_off, const void* Ap, int64_t ldap, int64_t astride,
                  int64_t a_off, int64_t M, int64_t N, int64_t K, float* G, int64_t ldg, float alpha, float beta, float* colsum_out,
                  float cs_alpha, float cs_beta, float* workspace, int64_t workspace_floats, hipStream_t stream) {
@@ -746,9 +776,7 @@ int wgrad_planes(const void* Yp, int64_t ldyp, int64_t ystride, int64_t y_off, c
 #ifdef USF_STAMP
   a.dbg = g_wpdbg;
 #endif
-  const bool balanced = wp_env("wgrad_sched", 1) != 0 && wp_schedule(M, N, K, true, 0, a.sched) &&
-                        (int64_t)wp_max_parts(a.sched) * N * (K + 1) <= workspace_floats;
-  if (!balanced && !wp_schedule(M, N, K, false, wp_plain_splits(M, N, K), a.sched)) {
+  if (wp_choose(M, N, K, workspace_floats, a.sched) < 0) {
     set_error("usf_wgrad_planes_f32: no schedule for M=%lld N=%lld K=%lld", (long long)M, (long long)N, (long long)K);
     return -2;
   }
@@ -786,9 +814,7 @@ int wgrad_blocked(const void* Yp, int64_t y_nkb, int64_t y_kb0, const void* Ap, 
   WpArgs a{(const __bf16*)Yp, 0, 0, (const __bf16*)Ap, 0, 0, 0, 0, (unsigned)yb, (unsigned)ab,
            workspace, (int)M, (int)N, (int)K, nullptr, nullptr, (int)y_nkb, (int)y_kb0, (int)a_nkb, (int)a_kb0};
   // the same schedules as usf_wgrad_planes_f32 (one block per CU where the tiles allow it, else the plain grid)
-  const bool balanced = wp_env("wgrad_sched", 1) != 0 && wp_schedule(M, N, K, true, 0, a.sched) &&
-                        (int64_t)wp_max_parts(a.sched) * N * (K + 1) <= workspace_floats;
-  if (!balanced && !wp_schedule(M, N, K, false, wp_plain_splits(M, N, K), a.sched)) {
+  if (wp_choose(M, N, K, workspace_floats, a.sched) < 0) {
     set_error("usf_wgrad_blocked_f32: no schedule for M=%lld N=%lld K=%lld", (long long)M, (long long)N, (long long)K);
     return -2;
   }
