@@ -73,7 +73,8 @@ int usf_internal_version(void);
  * sizeof(usf_gated_norm_bwd_desc|usf_wgrad_job|usf_wreduce_job|usf_wplanes_job) for kind 13|14|15|16 and
  * sizeof(usf_adam_chunk|usf_grad_chunk|usf_conv_variant_query|usf_conv_variant) for kind 17|18|19|20 and
  * sizeof(usf_conv_wgrad_query|usf_conv_wgrad_info|usf_ln_bwd_info) for kind 21|22|23 and
- * sizeof(usf_conv_band_query|usf_conv_band_info) for kind 27|28.
+ * sizeof(usf_conv_band_query|usf_conv_band_info) for kind 27|28 and
+ * sizeof(usf_conv_wgrad_band_query|usf_conv_wgrad_band_info) for kind 29|30.
  */
 
 /*
@@ -428,6 +429,58 @@ int usf_conv_wgrad_k4_f32(const float* x, const float* dy, int64_t B, int64_t ci
                           float* workspace, int64_t workspace_floats, usf_stream_t stream);
 int usf_conv_wgrad_k4_variant(const usf_conv_wgrad_query* q, usf_conv_wgrad_wide_info* out);
 int usf_conv_wgrad_k4_instances(int32_t* out, int32_t cap);
+
+/*
+ * usf_conv_wgrad_band_f32 (an addition: USF_INTERNAL_VERSION is unchanged): the contract and the argument list of
+ * usf_conv_wgrad_wide_f32 -- dW [cout, cin, ks, ks] and db [cout] (or NULL) of a stride-1 "same" convolution with kernel 1 or 3
+ * from x (with in_act, in_mul, pre_sub) and dy, exact fp32 on v_mfma_f32_16x16x4_f32, fixed-order sums, the same bits on every
+ * run, no atomics -- for the feature maps that kernel refuses: 257 .. 4096 pixels (usf_conv_wgrad_band.hip).  The wide kernel's
+ * decomposition with another GROUP: a persistent 256-thread block stages a band of RB consecutive rows of ONE sample (x rows
+ * r0 - pad .. r0 + RB - 1 + pad, dy rows r0 .. r0 + RB - 1; group g = sample g / bands, band g % bands), walks its groups in
+ * ascending order and keeps its accumulators across them.  One more argument, band_rows: 0 = the plan's band, > 0 caps it (a test
+ * and measurement aid, as usf_conv2d_same_band_f32 has).
+ * Served: ks 1 or 3, 1 <= cin, cout <= 64 (any value), 1 <= W <= 64 (W == 1 included), H * W <= 4096 (small maps too: the wide
+ * kernel's sums in another order), B >= 1, B * bands < 2^31, provided a band fits the 160 KiB of LDS:
+ *     kernel 3: S = W + 1, n = 4 * ceil(((RB - 1) * S + W) / 4), CSy = 2odd(n), CSx = 2odd(n + 2 * S + 2)
+ *     kernel 1: CSx = CSy = 2odd(4 * ceil(RB * W / 4))
+ *     4 * ((16 * ceil(cin / 16) + 1) * CSx + 64 + 16 * ceil(cout / 16) * CSy) <= 163840 bytes
+ * (+ 1 row and 64 floats: db's operand, ones in every 16th chunk of four positions, read by column j of the bias tile 16 - j
+ * chunks in, so that db is the fixed-order sum of 16 chains a sixteenth as long -- a block's chains span all its groups)
+ * -- and, at kernel 3, that the largest such RB is at least 4 or the whole map (refused: 49 .. 64 channels on both sides at
+ * W = 64, where one to three rows fit and the halo rows would outweigh the band).  The plan (usf_conv_wgrad_band_plan.h) takes the
+ * largest RB that fits; a batch with fewer groups than compute units takes a lower band, down to 4 rows; the bands are evened
+ * out (the same number of bands, ceil(H / bands) rows each); band_rows caps the result as it is.  Returns 1 (nothing written) for
+ * other shapes, 0 when done, < 0 on error (nothing written either).  workspace: at least usf_conv_wgrad_band_workspace(...,
+ * band_rows) floats (0: not served); it depends on the device's compute units and on the tuning knob conv_wgrad_band_blocks
+ * (> 0 caps the grid: a test aid, as conv_wgrad_blocks).  Two or three launches in stream order, no host synchronisation.
+ *
+ * usf_conv_wgrad_band_variant: the whole plan such a call launches from (host only; cus > 0 plans for that many compute units and
+ * needs no GPU, blocks_per_cu > 0 for that residency).  served 0 / 1; band_rows (of this launch), best_rows (the plan's own
+ * choice, before the cap), fit_rows (the most the LDS holds), bands, last_rows (of a sample's last band), staged_rows = band_rows
+ * + 2 * pad, groups = B * bands, grid = min(groups, cus * min(blocks_per_cu, 2)) under the knob, lds_bytes; tiles, tiles_per_wave
+ * (the instantiation, one of usf_conv_wgrad_band_instances), wave_groups, position_parts, slots = grid * position_parts summed
+ * in `rounds` (1 or 2) rounds, the first of two with rows_used rows of `per` slots, as in usf_conv_wgrad_wide_info;
+ * max_groups_per_block = ceil(groups / grid); the geometry (S, q0, CSx, CSy, nch, nacc); and the multiply-high divisions of the
+ * staging loops: m_x, m_y, m_w = ceil(2^32 / d) for d = staged_rows * W, band_rows * W, W (0: d == 1), applied to dividends up to
+ * max_dividend (m_w: below staged_rows * W).  usf_sizeof_desc reports sizeof(usf_conv_wgrad_band_query|_info) for kind 29|30.
+ */
+typedef struct usf_conv_wgrad_band_query {
+  int64_t B, cin, cout, H, W, ks;
+  int32_t band_rows, cus, blocks_per_cu, reserved;
+} usf_conv_wgrad_band_query;
+typedef struct usf_conv_wgrad_band_info {
+  int32_t served, band_rows, best_rows, fit_rows, bands, last_rows, staged_rows, groups;
+  int32_t grid, lds_bytes, CIT, COT, T, tiles, tiles_per_wave, wave_groups;
+  int32_t position_parts, slots, rounds, per, rows_used, max_groups_per_block, blocks_per_cu, cus;
+  int32_t S, q0, CSx, CSy, nch, nacc, max_dividend, reserved;
+  uint32_t m_x, m_y, m_w, reserved2;
+} usf_conv_wgrad_band_info;
+int64_t usf_conv_wgrad_band_workspace(int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks, int64_t band_rows);
+int usf_conv_wgrad_band_f32(const float* x, const float* dy, int64_t B, int64_t cin, int64_t cout, int64_t H, int64_t W, int64_t ks,
+                            const float* in_mul, const float* pre_sub, int32_t in_act, float in_slope, float* dW, float* db,
+                            float* workspace, int64_t workspace_floats, int64_t band_rows, usf_stream_t stream);
+int usf_conv_wgrad_band_variant(const usf_conv_wgrad_band_query* q, usf_conv_wgrad_band_info* out);
+int usf_conv_wgrad_band_instances(int32_t* out, int32_t cap);
 
 /*
  * usf_conv2d_same_pad_f32 (an addition: USF_INTERNAL_VERSION is unchanged): usf_conv2d_same_f32 (usflows_hip.h) with the

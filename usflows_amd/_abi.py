@@ -176,6 +176,22 @@ class ConvBandInfo(C.Structure):
                [(n, C.c_int32) for n in ("stage_iters", "CTX", "PC_full", "PR_full", "PC_last", "PR_last", "best_rows", "reserved")]
 
 
+class ConvWgradBandQuery(C.Structure):
+    """usf_conv_wgrad_band_query: one call of usf_conv_wgrad_band_f32, as usf_conv_wgrad_band_variant is asked about it"""
+    _fields_ = [("B", C.c_int64), ("cin", C.c_int64), ("cout", C.c_int64), ("H", C.c_int64), ("W", C.c_int64), ("ks", C.c_int64),
+                ("band_rows", C.c_int32), ("cus", C.c_int32), ("blocks_per_cu", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ConvWgradBandInfo(C.Structure):
+    """usf_conv_wgrad_band_info: the whole plan usf_conv_wgrad_band_f32 launches from -- the band, the grid, the instantiation, the
+    reduction, the LDS geometry and the staging loops' multiply-high divisions"""
+    _fields_ = [(n, C.c_int32) for n in ("served", "band_rows", "best_rows", "fit_rows", "bands", "last_rows", "staged_rows", "groups",
+                                         "grid", "lds_bytes", "CIT", "COT", "T", "tiles", "tiles_per_wave", "wave_groups",
+                                         "position_parts", "slots", "rounds", "per", "rows_used", "max_groups_per_block",
+                                         "blocks_per_cu", "cus", "S", "q0", "CSx", "CSy", "nch", "nacc", "max_dividend", "reserved")] + \
+               [(n, C.c_uint32) for n in ("m_x", "m_y", "m_w", "reserved2")]
+
+
 CONV_ENTRIES = {"plain": 0, "ctx": 1, "res": 2, "gate_mul": 3, "gate_add": 4, "gated": 5}   # USF_CONV_ENTRY_*
 
 
@@ -267,7 +283,8 @@ SIZEOF_KINDS = {OP_LINEAR: LinearDesc, OP_COUPLING: CouplingDesc, 0: Op, 3: LuPr
                 OP_GEMM_PLANES: GemmPlanesDesc, OP_COUPLING_PLANES: CouplingPlanesDesc, 8: MtChunk, OP_GATED_NORM: GatedNormDesc,
                 OP_CALL: CallDesc, 11: GradJob, 12: PsumJob, 13: GatedNormBwdDesc, 14: WgradJob, 15: WReduceJob, 16: WPlanesJob, 17: AdamChunk, 18: GradChunk,
                 19: ConvVariantQuery, 20: ConvVariant, 21: ConvWgradQuery, 22: ConvWgradInfo, 23: LnBwdInfo, 24: ConvWgradWideInfo,
-                25: ChannelAffineBwdQuery, 26: ChannelAffineBwdInfo, 27: ConvBandQuery, 28: ConvBandInfo}
+                25: ChannelAffineBwdQuery, 26: ChannelAffineBwdInfo, 27: ConvBandQuery, 28: ConvBandInfo,
+                29: ConvWgradBandQuery, 30: ConvWgradBandInfo}
 
 
 # every symbol include/usflows_hip.h declares (the stable public ABI): (restype, argtypes)
@@ -432,4 +449,10 @@ for _stem in ("usf_conv_wgrad_wide", "usf_conv_wgrad_k5", "usf_conv_wgrad_k4"): 
         _stem + "_f32": INTERNAL_SYMBOLS["usf_conv_wgrad_f32"],
         _stem + "_variant": (C.c_int, [C.POINTER(ConvWgradQuery), C.POINTER(ConvWgradWideInfo)]),
         _stem + "_instances": (C.c_int, [C.POINTER(C.c_int32), C.c_int32])})
+_wide = INTERNAL_SYMBOLS["usf_conv_wgrad_wide_f32"]
+INTERNAL_SYMBOLS.update({                                                                # the same contract + band_rows in front of the stream
+    "usf_conv_wgrad_band_workspace": (C.c_int64, [C.c_int64] * 7),
+    "usf_conv_wgrad_band_f32": (_wide[0], _wide[1][:-1] + [C.c_int64] + _wide[1][-1:]),
+    "usf_conv_wgrad_band_variant": (C.c_int, [C.POINTER(ConvWgradBandQuery), C.POINTER(ConvWgradBandInfo)]),
+    "usf_conv_wgrad_band_instances": (C.c_int, [C.POINTER(C.c_int32), C.c_int32])})
 SYMBOLS = {**PUBLIC_SYMBOLS, **INTERNAL_SYMBOLS}

@@ -24,7 +24,7 @@ from ._abi import (  # noqa: E402,F401  -- the declarations, re-exported: caller
     BASE_LPNORM1, BASE_LPNORM2, BASE_LPNORMINF, BASE_ROWSUM, NORM_LOGNORMAL, NORM_GAMMA, NORM_RAW_PARAMS, NORM_WEIBULL, NORM_HALFNORMAL, NORM_CHI, RADIAL_MAX_K, OP_LINEAR,
     OP_COUPLING, OP_PACK_PLANES, OP_GEMM_PLANES, OP_COUPLING_PLANES, OP_GATED_NORM, OP_CALL, PLANES_BF16X3, PLANES_F16X2, CALL_FNS,
     FN_COUPLING_PLANES_CTX, FN_COUPLING_VCTX, FN_GEMM_PLANES_SIDE, FN_COUPLING_PLANES_SIDE, VCTX_MAX,
-    _fp, LinearDesc, CouplingDesc, PackPlanesDesc, GemmPlanesDesc, CouplingPlanesDesc, MtChunk, AdamChunk, GradChunk, ConvVariantQuery, ConvVariant, ConvBandQuery, ConvBandInfo, ConvWgradQuery, ConvWgradInfo, ConvWgradWideInfo, ChannelAffineBwdQuery, ChannelAffineBwdInfo, LnBwdInfo, CONV_ENTRIES, GatedNormDesc, GatedNormBwdDesc,
+    _fp, LinearDesc, CouplingDesc, PackPlanesDesc, GemmPlanesDesc, CouplingPlanesDesc, MtChunk, AdamChunk, GradChunk, ConvVariantQuery, ConvVariant, ConvBandQuery, ConvBandInfo, ConvWgradQuery, ConvWgradInfo, ConvWgradWideInfo, ConvWgradBandQuery, ConvWgradBandInfo, ChannelAffineBwdQuery, ChannelAffineBwdInfo, LnBwdInfo, CONV_ENTRIES, GatedNormDesc, GatedNormBwdDesc,
     CallDesc, _OpUnion, Op, LuPrepDesc, PackJob, PsumJob, WgradJob, WReduceJob, WPlanesJob, GradJob, SIZEOF_KINDS, PUBLIC_SYMBOLS,
     INTERNAL_SYMBOLS, SYMBOLS)
 
@@ -697,6 +697,19 @@ def conv_wgrad_wide_instances() -> list:
     return _conv_wgrad_direct_instances("usf_conv_wgrad_wide")
 
 
+def conv_wgrad_band_variant(B, cin, cout, H, W, ks=3, band_rows=0, cus=0, blocks_per_cu=0) -> dict:
+    """usf_conv_wgrad_band_variant: the whole plan usf_conv_wgrad_band_f32 launches from for these sizes, as a dict of the answer's
+    fields (served 0: the call returns 1); cus / blocks_per_cu > 0 plan for that device answer (cus > 0: no GPU needed)"""
+    q = ConvWgradBandQuery(int(B), int(cin), int(cout), int(H), int(W), int(ks), int(band_rows), int(cus), int(blocks_per_cu), 0)
+    out = ConvWgradBandInfo()
+    check(load().usf_conv_wgrad_band_variant(C.byref(q), C.byref(out)), "usf_conv_wgrad_band_variant")
+    return {name: int(getattr(out, name)) for name, _ in ConvWgradBandInfo._fields_ if not name.startswith("reserved")}
+
+
+def conv_wgrad_band_instances() -> list:
+    return _conv_wgrad_direct_instances("usf_conv_wgrad_band")
+
+
 def conv_wgrad_k5_instances() -> list:
     return _conv_wgrad_direct_instances("usf_conv_wgrad_k5")
 
@@ -1069,6 +1082,24 @@ def _conv_wgrad_direct(entry, x, dy, ks, in_mul=None, pre_sub=None, in_act=ACT_N
 def conv_wgrad_wide(x, dy, ks, **transforms):
     """usf_conv_wgrad_wide_f32: feature maps of up to 256 pixels and any channel counts up to 64, kernel 1 and 3"""
     return _conv_wgrad_direct("usf_conv_wgrad_wide_f32", x, dy, ks, **transforms)
+
+
+def conv_wgrad_band(x, dy, ks, in_mul=None, pre_sub=None, in_act=ACT_NONE, in_slope=0.0, want_bias=True, band_rows=0):
+    """usf_conv_wgrad_band_f32: feature maps of up to 4096 pixels (W <= 64) and any channel counts up to 64, kernel 1 and 3 ->
+    (dW [cout, cin, ks, ks], db | None), or None when the shape is not served.  band_rows > 0 caps the band's rows (tests,
+    measurements).  Stream-ordered like its siblings: a captured training step replays it"""
+    B, cin, H, W = x.shape
+    cout = dy.shape[1]
+    ws_n = load().usf_conv_wgrad_band_workspace(B, cin, cout, H, W, ks, int(band_rows))
+    if ws_n <= 0:
+        return None
+    ws = torch.empty(ws_n, dtype=torch.float32, device=x.device)
+    dW = torch.empty(cout, cin, ks, ks, dtype=torch.float32, device=x.device)
+    db = torch.empty(cout, dtype=torch.float32, device=x.device) if want_bias else None
+    rc = _launch("usf_conv_wgrad_band_f32", (x.data_ptr(), dy.data_ptr(), B, cin, cout, H, W, ks, ptr(in_mul), ptr(pre_sub), int(in_act),
+                 float(in_slope), dW.data_ptr(), ptr(db), ws.data_ptr(), ws_n, int(band_rows), current_stream(x.device)),
+                 tape=False, unserved_ok=True)
+    return None if rc else (dW, db)
 
 
 def conv_wgrad_k5(x, dy, **transforms):

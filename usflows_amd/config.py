@@ -68,6 +68,7 @@ class Config:
         conv_k5=False,             # image flows: 5 x 5 "same" convolutions on usf_conv2d_same_f32 / _ctx_f32, their weight gradients on usf_conv_wgrad_k5_f32, and what the search's hidden widths 8 and 64 need beside them (a 64-channel GatedConv's gate convolution in two halves, kernel-1 weight gradients of channel counts off multiples of 16 on the wide kernel) (off: torch's convolution and autograd there; measured against the parent: ahead in six of eight workloads, behind at 64 hidden channels at 100 rows and at batch 32: profiles/conv5_bench.json)
         conv_k4=False,             # image flows: 4 x 4 convolutions with padding="same" (torch's placement: one zero before, two after) on usf_conv2d_same_f32 / _ctx_f32, their data gradients on the mirrored placement (usf_conv2d_same_pad_f32), their weight gradients on usf_conv_wgrad_k4_f32, and the two side routes conv_k5 opens (either knob opens them) (off: torch's convolution and autograd there; ships off: the refusal of kernel 4 at the default configuration is pinned by tests/test_conv5_cpu.py)
         conv_band=True,            # image flows, inference: "same" convolutions (kernel 1 / 3) on feature maps of 257 .. 4096 pixels (MNIST [1, 28, 28], CIFAR [3, 32, 32] without space-to-depth) on the row-banded kernel usf_conv2d_same_band_f32 (0: torch's convolution there; measured against the parent: every workload ahead beyond the spread, profiles/conv_band_bench.json)
+        train_band=False,          # image flows, training: feature maps of 257 .. 4096 pixels on the device -- forward and data gradient on the row-banded kernel usf_conv2d_same_band_f32 (needs conv_band), weight gradients on usf_conv_wgrad_band_f32 (off: torch autograd + MIOpen there; ships off: the torch route at the default configuration is pinned by tests/test_image_large_gpu.py::test_fit_keeps_torch_autograd; measured against the parent: profiles/image_band_train_bench.json)
         gated_tail=True,           # image training, few pixels: GatedConv's 1x1 conv + gate + ReLU + layer norm as one launch each way
     )
 

@@ -266,6 +266,8 @@ int usf_sizeof_desc(int32_t kind) {
     case 26: return (int)sizeof(usf_channel_affine_bwd_info);
     case 27: return (int)sizeof(usf_conv_band_query);
     case 28: return (int)sizeof(usf_conv_band_info);
+    case 29: return (int)sizeof(usf_conv_wgrad_band_query);
+    case 30: return (int)sizeof(usf_conv_wgrad_band_info);
     default: return -1;
   }
 }

@@ -14,7 +14,7 @@ import torch
 from . import _ext
 from .config import config
 
-BAND_MIN_PIXELS = 257    # feature maps of 257 .. 4096 pixels: usf_conv2d_same_f32 refuses them, usf_conv2d_same_band_f32 serves them (inference)
+BAND_MIN_PIXELS = 257    # feature maps of 257 .. 4096 pixels: usf_conv2d_same_f32 refuses them, usf_conv2d_same_band_f32 serves them (training: knob train_band)
 WIDE_MIN_PIXELS = 65      # feature maps of 65 .. 256 pixels: usf_conv_wgrad_f32 refuses them, usf_conv_wgrad_wide_f32 serves them
 
 
@@ -53,18 +53,26 @@ def pointwise_geometry(conv) -> bool:
 
 
 def band_conv_ok(cin: int, cout: int, H: int, W: int, ks: int) -> bool:
-    """inference only, under the knob ``conv_band``: a "same" convolution on a feature map too large for usf_conv2d_same_f32
-    (more than 256 pixels) that the row-banded kernel serves (usf_conv2d_same_band_f32: kernel 1 / 3, up to 64 channels, up to
-    4096 pixels, W <= 64, a band of at least 4 rows beside the weight planes in the LDS).  Training does not ask this rule:
-    no weight-gradient kernel serves such maps"""
+    """under the knob ``conv_band``: a "same" convolution on a feature map too large for usf_conv2d_same_f32 (more than 256
+    pixels) that the row-banded kernel serves (usf_conv2d_same_band_f32: kernel 1 / 3, up to 64 channels, up to 4096 pixels,
+    W <= 64, a band of at least 4 rows beside the weight planes in the LDS).  Inference asks it per convolution; training asks
+    it in both directions (``train_band_ok``) under the knob ``train_band``"""
     return bool(config.conv_band) and H * W >= BAND_MIN_PIXELS and ks in (1, 3) and \
         _ext.load().usf_conv2d_same_band_fits(cin, cout, H, W, ks) > 0
+
+
+def train_band_ok(cin: int, cout: int, H: int, W: int, ks: int) -> bool:
+    """under the knob ``train_band``: forward (cin -> cout) and data gradient (cout -> cin) of a convolution on a map above 256
+    pixels both run on the row-banded kernel.  64 -> 64 channels at kernel 3 do not (no four rows beside the weight planes),
+    nor kernel 4 / 5, nor maps wider than 64: those layers stay on torch"""
+    return bool(config.train_band) and band_conv_ok(cin, cout, H, W, ks) and band_conv_ok(cout, cin, H, W, ks)
 
 
 # ---- the weight gradient's route ------------------------------------------------------------------------------------------------
 def wgrad_kernels(ks: int, pixels: int) -> tuple:
     """names of the weight-gradient kernels tried for a ks x ks convolution on a feature map of `pixels`, in order:
-    kernel 5 / 4: usf_conv_wgrad_k5_f32 / _k4_f32 at every pixel count, under their knobs; 65 pixels and more:
+    kernel 5 / 4: usf_conv_wgrad_k5_f32 / _k4_f32 at every pixel count, under their knobs; kernel 1 / 3 at 257 pixels and more,
+    under the knob ``train_band``: usf_conv_wgrad_band_f32 alone (the others refuse every such map); 65 pixels and more:
     usf_conv_wgrad_wide_f32 (knob ``wgrad_wide``) -- without a try of the narrow kernel first: it refuses every map above 64
     pixels (pinned by tests/test_wide_wgrad_cpu.py::test_the_old_queries_answer_what_they_answered_before); up to 64 pixels
     usf_conv_wgrad_f32 as ever, and under ``conv_k5`` / ``conv_k4`` (either) what it refuses (channel counts that are no
@@ -74,6 +82,8 @@ def wgrad_kernels(ks: int, pixels: int) -> tuple:
         return ("k5",) if config.conv_k5 else ()
     if ks == 4:
         return ("k4",) if config.conv_k4 else ()
+    if pixels >= BAND_MIN_PIXELS and config.train_band:
+        return ("band",)
     if pixels >= WIDE_MIN_PIXELS:
         return ("wide",) if config.wgrad_wide else ()
     return ("narrow",) + (("wide",) if config.wgrad_wide and (config.conv_k5 or config.conv_k4) else ())
@@ -85,13 +95,15 @@ def _workspace_query(entry: str):
 
 # name: (served query (B, cin, cout, H, W, ks, masked), launch (x, dy, ks, defer, owners, transforms) -> (dW, db) | None).
 # The narrow kernel's two forms differ (64 -> 64 channels at kernel 1 and 57 .. 64 pixels run without a mask only), so its plan
-# answers for the asked form; the other three are one kernel for both forms: their workspace is > 0 or the shape is refused.
+# answers for the asked form; the other four are one kernel for both forms: their workspace is > 0 or the shape is refused.
 # Only the narrow kernel may queue its last sum (defer / owners); the others' launches run in stream order.  The launches look
 # their binding up on _ext when called.
 WGRAD_KERNELS = {
     "narrow": (lambda B, cin, cout, H, W, ks, masked: _ext.conv_wgrad_kernel(B, cin, cout, H, W, ks, masked) != 0,
                lambda x, dy, ks, defer, owners, kw: _ext.conv_wgrad(x, dy, ks, defer=defer, owners=owners, **kw)),
     "wide": (_workspace_query("usf_conv_wgrad_wide_workspace"), lambda x, dy, ks, defer, owners, kw: _ext.conv_wgrad_wide(x, dy, ks, **kw)),
+    "band": (lambda B, cin, cout, H, W, ks, masked: _ext.load().usf_conv_wgrad_band_workspace(B, cin, cout, H, W, ks, 0) > 0,
+             lambda x, dy, ks, defer, owners, kw: _ext.conv_wgrad_band(x, dy, ks, **kw)),
     "k5": (_workspace_query("usf_conv_wgrad_k5_workspace"), lambda x, dy, ks, defer, owners, kw: _ext.conv_wgrad_k5(x, dy, **kw)),
     "k4": (_workspace_query("usf_conv_wgrad_k4_workspace"), lambda x, dy, ks, defer, owners, kw: _ext.conv_wgrad_k4(x, dy, **kw)),
 }
@@ -135,6 +147,8 @@ def _dgrad_fits(cin: int, cout: int, H: int, W: int, ks: int) -> int:
 
 
 def _both_convs_fit(cin: int, cout: int, H: int, W: int, ks: int) -> bool:
+    if H * W >= BAND_MIN_PIXELS:        # (usf_conv2d_same_fits answers 0 there: the row-banded kernel or none)
+        return train_band_ok(cin, cout, H, W, ks)
     return _ext.load().usf_conv2d_same_fits(cin, cout, H, W, ks) >= 2 and _dgrad_fits(cin, cout, H, W, ks) >= 2
 
 

@@ -7,7 +7,9 @@ Each ``torch.autograd.Function`` here is one device pass of the inference path w
 * data gradients reuse the forward kernels on the transposed (and, for 3 x 3, flipped) weight:
   ``usf_conv2d_same_f32``, ``usf_pointwise_conv_f32``, ``usf_channel_affine_f32``;
 * weight / bias gradients come from ``usf_conv_wgrad_f32`` (exact fp32 on the f32 matrix instruction, deterministic) or one of
-  its three siblings of the same contract; which one is stated once, in ``image_rules.wgrad_kernels``;
+  its four siblings of the same contract; which one is stated once, in ``image_rules.wgrad_kernels``;
+* feature maps above 256 pixels (knob ``train_band``): forward and data gradient on ``usf_conv2d_same_band_f32`` (``conv_same``),
+  weight gradients on ``usf_conv_wgrad_band_f32``;
 * an affine block of up to 12 channels takes its whole backward (dx, dW, db) from ONE launch of
   ``usf_channel_affine_bwd_f32`` (knob ``affine_small_c``);
 * ``usf_layernorm_channels_bwd_f32``, ``usf_gated_residual_bwd_f32``, ``usf_act_grad_f32``, ``usf_masked_residual_f32`` and
@@ -25,7 +27,7 @@ import torch
 from . import _ext
 from .config import config
 # which kernel serves which convolution is stated in image_rules.py; the names stay importable from here
-from .image_rules import (WIDE_MIN_PIXELS, conv_ctx_shape_ok, conv_kernel_sizes, conv_shape_ok, conv_wgrad,  # noqa: F401
+from .image_rules import (BAND_MIN_PIXELS, WIDE_MIN_PIXELS, conv_ctx_shape_ok, conv_kernel_sizes, conv_shape_ok, conv_wgrad,  # noqa: F401
                           gate_halves_ok, pointwise_geometry, pointwise_shape_ok, wgrad_kernels, wgrad_route, wgrad_served,
                           wide_wgrad_served)
 
@@ -45,12 +47,25 @@ def _gate_inplace(d: torch.Tensor, h: torch.Tensor, act) -> None:
     _ext.act_grad(d, h, M=B, H=n, ldd=n, ldh=n, act=act[0], slope=act[1])
 
 
+def conv_same(x, planes, cout: int, ks: int, **kw):
+    """``_ext.conv2d_same`` up to 256 pixels, above them the row-banded kernel (``_ext.conv2d_same_band``, knob ``train_band``:
+    ``image_rules.train_band_ok`` said that it serves the shape in both directions): the ONE forward / data-gradient convolution
+    of ConvSame, ConvSameFork, ConvSameRes and ``data_grad``"""
+    if x.shape[2] * x.shape[3] >= BAND_MIN_PIXELS:
+        y = _ext.conv2d_same_band(x, planes, cout, ks, **kw)
+        if y is None:
+            raise RuntimeError(f"usflows_amd: usf_conv2d_same_band_f32 refuses a {ks} x {ks} convolution to {cout} channels on "
+                               f"{tuple(x.shape)} (train_band_ok was not consulted)")
+        return y
+    return _ext.conv2d_same(x, planes, cout, ks, **kw)
+
+
 def data_grad(dy, planes_t, cin: int, ks: int):
-    """the data gradient of a "same" convolution from the flipped, transposed weight planes: ``_ext.conv2d_same`` at an odd
+    """the data gradient of a "same" convolution from the flipped, transposed weight planes: ``conv_same`` at an odd
     kernel; at an even one the mirrored placement (``_ext.conv2d_same_pad``: two zeros before, one after at kernel 4)"""
     if ks % 2 == 0:
         return _ext.conv2d_same_pad(dy, planes_t, cin, ks, ks // 2)
-    return _ext.conv2d_same(dy, planes_t, cin, ks)
+    return conv_same(dy, planes_t, cin, ks)
 
 
 def _weight_planes(w, want_transposed: bool, param=None):
@@ -172,7 +187,8 @@ def _planes_t(ctx, w):
 
 def _input_grad(dy, planes_t, cin, ks, x, in_act, in_mul):
     """the data gradient with the input's (Leaky)ReLU and mask factors: in the data-gradient convolution's output stream where
-    usf_conv2d_same_gate_f32 takes the shape, else as passes behind the plain one"""
+    usf_conv2d_same_gate_f32 takes the shape, else (above 256 pixels always: the fused forms decline such maps) as passes
+    behind the plain one"""
     dx = None
     if in_act is not None or in_mul is not None:
         dx = _ext.conv2d_same_gate(dy, planes_t, cin, ks, x, in_act[1] if in_act is not None else 1.0, in_mul)
@@ -194,7 +210,7 @@ class ConvSame(torch.autograd.Function):
         ks = w.shape[2]
         ia, oa = _act(in_act), _act(out_act)
         planes, ctx.planes_t = _weight_planes(w, ctx.needs_input_grad[0], weight)
-        y = _ext.conv2d_same(x, planes, w.shape[0], ks, bias=None if bias is None else bias.detach().contiguous(),
+        y = conv_same(x, planes, w.shape[0], ks, bias=None if bias is None else bias.detach().contiguous(),
                              in_mul=in_mul, in_act=ia[0], in_slope=ia[1], out_act=oa[0], out_slope=oa[1])
         ctx.save_for_backward(x, w, in_mul, y if out_act is not None else None)
         ctx.cfg = (ks, in_act, out_act, bias is not None)
@@ -234,7 +250,7 @@ class ConvSameRes(torch.autograd.Function):
         b = None if bias is None else bias.detach().contiguous()
         y = _ext.conv2d_same_res(x, planes, w.shape[0], ks, rx, om, sign, bias=b)
         if y is None:
-            y = _ext.masked_residual(rx, _ext.conv2d_same(x, planes, w.shape[0], ks, bias=b), om, sign)
+            y = _ext.masked_residual(rx, conv_same(x, planes, w.shape[0], ks, bias=b), om, sign)
         ctx.save_for_backward(x, w, om)
         ctx.cfg = (ks, bias is not None, sign)
         ctx.params = (weight, bias)
@@ -265,7 +281,7 @@ class ConvSameFork(torch.autograd.Function):
         ks = w.shape[2]
         ia = _act(in_act)
         planes, ctx.planes_t = _weight_planes(w, ctx.needs_input_grad[0], weight)
-        y = _ext.conv2d_same(x, planes, w.shape[0], ks, bias=None if bias is None else bias.detach().contiguous(),
+        y = conv_same(x, planes, w.shape[0], ks, bias=None if bias is None else bias.detach().contiguous(),
                              in_mul=in_mul, in_act=ia[0], in_slope=ia[1])
         ctx.save_for_backward(x, w, in_mul)
         ctx.cfg = (ks, in_act, bias is not None)
@@ -560,7 +576,8 @@ def affine_small_c_served(B: int, C: int, P: int) -> bool:
 
 def channel_affine_train_ok(x, C) -> bool:
     """the training route of a C-channel affine block at this input: C in {16, 32, 48, 64} on the matrix-core weight gradients (as
-    ever: usf_conv_wgrad_f32 up to 64 pixels, usf_conv_wgrad_wide_f32 above); C <= 12 on usf_channel_affine_bwd_f32 at any pixel
+    ever: usf_conv_wgrad_f32 up to 64 pixels, usf_conv_wgrad_wide_f32 up to 256, above them usf_conv_wgrad_band_f32 under the knob
+    ``train_band`` -- through ``wgrad_served``; no flow fixture has such a block); C <= 12 on usf_channel_affine_bwd_f32 at any pixel
     count (knob ``affine_small_c``; off: declined, the torch route); every other C <= 64 at 65 .. 256 pixels on
     usf_conv_wgrad_wide_f32 + usf_channel_affine_f32 (knob ``wgrad_wide``), declined up to 64 pixels"""
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == C and 1 <= C <= 64):
